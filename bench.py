@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on BASELINE.json's configs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {0,1,2,3,4}]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {0,1,2,3,4}] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one navigation tick over one batch of synthetic input with everything resident in
@@ -28,6 +28,12 @@ configuration's size (strong scaling: BASELINE.json's metric is "1024^2 map, 100
 Prints ONE JSON line on rank 0, numbers only (what the keys mean: profiles/README.md, "the bench line"), shorter than
 6 KB with the summary of every regime LAST (`summary`), because the driver's record keeps the tail of the line.
 `value` = agents x steps / wall time of the K timed steps (barrier + synchronize on both sides, max over ranks).
+
+A plain run only sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`, the workload).
+`--full` adds everything else, run behind the timed steps as before: profiled kernel groups and the roofline, the
+sustained 100-tick world, shared fields, the crowded world, the reference on the host cores (cpu_baseline, drop-in,
+state pass) and, with N > 1 ranks, the weak-scaled job.  `--dump-outputs DIR` writes what the last timed step
+computed (dump_outputs) before any of that runs.
 """
 import argparse
 import hashlib
@@ -431,6 +437,31 @@ def run_ticks(T, pdist, torch, warmup, steps, early=None):
     return dt, ticks
 
 
+DUMP_AGENTS = 2_000_000        # --dump-outputs: agents beyond this many are sampled (20 B each in the dump)
+DUMP_FIELDS = 256              # --dump-outputs: chunk fields of the pool written (16 KB each as float32)
+
+
+def dump_outputs(T, out_dir):
+    """What the last timed tick handed its caller, as float32 DIR/<name>.npy (at most ~44 MB): the new position, velocity
+    and status of every agent this rank steps (a fixed, seeded sample of DUMP_AGENTS when there are more) and the
+    direction codes of a fixed, seeded sample of DUMP_FIELDS chunk fields of the field pool.  Called after the timed
+    steps have been synchronised and before anything else runs on the world."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    rows = np.arange(T.a0, T.a1)
+    if len(rows) > DUMP_AGENTS:
+        rows = np.sort(np.random.RandomState(1).choice(rows, DUMP_AGENTS, replace=False))
+    slots = np.arange(T.req_begin, T.req_end)
+    if len(slots) > DUMP_FIELDS:
+        slots = np.sort(np.random.RandomState(2).choice(slots, DUMP_FIELDS, replace=False))
+    out = {"pos_xz": T.t["pos_xz"].cpu().numpy()[rows], "vel_xz": T.t["vel_xz"].cpu().numpy()[rows],
+           "status": T.status.cpu().numpy()[rows],
+           "field_dirs": T.pool.index_select(0, torch.from_numpy(slots).to(T.pool.device)).cpu().numpy()}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -464,7 +495,15 @@ def main():
     ap.add_argument("--no-pipeline-fields", action="store_true",
                     help="build a tick's fields inside that tick, in front of its agent step (default: the fields "
                          "of tick t+1 are built during tick t, beside the agent step; same work, same results)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too (profiled kernel groups, roofline, sustained, "
+                         "shared fields, crowded world, cpu baseline, drop-in, state pass, weak scaling); a plain run "
+                         "only times the steps")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(relaunch_under_torchrun(args.gpus))
     cfg = dict(CONFIGS[args.config])
@@ -512,11 +551,59 @@ def main():
     T = make(args.crowded)
     fields_ahead, tick_every = T.pipeline_fields, T.tick_every
     request_source, los_source, velocity_source = T.request_source, T.los_source, T.velocity_source
-    early = {}
+    early = {} if args.full else None         # (--full: the last warm-up ticks are profiled ones, same trajectory)
     dt, ticks = run_ticks(T, pdist, torch, args.warmup, args.steps, early)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(T, args.dump_outputs)
+    host_enqueue_ms, tick_driver = T.host_enqueue_ms, getattr(T, "tick_driver", "python (tick.py)")
+    agents_total = T.N
+    cells_total = T.n_req_total * 4096
+    ms_per_step = dt / args.steps * 1e3
+    value = agents_total * args.steps / dt
+    cells_key = "flow_field_cells_kept_valid_per_s" if cfg["obstacles"] else "flow_field_cells_per_s"
+
+    def headline():
+        """The keys every line starts with: the metric, the timed steps and the workload."""
+        dims = T_dims(cfg, world, shared)
+        backend = torch.distributed.get_backend() if torch.distributed.is_initialized() else "none"
+        return {
+            "metric": "agent-steps/sec (+ flow-field cells/sec), every chunk field rebuilt + every agent stepped per tick",
+            "value": value, "unit": "agent-steps/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+            "scaling": None if world == 1 else ("strong" if shared else "weak"), "vs_baseline": None,
+            "dtype": "u64-bitmask/u8 fields, f32 agents (f64 exp)", "data": "synthetic",
+            "config": {"workload": "BASELINE configs[%d]%s: %dx%d cells, %d flow fields%s = %d chunk fields, %d agents%s"
+                                   % (args.config, " crowded" if args.crowded else "", dims[0], dims[1], cfg["fields"],
+                                      "" if shared or world == 1 else "/GPU", cells_total // 4096, agents_total,
+                                      ", %d obstacles" % cfg["obstacles"] if cfg["obstacles"] else ""),
+                       "baseline_config": args.config, "map_chunks": cfg["map"], "flow_fields": cfg["fields"],
+                       "agents": cfg["agents"], "hz": 20, "dynamic_obstacles": cfg["obstacles"],
+                       "parallelism": "requests by destination + uid slabs x%d, 1 all-gather (16 B/agent) per tick"
+                                      % world,
+                       "ranks": world, "rccl_ranks": pdist.comm_ranks(), "backend": backend,
+                       "tile_exchange": args.tile_exchange,
+                       "requests": "reference planner fixture" if "fixture" in request_source else "numpy stand-in",
+                       "has_dest_los": "device lookup" if "device lookup" in los_source else "0",
+                       "initial_velocities": "flow aligned" if "flow" in velocity_source else "N(0,0.35)",
+                       "fields_ahead": bool(fields_ahead), "tick_driver": tick_driver,
+                       "library": ("NAVHIP_LIB override: " + os.path.basename(os.environ["NAVHIP_LIB"]))
+                                  if os.environ.get("NAVHIP_LIB") else "libnavhip.so (in-tree)"},
+        }
+
+    if not args.full:
+        if rank == 0:
+            line = headline()
+            line[cells_key] = cells_total * args.steps / dt
+            line["summary"] = {"ms_per_step": ms_per_step, "ms_per_step_median": float(np.median(ticks)),
+                               "host_enqueue_ms": host_enqueue_ms, "ranks": world}
+            print(json.dumps(r4(line), separators=(",", ":")), flush=True)
+        T.close()
+        if torch.distributed.is_initialized():
+            torch.distributed.destroy_process_group()
+        return
+
     phases = T.phase_ms()
     hist = status_histogram(T)
-    host_enqueue_ms, tick_driver = T.host_enqueue_ms, getattr(T, "tick_driver", "python (tick.py)")
     fields_in_tick_ms, fields_in_tick_samples = T.fields_in_tick_ms, T.fields_in_tick_samples
 
     # per-kernel-group durations at the END of the run (the world has crowded by then); the same
@@ -525,11 +612,6 @@ def main():
     groups = profiled_ticks(T, 6)
     T_ticks_done = T.tick_no
     prof_ticks = "ticks %d-%d" % (prof_first + 1, T_ticks_done)
-
-    agents_total = T.N
-    cells_total = T.n_req_total * 4096
-    ms_per_step = dt / args.steps * 1e3
-    value = agents_total * args.steps / dt
 
     # ---- roofline (HBM bound; algorithmic bytes per launch) ---------------
     f_bytes = T.n_req_local * 4096 * BYTES_PER_CELL
@@ -703,36 +785,14 @@ def main():
         def at(i):          # (ticks: one value per window of T.tick_every ticks)
             w = (i - 1) // tick_every
             return float(ticks[w]) if len(ticks) > w else None
-        dims = T_dims(cfg, world, shared)
-        backend = torch.distributed.get_backend() if torch.distributed.is_initialized() else "none"
         drop = (cpu or {}).pop("dropin", None) if isinstance(cpu, dict) else None
         state_pass = drop.pop("state_pass", None) if isinstance(drop, dict) else None
         sampling = (cpu or {}).pop("flow_sampling", None) if isinstance(cpu, dict) else None
         t5 = [at(5), at(50), at(100)] if args.steps >= 100 or sustained is None else sustained["ms_tick_5_50_100"]
         # What every key means, and the prose that used to ride in the line: profiles/README.md ("the bench line").
         # The driver's record keeps the TAIL of the line: the summary of every regime comes last.
-        line = {
-            "metric": "agent-steps/sec (+ flow-field cells/sec), every chunk field rebuilt + every agent stepped per tick",
-            "value": value, "unit": "agent-steps/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-            "scaling": None if world == 1 else ("strong" if shared else "weak"), "vs_baseline": None,
-            "dtype": "u64-bitmask/u8 fields, f32 agents (f64 exp)", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[%d]%s: %dx%d cells, %d flow fields%s = %d chunk fields, %d agents%s"
-                                   % (args.config, " crowded" if args.crowded else "", dims[0], dims[1], cfg["fields"],
-                                      "" if shared or world == 1 else "/GPU", cells_total // 4096, agents_total,
-                                      ", %d obstacles" % cfg["obstacles"] if cfg["obstacles"] else ""),
-                       "baseline_config": args.config, "map_chunks": cfg["map"], "flow_fields": cfg["fields"],
-                       "agents": cfg["agents"], "hz": 20, "dynamic_obstacles": cfg["obstacles"],
-                       "parallelism": "requests by destination + uid slabs x%d, 1 all-gather (16 B/agent) per tick"
-                                      % world,
-                       "ranks": world, "rccl_ranks": pdist.comm_ranks(), "backend": backend,
-                       "tile_exchange": args.tile_exchange,
-                       "requests": "reference planner fixture" if "fixture" in request_source else "numpy stand-in",
-                       "has_dest_los": "device lookup" if "device lookup" in los_source else "0",
-                       "initial_velocities": "flow aligned" if "flow" in velocity_source else "N(0,0.35)",
-                       "fields_ahead": bool(fields_ahead), "tick_driver": tick_driver,
-                       "library": ("NAVHIP_LIB override: " + os.path.basename(os.environ["NAVHIP_LIB"]))
-                                  if os.environ.get("NAVHIP_LIB") else "libnavhip.so (in-tree)"},
+        line = headline()
+        line.update({
             "roofline": roof(dom, in_tick_ms=in_tick[dom]),
             "cpu_baseline": cpu,
             "roofline_secondary": {k: v for k, v in roof(other, in_tick_ms=in_tick[other]).items()
@@ -751,8 +811,7 @@ def main():
             "crowded_world": crowded,
             "dropin": drop,
             "state_pass": state_pass,
-            ("flow_field_cells_kept_valid_per_s" if cfg["obstacles"] else "flow_field_cells_per_s"):
-                cells_total * args.steps / dt,
+            cells_key: cells_total * args.steps / dt,
             "summary": {"ms_per_step": ms_per_step, "ms_per_step_median": float(np.median(ticks)),
                         "ms_tick_5_50_100": t5,
                         "ms_tick_5_50_100_of": "this run" if args.steps >= 100 or sustained is None else "sustained_100",
@@ -765,7 +824,7 @@ def main():
                         "state_pass_ms": state_pass.get("hip_ms_per_tick") if isinstance(state_pass, dict) else None,
                         "host_enqueue_ms": host_enqueue_ms,
                         "roofline_frac": roof(dom, in_tick_ms=in_tick[dom])["frac"], "ranks": world},
-        }
+        })
         print(json.dumps(r4(line), separators=(",", ":")), flush=True)
     if T is not None:
         T.close()

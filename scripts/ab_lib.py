@@ -41,7 +41,7 @@ def run(names, rounds=3, extra=()):
             lib = n
             if lib != "base":
                 env["NAVHIP_LIB"] = os.path.join(OUT, "libnavhip_%s.so" % lib)
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + list(extra), env=env,
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + list(extra), env=env,
                                stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
             d = json.loads(r.stdout.strip().splitlines()[-1])
             res[n].append(d["ms_per_step"])

@@ -36,7 +36,7 @@ vparity) for v in $VARS; do pick $v
          done; unset NAVHIP_LIB ;;
 parity)  timeout 900 python -m pytest tests/test_agents_gpu.py tests/test_fullsize_ref_gpu.py -m gpu -x -q -k "clearpath or crowded or velocity_step or whole_config" > $OUT/pytest_cp.log 2>&1; tail -4 $OUT/pytest_cp.log ;;
 binding) timeout 900 python -m pytest tests/test_binding_gpu.py -m gpu -x -q > $OUT/pytest_binding.log 2>&1; tail -3 $OUT/pytest_binding.log
-         timeout 600 python bench.py --steps 20 --no-crowded --no-sustained > $OUT/bench20.json 2> $OUT/bench20.err
+         timeout 600 python bench.py --full --steps 20 --no-crowded --no-sustained > $OUT/bench20.json 2> $OUT/bench20.err
          python -c "import json,sys; d=json.loads(open('$OUT/bench20.json').read().strip().splitlines()[-1]); print(d['ms_per_step']); print(json.dumps(d.get('dropin'), indent=1))" ;;
 ab20)    timeout 600 python scripts/ab_lib.py --run $VARS --steps=20 --rounds=3 > $OUT/ab_20.txt 2>&1; tail -$(( $(echo $VARS | wc -w) + 1 )) $OUT/ab_20.txt ;;
 ab100)   timeout 900 python scripts/ab_lib.py --run $VARS --steps=100 --rounds=2 > $OUT/ab_100.txt 2>&1; tail -$(( $(echo $VARS | wc -w) + 1 )) $OUT/ab_100.txt ;;

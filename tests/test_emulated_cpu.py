@@ -137,14 +137,14 @@ def test_bench_starts_its_own_ranks():
     """`python3 bench.py --gpus 2` -- the shape of the driver's N = 1 command, NOT wrapped in torchrun -- has to run two
     ranks by itself (torch.distributed.run, one rank per device; gloo and the emulator build here), split ONE world over
     them (BASELINE.json's metric: strong scaling), say how many ranks the communicator saw, run the weak-scaled job
-    behind it, and print ONE line that fits the driver's record."""
+    behind it (--full), and print ONE line that fits the driver's record."""
     import json
     lib = hostsim.build_navhip_emu()
     env = dict(os.environ, NAVHIP_LIB=lib, NAVHIP_DIST_BACKEND="gloo")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--map", "4", "--fields", "2", "--agents", "300",
-           "--steps", "2", "--warmup", "1", "--no-los"]
+           "--steps", "2", "--warmup", "1", "--no-los", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout + r.stderr)[-2000:]
@@ -155,6 +155,40 @@ def test_bench_starts_its_own_ranks():
     assert line["value"] > 0 and line["summary"]["ranks"] == 2
     assert len(lines[0]) < 6000
     assert all(len(v) <= 120 for v in line["config"].values() if isinstance(v, str))
+
+
+def test_bench_plain_run_and_its_outputs(tmp_path):
+    """A plain `bench.py` run prints the headline only; `--dump-outputs DIR` writes what the last timed step computed as
+    float32 .npy -- the same arrays from a second plain run and from a `--full` run, whose warm-up ends with profiled
+    ticks on the Python driver (the emulator build of the library here)."""
+    import json
+    import numpy as np
+    lib = hostsim.build_navhip_emu()
+    env = dict(os.environ, NAVHIP_LIB=lib)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--map", "4", "--fields", "2", "--agents", "300",
+            "--steps", "3", "--warmup", "4"]
+    runs = {"plain": [], "again": [], "full": ["--full", "--no-sustained", "--no-crowded", "--no-cpu-baseline"]}
+    lines, dumps = {}, {}
+    for name, extra in runs.items():
+        d = str(tmp_path / name)
+        r = subprocess.run(base + extra + ["--dump-outputs", d], cwd=ROOT, env=env, stdout=subprocess.PIPE,
+                           stderr=subprocess.PIPE, text=True, timeout=900)
+        out = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert r.returncode == 0 and len(out) == 1, (r.stdout + r.stderr)[-2000:]
+        lines[name] = json.loads(out[0])
+        dumps[name] = {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+    plain, full = lines["plain"], lines["full"]
+    assert plain["steps"] == 3 and plain["warmup"] == 4 and plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert all(plain[k] == full[k] for k in ("metric", "unit", "higher_is_better", "dtype", "config"))
+    assert "roofline" not in plain and "status" not in plain and "kernel_groups_ms_serial" in full
+    assert sorted(dumps["plain"]) == ["field_dirs", "pos_xz", "status", "vel_xz"]
+    assert dumps["plain"]["pos_xz"].shape == (300, 2) and dumps["plain"]["field_dirs"].shape[1] == 4096
+    assert sum(a.nbytes for a in dumps["plain"].values()) < 64 << 20
+    for name in ("again", "full"):
+        for k, a in dumps["plain"].items():
+            assert a.dtype == np.float32 and np.array_equal(a, dumps[name][k]), (name, k)
 
 
 def test_bench_refuses_more_ranks_than_devices():
