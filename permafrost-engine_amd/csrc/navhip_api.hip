@@ -100,7 +100,7 @@ int navhip_ctx_create(navhip_ctx **out, int chunk_w, int chunk_h, int device)
     memset(&ctx->counters, 0, sizeof(ctx->counters));
     ctx->gen_launches = 0;
     ctx->coh_flocks = ctx->coh_members = -1;
-    ctx->coh_parity = 0; ctx->coh_unique = 0;
+    ctx->coh_parity = 0; ctx->coh_unique = 0; ctx->scratch_moves = 0;
     ctx->ev_regroup = nullptr;
     ctx->regroup_pending = false;
     memset(ctx->coh_regroup_key, 0xff, sizeof(ctx->coh_regroup_key)); ctx->coh_regroup_age = 0;
@@ -692,7 +692,10 @@ int navhip_build_fields(navhip_ctx *ctx, const navhip_field_req *reqs, int n,
 // ---------------------------------------------------------------------------------------------
 static int ensure_buf(navhip_ctx *ctx, navhip_ctx::buf &b, size_t need)
 {
-    return ensure_cap(ctx, &b.p, &b.cap, need ? need : 16);
+    const void *old = b.p;
+    int rc = ensure_cap(ctx, &b.p, &b.cap, need ? need : 16);
+    if(b.p != old) ctx->scratch_moves++;
+    return rc;
 }
 
 // cohesion scratch: grow on demand; a new buffer or another flock count has no lane grouping yet
@@ -709,6 +712,7 @@ static int coh_scratch_ensure(navhip_ctx *ctx, int n_flocks, int n_members, hipS
         }
         HIPCHK(ctx, nh_cohesion_scratch_reset((int32_t*)ctx->coh_plan.p, n_flocks, n_members, s));
         ctx->coh_flocks = n_flocks; ctx->coh_members = n_members; ctx->coh_parity = 0;
+        ctx->scratch_moves++;
     }
     return NAVHIP_OK;
 }
@@ -972,10 +976,15 @@ int navhip_agent_prefetch_dev_ex(navhip_ctx *ctx, const navhip_world *w, void *s
     rc = step_fill_params(ctx, w, &P);
     if(rc) return rc;
     nh_nbr NB; nh_worklists WL;
+    const unsigned moves0 = ctx->scratch_moves;
     rc = ensure_buf(ctx, ctx->coh, (size_t)w->n_ents * 2 * sizeof(float));
     if(!rc) rc = coh_scratch_ensure(ctx, w->n_flocks, P.n_members, s);
     if(!rc) rc = step_scratch(ctx, w->n_ents, &NB, &WL, s);
     if(rc) return rc;
+    // (a lane-grouping reset or a zeroed reallocation just went onto `s`: the side streams must start behind it, not
+    // behind the end word of the last step -- else the reset could land in the middle of this call's cohesion term or
+    // regrouping on aux[1].  Constant counts move nothing, and the hand-over-free start stays.)
+    const bool scratch_moved = ctx->scratch_moves != moves0;
     // the front of the step (spatial hash -> neighbour walk) is a chain of small launches on the
     // critical path of the tick: NAVHIP_PREFETCH_FRONT_INLINE keeps it on the caller's stream, where it
     // follows the previous step without a cross-stream hand-over (tens of microseconds each)
@@ -986,7 +995,8 @@ int navhip_agent_prefetch_dev_ex(navhip_ctx *ctx, const navhip_world *w, void *s
     // of the front at all.  Otherwise a one-lane launch stores it now, in FRONT of the first kernel of the front: the
     // cohesion kernel ends last, so it must not start late (profiles/archive/r03_ab_fork_first.txt).
     nh_handover_mode(ctx, step_in_a_jam(ctx));           // (words, or events: under a serialising profiler, in a jam)
-    const bool follows = (flags & NAVHIP_PREFETCH_FOLLOWS_STEP) && ctx->step_end_on == s && !ctx->ho->by_events;
+    const bool follows = (flags & NAVHIP_PREFETCH_FOLLOWS_STEP) && ctx->step_end_on == s && !ctx->ho->by_events
+                      && !scratch_moved;
     if(!follows) nh_handover_signal(ctx, NH_HO_START, s);
     ctx->start_flag = follows ? NH_HO_END : NH_HO_START;
     ctx->start_seq = nh_handover_seq(ctx, ctx->start_flag);

@@ -63,6 +63,7 @@ struct navhip_ctx {
     unsigned     gen_launches; // parity selects the counter of a launch
     int          coh_flocks, coh_members, coh_parity;   // layout of coh_plan + which perm buffer is next
     unsigned     coh_unique;   // membership keys of slab steps whose caller gave no static_epoch: never equal
+    unsigned     scratch_moves; // step scratch reallocated or its lane grouping reset: either may enqueue on the caller's stream
     buf          stage[48];    // device copies of host buffers for the host-pointer entry points
     // side streams for navhip_agent_prefetch_dev (spatial hash | cohesion) + fork/join events; BORROWED from the process's
     // set (nh_device_stream)
