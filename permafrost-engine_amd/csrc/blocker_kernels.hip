@@ -250,7 +250,7 @@ __global__ __launch_bounds__(256) void k_refresh_touched(const uint8_t *cost, co
 __global__ __launch_bounds__(256) void k_local_islands(const uint64_t *passmask, uint16_t *local_islands,
                                                        const uint8_t *only, int nchunks)
 {
-    __shared__ __attribute__((aligned(16))) uint16_t stage[4][NH_CELLS];      // 32 KB
+    __shared__ __attribute__((aligned(16))) uint16_t staged[4][NH_CELLS];      // 32 KB
     const int wib = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int chunk = blockIdx.x * 4 + wib;
     if(chunk >= nchunks) return;
@@ -285,7 +285,7 @@ __global__ __launch_bounds__(256) void k_local_islands(const uint64_t *passmask,
             if((id >> k) & 1) pl[k] = pl[k] | comp;                 // id is wave-uniform
     }
     // expand: impassable / blocked cells are ISLAND_NONE (0xffff)
-    uint16_t *st = stage[wib];
+    uint16_t *st = staged[wib];
     const int P = 32 - __builtin_clz((unsigned)id | 1u);
     const uint64_t ps = to64(pass);
     for(int c = 0; c < 64; c++) {

@@ -25,15 +25,6 @@ typedef enum { ncclInt8 = 0, ncclChar = 0 } ncclDataType_t;
 }
 #endif
 
-#define HIPCHK(ctx, expr)                                                                   \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if(_e != hipSuccess) {                                                              \
-            (ctx)->last_error = std::string(#expr) + ": " + hipGetErrorString(_e);          \
-            return NAVHIP_ERR_DEVICE;                                                       \
-        }                                                                                   \
-    } while(0)
-
 namespace {
 
 struct rccl_api {

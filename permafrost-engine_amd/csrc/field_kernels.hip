@@ -671,15 +671,8 @@ __global__ __launch_bounds__(256) void k_field_generic(nh_map_view map, const na
 void nh_launch_fields(navhip_ctx *ctx, const navhip_field_req *d_reqs, int n, uint8_t *d_dirs,
                       float *d_integ, int32_t *d_gen_list, hipStream_t s, const int32_t *d_out_slot)
 {
-
     nh_map_view mv;
-    mv.w = ctx->w;
-    mv.h = ctx->h;
-    for(int l = 0; l < NAVHIP_NAV_LAYER_MAX; l++) {
-        const navhip_layer &L = ctx->layers[l];
-        mv.layers[l] = nh_layer_view{L.cost, L.blockers, L.local_islands, L.factions,
-                                     L.passmask, L.unit_cost, L.changed, L.islands};
-    }
+    nh_fill_map_view(ctx, &mv);
     const int force_generic = ctx->field_kernel_mode == 1;
     // (only launches that use the list alternate its counters)
     const int gen_slot = force_generic ? 0 : (int)(ctx->gen_launches++ & 1);

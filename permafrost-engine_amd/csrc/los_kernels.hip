@@ -262,19 +262,11 @@ __global__ __launch_bounds__(64) void k_los_field(nh_map_view map, const navhip_
 }
 
 void nh_launch_los(navhip_ctx *ctx, const navhip_los_req *d_reqs, int n, const uint8_t *d_prev,
-                   uint8_t *d_out, float map_x, float map_z, hipStream_t s)
+                   uint8_t *d_out, uint8_t *d_over, float map_x, float map_z, hipStream_t s)
 {
     nh_map_view mv;
-    mv.w = ctx->w;
-    mv.h = ctx->h;
-    for(int l = 0; l < NAVHIP_NAV_LAYER_MAX; l++) {
-        const navhip_layer &L = ctx->layers[l];
-        mv.layers[l] = nh_layer_view{L.cost, L.blockers, L.local_islands, L.factions,
-                                     L.passmask, L.unit_cost, L.changed, L.islands};
-    }
+    nh_fill_map_view(ctx, &mv);
     if(n > 0) {
-        uint8_t *d_over = nullptr;
-        if(navhip_stage_reserve(ctx, 42, (size_t)n, (void**)&d_over) != NAVHIP_OK) return;
         hipLaunchKernelGGL((k_los_field<1022, false>), dim3(n), dim3(64), 0, s, mv, d_reqs, n, d_prev, d_out, map_x,
                            map_z, d_over);
         hipLaunchKernelGGL((k_los_field<4096, true>), dim3(n), dim3(64), 0, s, mv, d_reqs, n, d_prev, d_out, map_x,

@@ -18,21 +18,13 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <vector>
 
-#define HIPCHK(ctx, expr)                                                                   \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if(_e != hipSuccess) {                                                              \
-            (ctx)->last_error = std::string(#expr) + ": " + hipGetErrorString(_e);          \
-            return NAVHIP_ERR_DEVICE;                                                       \
-        }                                                                                   \
-    } while(0)
-
 static int refresh_derived(navhip_ctx *ctx, hipStream_t s);
-static int ensure_buf(navhip_ctx *ctx, navhip_ctx::buf &b, size_t need);
 
 static size_t plane_elem_bytes(int plane)
 {
@@ -58,15 +50,24 @@ static void **plane_slot(navhip_layer &L, int plane)
     }
 }
 
-static int ensure_cap(navhip_ctx *ctx, void **p, size_t *cap, size_t need)
+int nh_ensure(navhip_ctx *ctx, nh_buf &b, size_t need)
 {
-    if(*cap >= need) return NAVHIP_OK;
-    if(*p) HIPCHK(ctx, hipFree(*p));
-    *p = nullptr; *cap = 0;
-    size_t want = need + need / 2;
-    HIPCHK(ctx, hipMalloc(p, want));
-    *cap = want;
+    if(b.cap >= need) return NAVHIP_OK;
+    if(b.p) HIPCHK(ctx, hipFree(b.p));
+    b = nh_buf();
+    const size_t want = need + need / 2;
+    HIPCHK(ctx, hipMalloc(&b.p, want));
+    b.cap = want;
     return NAVHIP_OK;
+}
+
+// the step's scratch and the staging slots: at least 16 bytes, and a buffer that moved is counted (scratch_moves)
+static int ensure_buf(navhip_ctx *ctx, nh_buf &b, size_t need)
+{
+    const void *old = b.p;
+    int rc = nh_ensure(ctx, b, need ? need : 16);
+    if(b.p != old) ctx->scratch_moves++;
+    return rc;
 }
 
 extern "C" {
@@ -86,35 +87,6 @@ int navhip_ctx_create(navhip_ctx **out, int chunk_w, int chunk_h, int device)
     if(!ctx) return NAVHIP_ERR_NOMEM;
     ctx->device = device;
     ctx->w = chunk_w; ctx->h = chunk_h; ctx->nchunks = chunk_w * chunk_h;
-    ctx->field_kernel_mode = 0;
-    memset(ctx->layers, 0, sizeof(ctx->layers));
-    ctx->d_reqs = nullptr; ctx->d_reqs_cap = 0;
-    ctx->d_dirs = nullptr; ctx->d_dirs_cap = 0;
-    ctx->d_integ = nullptr; ctx->d_integ_cap = 0;
-    ctx->d_reqmask = nullptr; ctx->d_reqmask_cap = 0;
-    ctx->d_dirty_list = nullptr; ctx->d_dirty_cap = 0;
-    memset(ctx->sp, 0, sizeof(ctx->sp));
-    memset(&ctx->coh, 0, sizeof(ctx->coh));
-    memset(&ctx->coh_plan, 0, sizeof(ctx->coh_plan));
-    memset(&ctx->gen_list, 0, sizeof(ctx->gen_list));
-    memset(&ctx->counters, 0, sizeof(ctx->counters));
-    ctx->gen_launches = 0;
-    ctx->coh_flocks = ctx->coh_members = -1;
-    ctx->coh_parity = 0; ctx->coh_unique = 0; ctx->scratch_moves = 0;
-    ctx->ev_regroup = nullptr;
-    ctx->regroup_pending = false;
-    memset(ctx->coh_regroup_key, 0xff, sizeof(ctx->coh_regroup_key)); ctx->coh_regroup_age = 0;
-    memset(&ctx->midrec, 0, sizeof(ctx->midrec));
-    memset(ctx->nbr, 0, sizeof(ctx->nbr));
-    memset(ctx->wl, 0, sizeof(ctx->wl));
-    ctx->wl_parity = 0;
-    memset(ctx->stage, 0, sizeof(ctx->stage));
-    ctx->profiling = false; ctx->ev_valid = false;
-    ctx->aux[0] = ctx->aux[1] = nullptr; ctx->aux_main = nullptr;
-    ctx->front_stream = nullptr; ctx->join0_signalled = ctx->lists_signalled = false; ctx->step_end_on = nullptr; ctx->step_end_signalled = false; ctx->start_seq = 0; ctx->start_flag = NH_HO_START;
-    memset(&ctx->pre, 0, sizeof(ctx->pre));
-    ctx->pool = nullptr; ctx->async = nullptr; ctx->comm = nullptr; ctx->ho = nullptr; ctx->sp_builds = 0; ctx->lists_pinned = nullptr;
-    memset(ctx->ev, 0, sizeof(ctx->ev));
     if(hipSetDevice(device) != hipSuccess
     || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
         delete ctx;
@@ -140,14 +112,7 @@ void navhip_ctx_destroy(navhip_ctx *ctx)
         hipFree(L.passmask); hipFree(L.probemask); hipFree(L.unit_cost); hipFree(L.touched); hipFree(L.changed);
         free(L.dirty);
     }
-    hipFree(ctx->d_reqs); hipFree(ctx->d_dirs); hipFree(ctx->d_integ); hipFree(ctx->d_reqmask);
-    hipFree(ctx->d_dirty_list);
-    for(auto &b : ctx->sp) hipFree(b.p);
-    for(auto &b : ctx->stage) hipFree(b.p);
-    hipFree(ctx->coh.p); hipFree(ctx->coh_plan.p); hipFree(ctx->midrec.p); hipFree(ctx->gen_list.p);
-    for(auto &b : ctx->nbr) hipFree(b.p);
-    for(auto &b : ctx->arrived) hipFree(b.p);
-    for(auto &b : ctx->wl) hipFree(b.p);
+    nh_ctx_each_buf(ctx, [](nh_buf &b) { hipFree(b.p); });
     for(auto &e : ctx->ev) if(e) hipEventDestroy(e);
     if(nh_streams_alive(ctx->device))
         for(auto &a : ctx->aux) if(a) hipStreamSynchronize(a);   // (borrowed: the process's own set, csrc/stream_set.hip)
@@ -322,12 +287,11 @@ static int refresh_derived(navhip_ctx *ctx, hipStream_t s)
             if((int)list.size() == ctx->nchunks) {
                 nh_launch_derive(ctx, l, nullptr, ctx->nchunks, s);
             }else{
-                int rc = ensure_cap(ctx, (void**)&ctx->d_dirty_list, &ctx->d_dirty_cap,
-                                    list.size() * sizeof(uint32_t));
+                int rc = nh_ensure(ctx, ctx->d_dirty_list, list.size() * sizeof(uint32_t));
                 if(rc) return rc;
-                HIPCHK(ctx, hipMemcpyAsync(ctx->d_dirty_list, list.data(),
+                HIPCHK(ctx, hipMemcpyAsync(ctx->d_dirty_list.p, list.data(),
                                            list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-                nh_launch_derive(ctx, l, ctx->d_dirty_list, (int)list.size(), s);
+                nh_launch_derive(ctx, l, (const uint32_t*)ctx->d_dirty_list.p, (int)list.size(), s);
                 HIPCHK(ctx, hipStreamSynchronize(s));   // list buffer is reused per layer
             }
             HIPCHK(ctx, hipGetLastError());
@@ -392,11 +356,12 @@ int navhip_blockers_circles(navhip_ctx *ctx, const navhip_circle *circles, int n
     }
     if(n == 0) return NAVHIP_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_buf(ctx, ctx->stage[23], (size_t)n * sizeof(navhip_circle));
+    nh_buf &d_circles = ctx->stage[NH_STAGE_CALL0];
+    int rc = ensure_buf(ctx, d_circles, (size_t)n * sizeof(navhip_circle));
     if(rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->stage[23].p, circles, (size_t)n * sizeof(navhip_circle),
+    HIPCHK(ctx, hipMemcpyAsync(d_circles.p, circles, (size_t)n * sizeof(navhip_circle),
                                hipMemcpyHostToDevice, ctx->stream));
-    rc = navhip_blockers_circles_dev(ctx, (const navhip_circle*)ctx->stage[23].p, n, map_pos_x,
+    rc = navhip_blockers_circles_dev(ctx, (const navhip_circle*)d_circles.p, n, map_pos_x,
                                      map_pos_z, ctx->stream);
     if(rc) return rc;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -490,22 +455,23 @@ int navhip_build_region_fields(navhip_ctx *ctx, const navhip_region_req *reqs, i
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    int rc = ensure_buf(ctx, ctx->stage[32], (size_t)n * sizeof(navhip_region_req));
-    if(!rc) rc = ensure_buf(ctx, ctx->stage[33], n_seeds * 4);
-    if(!rc) rc = ensure_buf(ctx, ctx->stage[34], n_overlay * 4);
-    if(!rc) rc = ensure_buf(ctx, ctx->stage[35], (size_t)n * out_stride);
+    nh_buf &d_reqs = ctx->stage[NH_STAGE_CALL0], &d_seeds = ctx->stage[NH_STAGE_CALL1];
+    nh_buf &d_overlay = ctx->stage[NH_STAGE_CALL2], &d_out = ctx->stage[NH_STAGE_CALL3];
+    int rc = ensure_buf(ctx, d_reqs, (size_t)n * sizeof(navhip_region_req));
+    if(!rc) rc = ensure_buf(ctx, d_seeds, n_seeds * 4);
+    if(!rc) rc = ensure_buf(ctx, d_overlay, n_overlay * 4);
+    if(!rc) rc = ensure_buf(ctx, d_out, (size_t)n * out_stride);
     if(rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->stage[32].p, reqs, (size_t)n * sizeof(navhip_region_req),
-                               hipMemcpyHostToDevice, s));
-    if(n_seeds) HIPCHK(ctx, hipMemcpyAsync(ctx->stage[33].p, seeds, n_seeds * 4, hipMemcpyHostToDevice, s));
-    if(n_overlay) HIPCHK(ctx, hipMemcpyAsync(ctx->stage[34].p, overlay, n_overlay * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(d_reqs.p, reqs, (size_t)n * sizeof(navhip_region_req), hipMemcpyHostToDevice, s));
+    if(n_seeds) HIPCHK(ctx, hipMemcpyAsync(d_seeds.p, seeds, n_seeds * 4, hipMemcpyHostToDevice, s));
+    if(n_overlay) HIPCHK(ctx, hipMemcpyAsync(d_overlay.p, overlay, n_overlay * 4, hipMemcpyHostToDevice, s));
     if(any_window)
-        HIPCHK(ctx, hipMemcpyAsync(ctx->stage[35].p, inout, (size_t)n * out_stride, hipMemcpyHostToDevice, s));
-    rc = navhip_build_region_fields_dev(ctx, (const navhip_region_req*)ctx->stage[32].p, n, max_dim,
-                                        (const int16_t*)ctx->stage[33].p, (const int16_t*)ctx->stage[34].p,
-                                        (uint8_t*)ctx->stage[35].p, out_stride, s);
+        HIPCHK(ctx, hipMemcpyAsync(d_out.p, inout, (size_t)n * out_stride, hipMemcpyHostToDevice, s));
+    rc = navhip_build_region_fields_dev(ctx, (const navhip_region_req*)d_reqs.p, n, max_dim,
+                                        (const int16_t*)d_seeds.p, (const int16_t*)d_overlay.p,
+                                        (uint8_t*)d_out.p, out_stride, s);
     if(rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(inout, ctx->stage[35].p, (size_t)n * out_stride, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(inout, d_out.p, (size_t)n * out_stride, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     return NAVHIP_OK;
 }
@@ -522,7 +488,10 @@ int navhip_build_los_dev(navhip_ctx *ctx, const navhip_los_req *dev_reqs, int n,
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     ctx->counters.los_fields += (uint64_t)n;
-    nh_launch_los(ctx, dev_reqs, n, dev_prev_fields, dev_out_fields, map_pos_x, map_pos_z, s);
+    uint8_t *d_over = nullptr;                 // the per-request overlay of the two launches
+    int rc = nh_stage_reserve(ctx, NH_STAGE_LOS_OVERLAY, (size_t)n, (void**)&d_over);
+    if(rc) return rc;
+    nh_launch_los(ctx, dev_reqs, n, dev_prev_fields, dev_out_fields, d_over, map_pos_x, map_pos_z, s);
     HIPCHK(ctx, hipGetLastError());
     return NAVHIP_OK;
 }
@@ -553,21 +522,18 @@ int navhip_build_los(navhip_ctx *ctx, const navhip_los_req *reqs, int n,
     if(any_prev && !prev_fields) return NAVHIP_ERR_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    int rc = ensure_buf(ctx, ctx->stage[29], (size_t)n * sizeof(navhip_los_req));
-    if(!rc) rc = ensure_buf(ctx, ctx->stage[30], (size_t)n * NH_CELLS);
-    if(!rc) rc = ensure_buf(ctx, ctx->stage[31], (size_t)n * NH_CELLS);
+    nh_buf &d_reqs = ctx->stage[NH_STAGE_CALL0], &d_prev = ctx->stage[NH_STAGE_CALL1], &d_out = ctx->stage[NH_STAGE_CALL2];
+    int rc = ensure_buf(ctx, d_reqs, (size_t)n * sizeof(navhip_los_req));
+    if(!rc) rc = ensure_buf(ctx, d_prev, (size_t)n * NH_CELLS);
+    if(!rc) rc = ensure_buf(ctx, d_out, (size_t)n * NH_CELLS);
     if(rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->stage[29].p, reqs, (size_t)n * sizeof(navhip_los_req),
-                               hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(d_reqs.p, reqs, (size_t)n * sizeof(navhip_los_req), hipMemcpyHostToDevice, s));
     if(any_prev)
-        HIPCHK(ctx, hipMemcpyAsync(ctx->stage[30].p, prev_fields, (size_t)n * NH_CELLS,
-                                   hipMemcpyHostToDevice, s));
-    rc = navhip_build_los_dev(ctx, (const navhip_los_req*)ctx->stage[29].p, n,
-                              (const uint8_t*)ctx->stage[30].p, (uint8_t*)ctx->stage[31].p,
+        HIPCHK(ctx, hipMemcpyAsync(d_prev.p, prev_fields, (size_t)n * NH_CELLS, hipMemcpyHostToDevice, s));
+    rc = navhip_build_los_dev(ctx, (const navhip_los_req*)d_reqs.p, n, (const uint8_t*)d_prev.p, (uint8_t*)d_out.p,
                               map_pos_x, map_pos_z, s);
     if(rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(out_fields, ctx->stage[31].p, (size_t)n * NH_CELLS,
-                               hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(out_fields, d_out.p, (size_t)n * NH_CELLS, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     return NAVHIP_OK;
 }
@@ -637,7 +603,7 @@ int navhip_build_fields_slots_dev(navhip_ctx *ctx, const navhip_field_req *dev_r
     return build_fields_on(ctx, dev_reqs, n, dev_fields, nullptr, dev_slots, s);
 }
 
-int navhip_stage_reserve(navhip_ctx *ctx, int slot, size_t bytes, void **dev)
+int nh_stage_reserve(navhip_ctx *ctx, nh_stage_slot slot, size_t bytes, void **dev)
 {
     int rc = ensure_buf(ctx, ctx->stage[slot], bytes);
     if(rc) return rc;
@@ -656,31 +622,27 @@ int navhip_build_fields(navhip_ctx *ctx, const navhip_field_req *reqs, int n,
     int rc = nh_validate_field_reqs(ctx, reqs, n);
     if(rc) return rc;
     hipStream_t s = ctx->stream;
-    rc = ensure_cap(ctx, &ctx->d_reqs, &ctx->d_reqs_cap, (size_t)n * sizeof(navhip_field_req));
+    rc = nh_ensure(ctx, ctx->d_reqs, (size_t)n * sizeof(navhip_field_req));
+    if(!rc) rc = nh_ensure(ctx, ctx->d_dirs, (size_t)n * NH_CELLS);
+    if(!rc && out_integ) rc = nh_ensure(ctx, ctx->d_integ, (size_t)n * NH_CELLS * sizeof(float));
     if(rc) return rc;
-    rc = ensure_cap(ctx, (void**)&ctx->d_dirs, &ctx->d_dirs_cap, (size_t)n * NH_CELLS);
-    if(rc) return rc;
-    if(out_integ) {
-        rc = ensure_cap(ctx, (void**)&ctx->d_integ, &ctx->d_integ_cap,
-                        (size_t)n * NH_CELLS * sizeof(float));
-        if(rc) return rc;
-    }
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_reqs, reqs, (size_t)n * sizeof(navhip_field_req),
+    uint8_t *d_dirs = (uint8_t*)ctx->d_dirs.p;
+    float *d_integ = out_integ ? (float*)ctx->d_integ.p : nullptr;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_reqs.p, reqs, (size_t)n * sizeof(navhip_field_req),
                                hipMemcpyHostToDevice, s));
     bool any_inout = false;
     for(int i = 0; i < n; i++)      // skipped (IF_CHANGED) slots must come back unchanged too
         any_inout |= (reqs[i].flags & (NAVHIP_REQ_INOUT | NAVHIP_REQ_IF_CHANGED | NAVHIP_REQ_ISLAND_NEAREST)) != 0
                   || reqs[i].type == NAVHIP_TARGET_NEAREST_PATHABLE;
     if(any_inout)
-        HIPCHK(ctx, hipMemcpyAsync(ctx->d_dirs, inout_dirs, (size_t)n * NH_CELLS,
+        HIPCHK(ctx, hipMemcpyAsync(d_dirs, inout_dirs, (size_t)n * NH_CELLS,
                                    hipMemcpyHostToDevice, s));
-    rc = navhip_build_fields_dev(ctx, (const navhip_field_req*)ctx->d_reqs, n, ctx->d_dirs,
-                                 out_integ ? ctx->d_integ : nullptr, s);
+    rc = navhip_build_fields_dev(ctx, (const navhip_field_req*)ctx->d_reqs.p, n, d_dirs, d_integ, s);
     if(rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(inout_dirs, ctx->d_dirs, (size_t)n * NH_CELLS,
+    HIPCHK(ctx, hipMemcpyAsync(inout_dirs, d_dirs, (size_t)n * NH_CELLS,
                                hipMemcpyDeviceToHost, s));
     if(out_integ)
-        HIPCHK(ctx, hipMemcpyAsync(out_integ, ctx->d_integ, (size_t)n * NH_CELLS * sizeof(float),
+        HIPCHK(ctx, hipMemcpyAsync(out_integ, d_integ, (size_t)n * NH_CELLS * sizeof(float),
                                    hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     return NAVHIP_OK;
@@ -690,14 +652,6 @@ int navhip_build_fields(navhip_ctx *ctx, const navhip_field_req *reqs, int n,
 // ---------------------------------------------------------------------------------------------
 // agent step
 // ---------------------------------------------------------------------------------------------
-static int ensure_buf(navhip_ctx *ctx, navhip_ctx::buf &b, size_t need)
-{
-    const void *old = b.p;
-    int rc = ensure_cap(ctx, &b.p, &b.cap, need ? need : 16);
-    if(b.p != old) ctx->scratch_moves++;
-    return rc;
-}
-
 // cohesion scratch: grow on demand; a new buffer or another flock count has no lane grouping yet
 static int coh_scratch_ensure(navhip_ctx *ctx, int n_flocks, int n_members, hipStream_t s)
 {
@@ -732,18 +686,8 @@ static bool grid_geometry(const navhip_world *w, nh_grid *g)
     return true;
 }
 
-static void fill_map_view(const navhip_ctx *ctx, nh_map_view *mv)
-{
-    mv->w = ctx->w; mv->h = ctx->h;
-    for(int l = 0; l < NAVHIP_NAV_LAYER_MAX; l++) {
-        const navhip_layer &L = ctx->layers[l];
-        mv->layers[l] = nh_layer_view{L.cost, L.blockers, L.local_islands, L.factions,
-                                      L.passmask, L.unit_cost, L.changed, L.islands, L.probemask};
-    }
-}
-
 // like ensure_buf, but a fresh allocation is zeroed (counters that the kernels keep at zero themselves)
-static int ensure_zeroed(navhip_ctx *ctx, navhip_ctx::buf &b, size_t need, hipStream_t s)
+static int ensure_zeroed(navhip_ctx *ctx, nh_buf &b, size_t need, hipStream_t s)
 {
     const void *old = b.p;
     int rc = ensure_buf(ctx, b, need);
@@ -830,7 +774,7 @@ static int step_fill_params(navhip_ctx *ctx, const navhip_world *w, nh_step_para
     memset(&P, 0, sizeof(P));
     int rc_masks = refresh_derived(ctx, ctx->stream);      // the tile probes read the derived row masks
     if(rc_masks) return rc_masks;
-    fill_map_view(ctx, &P.map);
+    nh_fill_map_view(ctx, &P.map);
     P.map_x = w->map_pos_x; P.map_z = w->map_pos_z;
     P.n_ents = w->n_ents; P.n_flocks = w->n_flocks; P.hz = w->hz;
     P.n_members = w->n_ents;          // every entity belongs to at most one flock
@@ -1192,6 +1136,16 @@ int navhip_last_step_ms(navhip_ctx *ctx, float out_ms[NAVHIP_STEP_PHASES])
     return NAVHIP_OK;
 }
 
+// the counters of a step's work lists -> the six reported: the wave and the heavy list together (17-64 neighbours),
+// the retry list not at all
+static void sum_step_lists(const volatile int32_t *h, int32_t out_counts[6])
+{
+    static const int slot_of[NH_WL_LISTS] = {0, 1, 2, 3, 4, 4, 5, -1};
+    for(int l = 0; l < 6; l++) out_counts[l] = 0;
+    for(int l = 0; l < NH_WL_LISTS; l++)
+        for(int sb = 0; sb < NH_WL_SUB; sb++) if(slot_of[l] >= 0) out_counts[slot_of[l]] += h[l * NH_WL_SUB + sb];
+}
+
 // the work-list sizes of the last agent step: {light 1..4, wave, full} (waits for the step)
 int navhip_last_step_lists(navhip_ctx *ctx, int32_t out_counts[6])
 {
@@ -1201,28 +1155,20 @@ int navhip_last_step_lists(navhip_ctx *ctx, int32_t out_counts[6])
     const int32_t *src = (const int32_t*)ctx->wl[0].p + (ctx->wl_parity ^ 1) * NH_WL_COUNTERS;
     int32_t h[NH_WL_COUNTERS];
     HIPCHK(ctx, hipMemcpy(h, src, sizeof(h), hipMemcpyDeviceToHost));
-    // (the wave and the heavy list are reported together: 17-64 neighbours)
-    static const int slot_of[NH_WL_LISTS] = {0, 1, 2, 3, 4, 4, 5, -1};     // (the retry list is not reported)
-    for(int l = 0; l < 6; l++) out_counts[l] = 0;
-    for(int l = 0; l < NH_WL_LISTS; l++)
-        for(int sb = 0; sb < NH_WL_SUB; sb++) if(slot_of[l] >= 0) out_counts[slot_of[l]] += h[l * NH_WL_SUB + sb];
+    sum_step_lists(h, out_counts);
     return NAVHIP_OK;
 }
 
 int navhip_step_lists_peek(navhip_ctx *ctx, int32_t out_counts[6])
 {
     if(!ctx || !out_counts) return NAVHIP_ERR_INVALID;
-    static const int slot_of[NH_WL_LISTS] = {0, 1, 2, 3, 4, 4, 5, -1};
     for(int l = 0; l < 6; l++) out_counts[l] = 0;
-    if(!ctx->lists_pinned) return NAVHIP_OK;
-    const volatile int32_t *h = ctx->lists_pinned;
-    for(int l = 0; l < NH_WL_LISTS; l++)
-        for(int sb = 0; sb < NH_WL_SUB; sb++) if(slot_of[l] >= 0) out_counts[slot_of[l]] += h[l * NH_WL_SUB + sb];
+    if(ctx->lists_pinned) sum_step_lists((const volatile int32_t*)ctx->lists_pinned, out_counts);
     return NAVHIP_OK;
 }
 
 // copy a host array to a staging buffer; returns device pointer through *dst (NULL stays NULL)
-static int stage_in(navhip_ctx *ctx, int slot, const void *host, size_t bytes, const void **dst,
+static int stage_in(navhip_ctx *ctx, nh_stage_slot slot, const void *host, size_t bytes, const void **dst,
                     hipStream_t s)
 {
     nh_async_invalidate_static(ctx);
@@ -1235,35 +1181,22 @@ static int stage_in(navhip_ctx *ctx, int slot, const void *host, size_t bytes, c
     return NAVHIP_OK;
 }
 
-static int stage_world(navhip_ctx *ctx, const navhip_world *w, navhip_world *d, hipStream_t s)
+// the world's arrays, staged row by row of nh_world_rows; `only`: just these members (their offsets)
+static int stage_world(navhip_ctx *ctx, const navhip_world *w, navhip_world *d, hipStream_t s,
+                       std::initializer_list<size_t> only = {})
 {
     *d = *w;
-    const size_t n = (size_t)w->n_ents, F = (size_t)w->n_flocks;
-    size_t nmembers = 0;
-    if(F > 0 && w->flock_offsets) nmembers = (size_t)w->flock_offsets[F];
-    const size_t nchunks = (size_t)ctx->nchunks;
-    int rc = 0;
-#define ST(slot, field, bytes) \
-    if(!rc) rc = stage_in(ctx, slot, w->field, (bytes), (const void**)&d->field, s)
-    ST(0, pos_xz, n * 8);        ST(1, vel_xz, n * 8);       ST(2, radius, n * 4);
-    ST(3, max_speed, n * 4);     ST(4, speed, n * 4);        ST(5, flags, n * 4);
-    ST(6, state, n);             ST(7, has_dest_los, n);     ST(8, flock, n * 4);
-    ST(9, vdes_xz, n * 8);       ST(10, flock_target_xz, F * 8);
-    ST(11, flock_offsets, (F + 1) * 4);                      ST(12, flock_members, nmembers * 4);
-    if(w->n_field_slots != NAVHIP_POOL_RESIDENT) {
-        ST(13, flock_field_slot, F * nchunks * 4);
-        ST(14, field_pool, (size_t)w->n_field_slots * NH_CELLS);
+    const size_t F = (size_t)w->n_flocks;
+    const size_t nmembers = (F > 0 && w->flock_offsets) ? (size_t)w->flock_offsets[F] : 0;
+    const bool resident = w->n_field_slots == NAVHIP_POOL_RESIDENT;
+    for(const nh_world_row &r : nh_world_rows) {
+        if(resident && (r.flags & NH_ROW_NOT_RESIDENT)) continue;
+        if(only.size() && std::find(only.begin(), only.end(), r.off) == only.end()) continue;
+        int rc = stage_in(ctx, r.slot, nh_member(w, r.off), nh_world_row_bytes(r, w, (size_t)ctx->nchunks, nmembers),
+                          (const void**)&nh_member(d, r.off), s);
+        if(rc) return rc;
     }
-    ST(24, form_ready, n);       ST(25, cell_pos_xz, n * 8); ST(26, form_cohesion_xz, n * 8);
-    ST(27, form_align_xz, n * 8); ST(28, form_drag_xz, n * 8);
-    ST(36, arrival_sink_xz, n * 8); ST(37, arrival_flags, n);
-    ST(38, los_pool, (size_t)(w->n_los_slots > 0 ? w->n_los_slots : 0) * NH_CELLS);
-    ST(39, flock_los_slot, F * nchunks * 4); ST(40, los_pos_xz, n * 8);
-    ST(46, region_row, n * 4);
-    if(w->n_field_slots != NAVHIP_POOL_RESIDENT)
-        ST(47, region_field_slot, (size_t)(w->n_region_rows > 0 ? w->n_region_rows : 0) * nchunks * 4);
-#undef ST
-    return rc;
+    return NAVHIP_OK;
 }
 
 int navhip_agent_step(navhip_ctx *ctx, const navhip_world *w, const navhip_step_out *out)
@@ -1277,17 +1210,10 @@ int navhip_agent_step(navhip_ctx *ctx, const navhip_world *w, const navhip_step_
     if(rc) return rc;
     const size_t n = (size_t)w->n_ents;
     navhip_step_out dout = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    struct { void **dev; void *host; size_t bytes; int slot; } outs[5] = {
-        {(void**)&dout.vel_xz,     out->vel_xz,     n * 8, 15},
-        {(void**)&dout.new_pos_xz, out->new_pos_xz, n * 8, 16},
-        {(void**)&dout.vdes_xz,    out->vdes_xz,    n * 8, 17},
-        {(void**)&dout.vpref_xz,   out->vpref_xz,   n * 8, 18},
-        {(void**)&dout.status,     out->status,     n,     19}};
-    for(auto &o : outs) {
-        if(!o.host) continue;
-        rc = ensure_buf(ctx, ctx->stage[o.slot], o.bytes);
+    for(const nh_out_row &o : nh_out_rows) {
+        if(!nh_member(out, o.off)) continue;
+        rc = nh_stage_reserve(ctx, o.slot, n * o.row_bytes, &nh_member(&dout, o.off));
         if(rc) return rc;
-        *o.dev = ctx->stage[o.slot].p;
     }
     rc = navhip_agent_step_dev(ctx, &d, &dout, s);
     if(rc) return rc;
@@ -1295,10 +1221,11 @@ int navhip_agent_step(navhip_ctx *ctx, const navhip_world *w, const navhip_step_
     // the same output arrays (move_submit_cpu_work, movement.c:3759-3762) keeps its other slabs
     size_t b = (size_t)w->work_begin, e = (size_t)w->work_end;
     if(b == 0 && e == 0) e = n;
-    for(auto &o : outs) {
-        if(!o.host || e <= b) continue;
-        const size_t row = o.bytes / n;
-        HIPCHK(ctx, hipMemcpyAsync((char*)o.host + b * row, (char*)*o.dev + b * row, (e - b) * row,
+    for(const nh_out_row &o : nh_out_rows) {
+        char *host = (char*)nh_member(out, o.off);
+        if(!host || e <= b) continue;
+        const size_t row = o.row_bytes;
+        HIPCHK(ctx, hipMemcpyAsync(host + b * row, (char*)nh_member(&dout, o.off) + b * row, (e - b) * row,
                                    hipMemcpyDeviceToHost, s));
     }
     HIPCHK(ctx, hipStreamSynchronize(s));
@@ -1320,7 +1247,7 @@ int navhip_state_update_dev(navhip_ctx *ctx, const navhip_world *w, const navhip
     memset(&P, 0, sizeof(P));
     int rc_masks = refresh_derived(ctx, ctx->stream);
     if(rc_masks) return rc_masks;
-    fill_map_view(ctx, &P.map);
+    nh_fill_map_view(ctx, &P.map);
     P.map_x = w->map_pos_x; P.map_z = w->map_pos_z;
     P.n_ents = w->n_ents; P.n_flocks = w->n_flocks; P.hz = w->hz;
     P.work_begin = w->work_begin; P.work_end = w->work_end;
@@ -1353,30 +1280,26 @@ int navhip_state_update(navhip_ctx *ctx, const navhip_world *w, const navhip_sta
         ctx->last_error = "navhip_state_update: more flock members than entities";
         return NAVHIP_ERR_INVALID;
     }
-    navhip_world d = *w;
+    navhip_world d;
     navhip_state_in di = *in;
-    int rc = 0;
-#define ST(slot, src, dst, bytes) if(!rc) rc = stage_in(ctx, slot, src, (bytes), (const void**)&dst, s)
-    ST(0, w->pos_xz, d.pos_xz, n * 8);       ST(2, w->radius, d.radius, n * 4);   ST(5, w->flags, d.flags, n * 4);
-    ST(6, w->state, d.state, n);             ST(8, w->flock, d.flock, n * 4);
-    ST(10, w->flock_target_xz, d.flock_target_xz, F * 8);
-    ST(11, w->flock_offsets, d.flock_offsets, (F + 1) * 4);
-    ST(12, w->flock_members, d.flock_members, nmembers * 4);
-    ST(16, in->new_pos_xz, di.new_pos_xz, n * 8);   ST(17, in->vdes_xz, di.vdes_xz, n * 8);
-    ST(7, in->skip, di.skip, n);
-    ST(33, in->flock_layer, di.flock_layer, F);     ST(34, in->flock_nearest_xz, di.flock_nearest_xz, F * 8);
-    ST(35, in->flock_tiles_off, di.flock_tiles_off, (F + 1) * 4);
-    ST(41, in->flock_tiles, di.flock_tiles, ntiles * 4);
+    // (the arrays of the snapshot that k_state_update reads)
+    int rc = stage_world(ctx, w, &d, s, {offsetof(navhip_world, pos_xz), offsetof(navhip_world, radius), offsetof(navhip_world, flags),
+                                         offsetof(navhip_world, state), offsetof(navhip_world, flock),
+                                         offsetof(navhip_world, flock_target_xz), offsetof(navhip_world, flock_offsets),
+                                         offsetof(navhip_world, flock_members)});
+#define ST(slot, member, bytes) if(!rc) rc = stage_in(ctx, slot, in->member, (bytes), (const void**)&di.member, s)
+    ST(NH_STAGE_SIN_NEW_POS, new_pos_xz, n * 8);    ST(NH_STAGE_SIN_VDES, vdes_xz, n * 8);
+    ST(NH_STAGE_SIN_SKIP, skip, n);
+    ST(NH_STAGE_SIN_FLOCK_LAYER, flock_layer, F);   ST(NH_STAGE_SIN_FLOCK_NEAREST, flock_nearest_xz, F * 8);
+    ST(NH_STAGE_SIN_TILES_OFF, flock_tiles_off, (F + 1) * 4);
+    ST(NH_STAGE_SIN_TILES, flock_tiles, ntiles * 4);
 #undef ST
-    if(!rc && F > 0 && ntiles == 0) {
-        // (no destination has island tiles: the kernel still wants a pointer -- nothing is read from it)
-        rc = ensure_buf(ctx, ctx->stage[41], 4);
-        di.flock_tiles = (const int16_t*)ctx->stage[41].p;
-    }
-    if(!rc) rc = ensure_buf(ctx, ctx->stage[32], 2 * n);
+    // (no destination has island tiles: the kernel still wants a pointer -- nothing is read from it)
+    if(!rc && F > 0 && ntiles == 0) rc = nh_stage_reserve(ctx, NH_STAGE_SIN_TILES, 4, (void**)&di.flock_tiles);
+    uint8_t *d_out = nullptr;
+    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_SIN_OUT, 2 * n, (void**)&d_out);
     if(rc) return rc;
     nh_async_invalidate_static(ctx);
-    uint8_t *d_out = (uint8_t*)ctx->stage[32].p;
     rc = navhip_state_update_dev(ctx, &d, &di, d_out, d_out + n, s);
     if(rc) return rc;
     size_t b = (size_t)w->work_begin, e = (size_t)w->work_end;
@@ -1401,7 +1324,7 @@ int navhip_region_lookup(navhip_ctx *ctx, int nq, const float *pos_xz, const int
     hipStream_t s = ctx->stream;
     nh_step_params P;
     memset(&P, 0, sizeof(P));
-    fill_map_view(ctx, &P.map);
+    nh_fill_map_view(ctx, &P.map);
     P.map_x = map_pos_x; P.map_z = map_pos_z;
     const size_t nchunks = (size_t)ctx->nchunks;
     const bool resident = !region_field_slot && !field_pool;
@@ -1411,21 +1334,22 @@ int navhip_region_lookup(navhip_ctx *ctx, int nq, const float *pos_xz, const int
         n_region_rows = nh_pool_dests(ctx);
     }else{
         if(!region_field_slot || !field_pool || n_region_rows < 1 || n_field_slots < 1) return NAVHIP_ERR_INVALID;
-        int rc = stage_in(ctx, 47, region_field_slot, (size_t)n_region_rows * nchunks * 4, (const void**)&P.region_field_slot, s);
-        if(!rc) rc = stage_in(ctx, 14, field_pool, (size_t)n_field_slots * NH_CELLS, (const void**)&P.field_pool, s);
+        // (the slots of the world's own tables: the same data)
+        int rc = stage_in(ctx, NH_STAGE_REGION_FIELD_SLOT, region_field_slot, (size_t)n_region_rows * nchunks * 4, (const void**)&P.region_field_slot, s);
+        if(!rc) rc = stage_in(ctx, NH_STAGE_FIELD_POOL, field_pool, (size_t)n_field_slots * NH_CELLS, (const void**)&P.field_pool, s);
         if(rc) return rc;
         nh_async_invalidate_static(ctx);
     }
     for(int q = 0; q < nq; q++)
         if(rows[q] < -1 || rows[q] >= n_region_rows) return NAVHIP_ERR_INVALID;
     const float *d_pos; const int32_t *d_rows, *d_cen = nullptr, *d_rad = nullptr;
-    int rc = stage_in(ctx, 20, pos_xz, (size_t)nq * 8, (const void**)&d_pos, s);
-    if(!rc) rc = stage_in(ctx, 21, rows, (size_t)nq * 4, (const void**)&d_rows, s);
-    if(!rc && out_at_slot) rc = stage_in(ctx, 22, centre_abs, (size_t)nq * 8, (const void**)&d_cen, s);
-    if(!rc && out_at_slot) rc = stage_in(ctx, 23, radius, (size_t)nq * 4, (const void**)&d_rad, s);
-    if(!rc) rc = ensure_buf(ctx, ctx->stage[32], (size_t)nq * 2);
+    uint8_t *d_out = nullptr;
+    int rc = stage_in(ctx, NH_STAGE_CALL0, pos_xz, (size_t)nq * 8, (const void**)&d_pos, s);
+    if(!rc) rc = stage_in(ctx, NH_STAGE_CALL1, rows, (size_t)nq * 4, (const void**)&d_rows, s);
+    if(!rc && out_at_slot) rc = stage_in(ctx, NH_STAGE_CALL2, centre_abs, (size_t)nq * 8, (const void**)&d_cen, s);
+    if(!rc && out_at_slot) rc = stage_in(ctx, NH_STAGE_CALL3, radius, (size_t)nq * 4, (const void**)&d_rad, s);
+    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_CALL4, (size_t)nq * 2, (void**)&d_out);
     if(rc) return rc;
-    uint8_t *d_out = (uint8_t*)ctx->stage[32].p;
     nh_launch_region_lookup(P, nq, d_pos, d_rows, d_cen, d_rad, d_out, d_out + nq, s);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(out_dir, d_out, (size_t)nq, hipMemcpyDeviceToHost, s));
@@ -1462,20 +1386,19 @@ int navhip_spatial_query(navhip_ctx *ctx, const navhip_world *w, const float *qu
         return NAVHIP_ERR_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    navhip_world d = *w;
-    int rc = stage_in(ctx, 0, w->pos_xz, (size_t)w->n_ents * 8, (const void**)&d.pos_xz, s);
+    navhip_world d;
+    int rc = stage_world(ctx, w, &d, s, {offsetof(navhip_world, pos_xz)});
     if(rc) return rc;
-    const float *dq; 
-    rc = stage_in(ctx, 20, query_xz, (size_t)nq * 8, (const void**)&dq, s);
+    const float *dq;
+    int32_t *d_counts; uint32_t *d_ids;
+    rc = stage_in(ctx, NH_STAGE_CALL0, query_xz, (size_t)nq * 8, (const void**)&dq, s);
+    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_CALL1, (size_t)nq * 4, (void**)&d_counts);
+    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_CALL2, (size_t)nq * maxout * 4, (void**)&d_ids);
     if(rc) return rc;
-    rc = ensure_buf(ctx, ctx->stage[21], (size_t)nq * 4);
+    rc = nh_spatial_query_dev(ctx, &d, dq, nq, range, maxout, d_counts, d_ids, s);
     if(rc) return rc;
-    rc = ensure_buf(ctx, ctx->stage[22], (size_t)nq * maxout * 4);
-    if(rc) return rc;
-    rc = nh_spatial_query_dev(ctx, &d, dq, nq, range, maxout, (int32_t*)ctx->stage[21].p, (uint32_t*)ctx->stage[22].p, s);
-    if(rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(out_counts, ctx->stage[21].p, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(out_ids, ctx->stage[22].p, (size_t)nq * maxout * 4,
+    HIPCHK(ctx, hipMemcpyAsync(out_counts, d_counts, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(out_ids, d_ids, (size_t)nq * maxout * 4,
                                hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     return NAVHIP_OK;
@@ -1495,20 +1418,20 @@ static int clearpath_batch(navhip_ctx *ctx, int nq, const float *ent, const floa
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const void *d[6];
-    const void *h[6] = {ent, des_v, dyn, n_dyn, stat, n_stat};
-    const size_t b[6] = {(size_t)nq * 20, (size_t)nq * 8, (size_t)nq * 640, (size_t)nq * 4,
-                         (size_t)nq * 640, (size_t)nq * 4};
+    const struct { const void *host; size_t bytes; nh_stage_slot slot; } in[6] = {
+        {ent, (size_t)nq * 20, NH_STAGE_CALL0},   {des_v, (size_t)nq * 8, NH_STAGE_CALL1},  {dyn, (size_t)nq * 640, NH_STAGE_CALL2},
+        {n_dyn, (size_t)nq * 4, NH_STAGE_CALL3},  {stat, (size_t)nq * 640, NH_STAGE_CALL4}, {n_stat, (size_t)nq * 4, NH_STAGE_CALL5}};
     for(int i = 0; i < 6; i++) {
-        int rc = stage_in(ctx, i, h[i], b[i], &d[i], s);
+        int rc = stage_in(ctx, in[i].slot, in[i].host, in[i].bytes, &d[i], s);
         if(rc) return rc;
     }
-    int rc = ensure_buf(ctx, ctx->stage[15], (size_t)nq * 8);
+    float *d_out = nullptr;
+    int rc = nh_stage_reserve(ctx, NH_STAGE_CALL6, (size_t)nq * 8, (void**)&d_out);
     if(rc) return rc;
     nh_launch_clearpath(nq, (const float*)d[0], (const float*)d[1], (const float*)d[2],
-                        (const int32_t*)d[3], (const float*)d[4], (const int32_t*)d[5],
-                        (float*)ctx->stage[15].p, rows, s);
+                        (const int32_t*)d[3], (const float*)d[4], (const int32_t*)d[5], d_out, rows, s);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out, ctx->stage[15].p, (size_t)nq * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(out, d_out, (size_t)nq * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     return NAVHIP_OK;
 }

@@ -13,24 +13,16 @@
 #include "agent_internal.h"
 
 #include <algorithm>
+#include <iterator>
 #include <cstring>
 #include <list>
 #include <unordered_map>
 #include <vector>
 
-#define HIPCHK(ctx, expr)                                                                   \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if(_e != hipSuccess) {                                                              \
-            (ctx)->last_error = std::string(#expr) + ": " + hipGetErrorString(_e);          \
-            return NAVHIP_ERR_DEVICE;                                                       \
-        }                                                                                   \
-    } while(0)
-
 struct nh_pool {
-    int       n_slots, n_dests, nchunks;
-    uint8_t  *d_fields;                 // [n_slots][4096]
-    int32_t  *d_map;                    // [n_dests][nchunks] slot of the (dest, chunk) field, -1 = none
+    int       n_slots = 0, n_dests = 0, nchunks = 0;
+    uint8_t  *d_fields = nullptr;       // [n_slots][4096]
+    int32_t  *d_map = nullptr;          // [n_dests][nchunks] slot of the (dest, chunk) field, -1 = none
     std::vector<int32_t>  h_map;
     std::vector<uint64_t> id_of;        // per slot (valid when used[slot])
     std::vector<uint8_t>  used;
@@ -39,9 +31,8 @@ struct nh_pool {
     std::vector<std::list<int>::iterator> lru_it;
     std::vector<std::vector<int64_t>> refs;   // per slot: map entries that point at it
     // scratch
-    void *d_reqs; size_t d_reqs_cap;
-    int32_t *d_slots; size_t d_slots_cap;
-    int32_t *d_upd; size_t d_upd_cap;   // (index, value) pairs of map updates
+    nh_buf d_reqs, d_slots;             // requests and slot lists of a build
+    nh_buf d_upd;                       // (index, value) pairs of map updates
     std::vector<int32_t> pending;       // host list of (index, value) map updates not yet on the device
 };
 
@@ -59,17 +50,6 @@ __global__ void k_copy_field(uint8_t *fields, const int32_t *src_dst, int n)
     const uint4 *s = (const uint4*)(fields + ((size_t)src_dst[2 * i] << 12));
     uint4 *d = (uint4*)(fields + ((size_t)src_dst[2 * i + 1] << 12));
     d[threadIdx.x] = s[threadIdx.x];
-}
-
-static int grow(navhip_ctx *ctx, void **p, size_t *cap, size_t need)
-{
-    if(*cap >= need) return NAVHIP_OK;
-    if(*p) HIPCHK(ctx, hipFree(*p));
-    *p = nullptr; *cap = 0;
-    const size_t want = need + need / 2 + 64;
-    HIPCHK(ctx, hipMalloc(p, want));
-    *cap = want;
-    return NAVHIP_OK;
 }
 
 static void pool_touch(nh_pool *P, int slot)
@@ -159,11 +139,11 @@ static int pool_flush_map(navhip_ctx *ctx, nh_pool *P, hipStream_t s)
         }
     }
     const int n = (int)(P->pending.size() / 2);
-    int rc = grow(ctx, (void**)&P->d_upd, &P->d_upd_cap, P->pending.size() * sizeof(int32_t));
+    int rc = nh_ensure(ctx, P->d_upd, P->pending.size() * sizeof(int32_t));
     if(rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(P->d_upd, P->pending.data(), P->pending.size() * sizeof(int32_t),
+    HIPCHK(ctx, hipMemcpyAsync(P->d_upd.p, P->pending.data(), P->pending.size() * sizeof(int32_t),
                                hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_scatter_i32, dim3((n + 255) / 256), dim3(256), 0, s, P->d_map, (const int32_t*)P->d_upd, n);
+    hipLaunchKernelGGL(k_scatter_i32, dim3((n + 255) / 256), dim3(256), 0, s, P->d_map, (const int32_t*)P->d_upd.p, n);
     HIPCHK(ctx, hipStreamSynchronize(s));          // (the host vector is reused)
     P->pending.clear();
     return NAVHIP_OK;
@@ -189,9 +169,6 @@ int navhip_pool_create(navhip_ctx *ctx, int n_slots, int n_dests)
     nh_pool *P = new (std::nothrow) nh_pool();
     if(!P) return NAVHIP_ERR_NOMEM;
     P->n_slots = n_slots; P->n_dests = n_dests; P->nchunks = ctx->nchunks;
-    P->d_fields = nullptr; P->d_map = nullptr;
-    P->d_reqs = nullptr; P->d_reqs_cap = 0; P->d_slots = nullptr; P->d_slots_cap = 0;
-    P->d_upd = nullptr; P->d_upd_cap = 0;
     ctx->pool = P;
     HIPCHK(ctx, hipMalloc((void**)&P->d_fields, (size_t)n_slots * NH_CELLS));
     HIPCHK(ctx, hipMalloc((void**)&P->d_map, (size_t)n_dests * P->nchunks * sizeof(int32_t)));
@@ -212,7 +189,8 @@ void navhip_pool_destroy(navhip_ctx *ctx)
     nh_pool *P = ctx->pool;
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
-    hipFree(P->d_fields); hipFree(P->d_map); hipFree(P->d_reqs); hipFree(P->d_slots); hipFree(P->d_upd);
+    hipFree(P->d_fields); hipFree(P->d_map);
+    for(nh_buf *b : {&P->d_reqs, &P->d_slots, &P->d_upd}) hipFree(b->p);
     delete P;
     ctx->pool = nullptr;
 }
@@ -328,9 +306,11 @@ int navhip_pool_build(navhip_ctx *ctx, const navhip_field_req *reqs, const uint6
         }
         if((int)touched.size() > P->n_slots) { ctx->last_error = "navhip_pool_build: the call touches more fields than the pool has slots"; return NAVHIP_ERR_NOMEM; }
     }
-    rc = grow(ctx, &P->d_reqs, &P->d_reqs_cap, (size_t)n * sizeof(navhip_field_req));
-    if(!rc) rc = grow(ctx, (void**)&P->d_slots, &P->d_slots_cap, (size_t)n * 4 * sizeof(int32_t));
+    rc = nh_ensure(ctx, P->d_reqs, (size_t)n * sizeof(navhip_field_req));
+    if(!rc) rc = nh_ensure(ctx, P->d_slots, (size_t)n * 4 * sizeof(int32_t));
     if(rc) return rc;
+    navhip_field_req *d_reqs = (navhip_field_req*)P->d_reqs.p;
+    int32_t *d_slots = (int32_t*)P->d_slots.p;       // [n] slots, [2n] copy pairs, [n] slots to zero
     std::vector<int32_t> slots(n), copies, zeros;
     std::vector<uint8_t> pinned(P->n_slots, 0);
     std::vector<int> fresh_slots;
@@ -391,23 +371,22 @@ int navhip_pool_build(navhip_ctx *ctx, const navhip_field_req *reqs, const uint6
         const int m = end - begin;
         rc = pool_flush_map(ctx, P, s);
         if(rc) POOL_FAIL(rc);
-        POOL_HIPCHK(hipMemcpyAsync((char*)P->d_reqs + (size_t)begin * sizeof(navhip_field_req), &rq[begin],
+        POOL_HIPCHK(hipMemcpyAsync(d_reqs + begin, &rq[begin],
                                    (size_t)m * sizeof(navhip_field_req), hipMemcpyHostToDevice, s));
-        POOL_HIPCHK(hipMemcpyAsync(P->d_slots + begin, &slots[begin], (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        POOL_HIPCHK(hipMemcpyAsync(d_slots + begin, &slots[begin], (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, s));
         if(!zeros.empty()) {
-            int32_t *d_z = P->d_slots + 3 * (size_t)n;
+            int32_t *d_z = d_slots + 3 * (size_t)n;
             POOL_HIPCHK(hipMemcpyAsync(d_z, zeros.data(), zeros.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
             hipLaunchKernelGGL(k_zero_fields, dim3((unsigned)zeros.size()), dim3(256), 0, s, P->d_fields,
                                (const int32_t*)d_z, (int)zeros.size());
         }
         if(!copies.empty()) {
-            int32_t *d_cp = P->d_slots + n;
+            int32_t *d_cp = d_slots + n;
             POOL_HIPCHK(hipMemcpyAsync(d_cp, copies.data(), copies.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
             hipLaunchKernelGGL(k_copy_field, dim3((unsigned)(copies.size() / 2)), dim3(256), 0, s, P->d_fields,
                                (const int32_t*)d_cp, (int)(copies.size() / 2));
         }
-        rc = navhip_build_fields_slots_dev(ctx, (const navhip_field_req*)P->d_reqs + begin, m, P->d_fields,
-                                           P->d_slots + begin, s);
+        rc = navhip_build_fields_slots_dev(ctx, d_reqs + begin, m, P->d_fields, d_slots + begin, s);
         if(rc) POOL_FAIL(rc);
         POOL_HIPCHK(hipStreamSynchronize(s));       // (host vectors of the next sub-batch reuse the staging)
         begin = end;
@@ -449,21 +428,21 @@ static bool is_pinned(const void *p)
 }
 
 struct nh_async {
-    bool        pending;
-    bool        empty;           // the submitted world had no entities: nothing is in flight, poll / wait succeed
-    hipEvent_t  done;
+    bool        pending = false;
+    bool        empty = false;   // the submitted world had no entities: nothing is in flight, poll / wait succeed
+    hipEvent_t  done = nullptr;
     // pinned staging: one slab for the inputs, one for the outputs
-    char  *h_in;  size_t h_in_cap;
-    char  *h_out; size_t h_out_cap;
+    char  *h_in = nullptr;  size_t h_in_cap = 0;
+    char  *h_out = nullptr; size_t h_out_cap = 0;
     struct cp { void *dst; const void *src; size_t bytes; };
     std::vector<cp> finish;          // staging -> caller copies at completion
     // the attribute tables on the device are those of this epoch / entity count / flock count
-    uint32_t static_epoch; int32_t static_n, static_f;
+    uint32_t static_epoch = 0; int32_t static_n = 0, static_f = 0;
     // what the last submitted step left on the device: its snapshot (device addresses) and its outputs -- the state half
     // of the tick reads them in place (navhip_state_pass_resident)
-    bool            resident;
-    navhip_world    d_world;
-    navhip_step_out d_out;
+    bool            resident = false;
+    navhip_world    d_world = {};
+    navhip_step_out d_out = {};
 };
 
 static int pinned_grow(navhip_ctx *ctx, char **p, size_t *cap, size_t need)
@@ -487,10 +466,6 @@ int navhip_agent_step_submit(navhip_ctx *ctx, const navhip_world *w, const navhi
     if(!ctx->async) {
         ctx->async = new (std::nothrow) nh_async();
         if(!ctx->async) return NAVHIP_ERR_NOMEM;
-        ctx->async->pending = false; ctx->async->empty = false; ctx->async->h_in = ctx->async->h_out = nullptr;
-        ctx->async->h_in_cap = ctx->async->h_out_cap = 0;
-        ctx->async->static_epoch = 0; ctx->async->static_n = ctx->async->static_f = 0;
-        ctx->async->resident = false;
         HIPCHK(ctx, hipEventCreateWithFlags(&ctx->async->done, hipEventDisableTiming));
     }
     nh_async *A = ctx->async;
@@ -506,39 +481,14 @@ int navhip_agent_step_submit(navhip_ctx *ctx, const navhip_world *w, const navhi
     const size_t n = (size_t)w->n_ents, F = (size_t)w->n_flocks;
     size_t nmembers = (F > 0 && w->flock_offsets) ? (size_t)w->flock_offsets[F] : 0;
     const bool resident = w->n_field_slots == NAVHIP_POOL_RESIDENT;
-    struct item { const void *host; size_t bytes; int slot; const void **dev; bool attr; bool early; };
+    struct item { const void *host; size_t bytes; nh_stage_slot slot; const void **dev; bool attr; bool early; };
     navhip_world d = *w;
-    std::vector<item> items = {
-        {w->pos_xz, n * 8, 0, (const void**)&d.pos_xz, false, true},       {w->vel_xz, n * 8, 1, (const void**)&d.vel_xz, false, true},
-        // (radius, max_speed and flags change without any entity being added, removed or re-flocked --
-        // MOVE_CMD_SET_MAX_SPEED movement.c:3226, selection-radius updates, ENTITY_FLAG_GARRISONED toggled
-        // by the garrison module --: they travel every tick, only the flock tables are epoch-cached)
-        {w->radius, n * 4, 2, (const void**)&d.radius, false, true}, {w->max_speed, n * 4, 3, (const void**)&d.max_speed},
-        {w->speed, n * 4, 4, (const void**)&d.speed},         {w->flags, n * 4, 5, (const void**)&d.flags, false, true},
-        {w->state, n, 6, (const void**)&d.state, false, true},             {w->has_dest_los, n, 7, (const void**)&d.has_dest_los},
-        {w->flock, n * 4, 8, (const void**)&d.flock, true},         {w->vdes_xz, n * 8, 9, (const void**)&d.vdes_xz},
-        {w->flock_target_xz, F * 8, 10, (const void**)&d.flock_target_xz, true},
-        {w->flock_offsets, (F + 1) * 4, 11, (const void**)&d.flock_offsets, true},
-        {w->flock_members, nmembers * 4, 12, (const void**)&d.flock_members, true},
-        {w->form_ready, n, 24, (const void**)&d.form_ready},  {w->cell_pos_xz, n * 8, 25, (const void**)&d.cell_pos_xz},
-        {w->form_cohesion_xz, n * 8, 26, (const void**)&d.form_cohesion_xz},
-        {w->form_align_xz, n * 8, 27, (const void**)&d.form_align_xz},
-        {w->form_drag_xz, n * 8, 28, (const void**)&d.form_drag_xz},
-        {w->arrival_sink_xz, n * 8, 36, (const void**)&d.arrival_sink_xz, false, true},
-        {w->arrival_flags, n, 37, (const void**)&d.arrival_flags, false, true},
-        {w->los_pool, (size_t)(w->n_los_slots > 0 ? w->n_los_slots : 0) * NH_CELLS, 38, (const void**)&d.los_pool},
-        {w->flock_los_slot, F * (size_t)ctx->nchunks * 4, 39, (const void**)&d.flock_los_slot},
-        {w->los_pos_xz, n * 8, 40, (const void**)&d.los_pos_xz},
-        {w->region_row, n * 4, 46, (const void**)&d.region_row},
-    };
-    if(!resident)
-        items.push_back({w->region_field_slot, (size_t)(w->n_region_rows > 0 ? w->n_region_rows : 0) * (size_t)ctx->nchunks * 4,
-                         47, (const void**)&d.region_field_slot});
-    if(!resident) {
-        items.push_back({w->flock_field_slot, F * (size_t)ctx->nchunks * 4, 13, (const void**)&d.flock_field_slot});
-        items.push_back({w->field_pool, (size_t)(w->n_field_slots > 0 ? w->n_field_slots : 0) * NH_CELLS, 14,
-                         (const void**)&d.field_pool});
-    }
+    std::vector<item> items;
+    items.reserve(std::size(nh_world_rows));
+    for(const nh_world_row &r : nh_world_rows)
+        if(!(resident && (r.flags & NH_ROW_NOT_RESIDENT)))
+            items.push_back({nh_member(w, r.off), nh_world_row_bytes(r, w, (size_t)ctx->nchunks, nmembers), r.slot,
+                             (const void**)&nh_member(&d, r.off), (r.flags & NH_ROW_ATTR) != 0, (r.flags & NH_ROW_EARLY) != 0});
     // inputs: pageable arrays are packed into the pinned slab (one memcpy each) and cross the bus as ONE
     // transfer into one device slab -- a dozen separate copies cost a dozen hand-overs to the copy
     // engine, more than the bytes --; pinned ones (navhip_host_alloc) are transferred in place
@@ -552,7 +502,7 @@ int navhip_agent_step_submit(navhip_ctx *ctx, const navhip_world *w, const navhi
     int rc = pinned_grow(ctx, &A->h_in, &A->h_in_cap, need);
     if(rc) return rc;
     char *d_slab = nullptr;
-    if(need) { rc = navhip_stage_reserve(ctx, 44, need, (void**)&d_slab); if(rc) return rc; }
+    if(need) { rc = nh_stage_reserve(ctx, NH_STAGE_SUBMIT_IN, need, (void**)&d_slab); if(rc) return rc; }
     // Two passes: what the front of the step reads (positions, velocities, states, the attribute
     // tables) goes first and the front is started on it (navhip_agent_prefetch_dev); the rest is packed
     // and transferred while the spatial hash, the neighbour walk and the cohesion term run.
@@ -562,7 +512,7 @@ int navhip_agent_step_submit(navhip_ctx *ctx, const navhip_world *w, const navhi
         for(auto &it : items) {
             if(!it.host || (it.attr || it.early) != (pass == 0)) continue;
             if(it.attr || is_pinned(it.host)) {
-                rc = navhip_stage_reserve(ctx, it.slot, it.bytes, (void**)it.dev);
+                rc = nh_stage_reserve(ctx, it.slot, it.bytes, (void**)it.dev);
                 if(rc) return rc;
                 if(it.attr && attrs_resident) continue;
                 if(it.bytes) HIPCHK(ctx, hipMemcpyAsync((void*)*it.dev, it.host, it.bytes, hipMemcpyHostToDevice, s));
@@ -587,7 +537,7 @@ int navhip_agent_step_submit(navhip_ctx *ctx, const navhip_world *w, const navhi
             size_t o2 = off;
             for(auto &it : items) {
                 if(!it.host || it.attr || it.early) continue;
-                if(is_pinned(it.host)) { rc = navhip_stage_reserve(ctx, it.slot, it.bytes, (void**)it.dev); if(rc) return rc; }
+                if(is_pinned(it.host)) { rc = nh_stage_reserve(ctx, it.slot, it.bytes, (void**)it.dev); if(rc) return rc; }
                 else { *it.dev = d_slab + o2; o2 += (it.bytes + AL - 1) & ~(AL - 1); }
             }
             rc = navhip_agent_prefetch_dev(ctx, &d, s);
@@ -599,10 +549,12 @@ int navhip_agent_step_submit(navhip_ctx *ctx, const navhip_world *w, const navhi
     size_t b = (size_t)w->work_begin, e = (size_t)w->work_end;
     if(b == 0 && e == 0) e = n;
     navhip_step_out dout = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    struct oitem { void **dev; void *host; size_t row; int slot; size_t off; } outs[5] = {
-        {(void**)&dout.vel_xz, out->vel_xz, 8, 15, 0},   {(void**)&dout.new_pos_xz, out->new_pos_xz, 8, 16, 0},
-        {(void**)&dout.vdes_xz, out->vdes_xz, 8, 17, 0}, {(void**)&dout.vpref_xz, out->vpref_xz, 8, 18, 0},
-        {(void**)&dout.status, out->status, 1, 19, 0}};
+    struct oitem { void **dev; void *host; size_t row; nh_stage_slot slot; size_t off; };
+    oitem outs[std::size(nh_out_rows)];
+    for(size_t k = 0; k < std::size(nh_out_rows); k++) {
+        const nh_out_row &o = nh_out_rows[k];
+        outs[k] = {&nh_member(&dout, o.off), (void*)nh_member(out, o.off), o.row_bytes, o.slot, 0};
+    }
     // (a pageable output lives in the slab as its rows [b, e): the kernels index by entity, so the
     // array's device address is the slab position minus b rows)
     size_t oneed = 0;
@@ -610,11 +562,11 @@ int navhip_agent_step_submit(navhip_ctx *ctx, const navhip_world *w, const navhi
     rc = pinned_grow(ctx, &A->h_out, &A->h_out_cap, oneed);
     if(rc) return rc;
     char *d_oslab = nullptr;
-    if(oneed) { rc = navhip_stage_reserve(ctx, 45, oneed, (void**)&d_oslab); if(rc) return rc; }
+    if(oneed) { rc = nh_stage_reserve(ctx, NH_STAGE_SUBMIT_OUT, oneed, (void**)&d_oslab); if(rc) return rc; }
     for(auto &o : outs) {
         if(!o.host) continue;
         if(is_pinned(o.host)) {
-            rc = navhip_stage_reserve(ctx, o.slot, n * o.row, o.dev);
+            rc = nh_stage_reserve(ctx, o.slot, n * o.row, o.dev);
             if(rc) return rc;
         }else{
             *o.dev = d_oslab + o.off - b * o.row;

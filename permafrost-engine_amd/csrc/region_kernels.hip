@@ -160,13 +160,7 @@ void nh_launch_region_fields(navhip_ctx *ctx, const navhip_region_req *d_reqs, i
                              size_t out_stride, hipStream_t s)
 {
     nh_map_view mv;
-    mv.w = ctx->w;
-    mv.h = ctx->h;
-    for(int l = 0; l < NAVHIP_NAV_LAYER_MAX; l++) {
-        const navhip_layer &L = ctx->layers[l];
-        mv.layers[l] = nh_layer_view{L.cost, L.blockers, L.local_islands, L.factions,
-                                     L.passmask, L.unit_cost, L.changed, L.islands};
-    }
+    nh_fill_map_view(ctx, &mv);
     const size_t lds = (size_t)max_dim * max_dim * 5;
     // (per device, not per process: every context's device needs the attribute)
     static bool attr_set[64] = {false};

@@ -17,12 +17,8 @@
 #include "agent_internal.h"
 #include "agent_math.h"
 
-#define SK_SLOT      43          /* ctx->stage[] slot this file owns                                     */
 #define SK_QUERY_R   30.0f       /* SEPARATION_NEIGHB_RADIUS, movement.c:428                            */
 #define SK_QUERY_MAX 128         /* near_ents[128], movement.c:997                                      */
-
-#define SKCHK(ctx, call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { \
-    (ctx)->last_error = std::string(#call) + ": " + hipGetErrorString(e_); return NAVHIP_ERR_DEVICE; } } while(0)
 
 // ---------------------------------------------------------------------------------------------
 // the heading gate, a thread per unit
@@ -487,12 +483,7 @@ struct sk_arena {                     // one staging slot, carved up: offsets fi
 void sk_map_view(const navhip_ctx *ctx, const navhip_world *w, nh_step_params *P)
 {
     memset(P, 0, sizeof(*P));
-    P->map.w = ctx->w; P->map.h = ctx->h;
-    for(int l = 0; l < NAVHIP_NAV_LAYER_MAX; l++) {
-        const navhip_layer &L = ctx->layers[l];
-        P->map.layers[l] = nh_layer_view{L.cost, L.blockers, L.local_islands, L.factions,
-                                         L.passmask, L.unit_cost, L.changed, L.islands, L.probemask};
-    }
+    nh_fill_map_view(ctx, &P->map);
     P->map_x = w->map_pos_x; P->map_z = w->map_pos_z;
     P->n_ents = w->n_ents; P->hz = w->hz;
 }
@@ -545,7 +536,7 @@ int navhip_heading_gate_dev(navhip_ctx *ctx, const navhip_world *w, const navhip
     if(!sk_interp_inputs_ok(w, in)) return NAVHIP_ERR_INVALID;
     int b, e;
     if(!sk_work_range(w, &b, &e)) return NAVHIP_ERR_INVALID;
-    SKCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
     if(in->interp_from_xz) {
         // (the accept test of the interpolated position probes the derived row masks: rebuilt here if a plane changed)
         int rc = nh_refresh_derived(ctx, ctx->stream);
@@ -556,7 +547,7 @@ int navhip_heading_gate_dev(navhip_ctx *ctx, const navhip_world *w, const navhip
     if(e > b)
         hipLaunchKernelGGL(k_heading_gate, dim3((e - b + 255) / 256), dim3(256), 0, stream ? (hipStream_t)stream : ctx->stream,
                            P, b, e, w->pos_xz, w->vel_xz, w->state, w->radius, w->flags, *in, out_vel, out_new_pos, out_gate);
-    SKCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipGetLastError());
     return NAVHIP_OK;
 }
 
@@ -568,7 +559,7 @@ int navhip_heading_gate(navhip_ctx *ctx, const navhip_world *w, const navhip_gat
     if(!w->pos_xz || !w->vel_xz || !w->state || !in->next_rot || !in->new_vel_xz || !in->vdes_xz) return NAVHIP_ERR_INVALID;
     int b, e;
     if(!sk_work_range(w, &b, &e)) return NAVHIP_ERR_INVALID;
-    SKCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const size_t n = (size_t)w->n_ents;
     if(!sk_interp_inputs_ok(w, in)) return NAVHIP_ERR_INVALID;
@@ -578,22 +569,22 @@ int navhip_heading_gate(navhip_ctx *ctx, const navhip_world *w, const navhip_gat
                  o_nv = A.take(n * 8), o_vd = A.take(n * 8), o_ov = A.take(n * 8), o_op = A.take(n * 8), o_og = A.take(n),
                  o_if = A.take(ip ? n * 8 : 0), o_is = A.take(ip ? n * 4 : 0), o_rad = A.take(ip ? n * 4 : 0), o_flg = A.take(ip ? n * 4 : 0);
     char *base;
-    int rc = navhip_stage_reserve(ctx, SK_SLOT, A.total, (void**)&base);
+    int rc = nh_stage_reserve(ctx, NH_STAGE_STATE_ARENA, A.total, (void**)&base);
     if(rc) return rc;
-    SKCHK(ctx, hipMemcpyAsync(base + o_pos, w->pos_xz, n * 8, hipMemcpyHostToDevice, s));
-    SKCHK(ctx, hipMemcpyAsync(base + o_vel, w->vel_xz, n * 8, hipMemcpyHostToDevice, s));
-    SKCHK(ctx, hipMemcpyAsync(base + o_state, w->state, n, hipMemcpyHostToDevice, s));
-    SKCHK(ctx, hipMemcpyAsync(base + o_rot, in->next_rot, n * 16, hipMemcpyHostToDevice, s));
-    SKCHK(ctx, hipMemcpyAsync(base + o_nv, in->new_vel_xz, n * 8, hipMemcpyHostToDevice, s));
-    SKCHK(ctx, hipMemcpyAsync(base + o_vd, in->vdes_xz, n * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_pos, w->pos_xz, n * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_vel, w->vel_xz, n * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_state, w->state, n, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_rot, in->next_rot, n * 16, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_nv, in->new_vel_xz, n * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_vd, in->vdes_xz, n * 8, hipMemcpyHostToDevice, s));
     navhip_world d = *w;
     d.pos_xz = (const float*)(base + o_pos); d.vel_xz = (const float*)(base + o_vel); d.state = (const uint8_t*)(base + o_state);
     navhip_gate_in di = {(const float*)(base + o_rot), (const float*)(base + o_nv), (const float*)(base + o_vd), nullptr, nullptr};
     if(ip) {
-        SKCHK(ctx, hipMemcpyAsync(base + o_if, in->interp_from_xz, n * 8, hipMemcpyHostToDevice, s));
-        SKCHK(ctx, hipMemcpyAsync(base + o_is, in->interp_step, n * 4, hipMemcpyHostToDevice, s));
-        SKCHK(ctx, hipMemcpyAsync(base + o_rad, w->radius, n * 4, hipMemcpyHostToDevice, s));
-        SKCHK(ctx, hipMemcpyAsync(base + o_flg, w->flags, n * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_if, in->interp_from_xz, n * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_is, in->interp_step, n * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_rad, w->radius, n * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_flg, w->flags, n * 4, hipMemcpyHostToDevice, s));
         di.interp_from_xz = (const float*)(base + o_if); di.interp_step = (const float*)(base + o_is);
         d.radius = (const float*)(base + o_rad); d.flags = (const uint32_t*)(base + o_flg);
     }
@@ -601,11 +592,11 @@ int navhip_heading_gate(navhip_ctx *ctx, const navhip_world *w, const navhip_gat
     if(rc) return rc;
     if(e > b) {
         const size_t lo = (size_t)b, cnt = (size_t)(e - b);
-        SKCHK(ctx, hipMemcpyAsync(out_vel + 2 * lo, base + o_ov + 8 * lo, cnt * 8, hipMemcpyDeviceToHost, s));
-        SKCHK(ctx, hipMemcpyAsync(out_new_pos + 2 * lo, base + o_op + 8 * lo, cnt * 8, hipMemcpyDeviceToHost, s));
-        SKCHK(ctx, hipMemcpyAsync(out_gate + lo, base + o_og + lo, cnt, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(out_vel + 2 * lo, base + o_ov + 8 * lo, cnt * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(out_new_pos + 2 * lo, base + o_op + 8 * lo, cnt * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(out_gate + lo, base + o_og + lo, cnt, hipMemcpyDeviceToHost, s));
     }
-    SKCHK(ctx, hipStreamSynchronize(s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
     return NAVHIP_OK;
 }
 
@@ -619,7 +610,7 @@ int navhip_state_update_aux_dev(navhip_ctx *ctx, const navhip_world *w, const na
         return NAVHIP_ERR_INVALID;
     int b, e;
     if(!sk_work_range(w, &b, &e)) return NAVHIP_ERR_INVALID;
-    SKCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
     nh_step_params P;
     sk_map_view(ctx, w, &P);
     P.work_begin = b; P.work_end = e;
@@ -627,7 +618,7 @@ int navhip_state_update_aux_dev(navhip_ctx *ctx, const navhip_world *w, const na
     if(e > b)
         hipLaunchKernelGGL(k_state_aux, dim3((e - b + 255) / 256), dim3(256), 0, stream ? (hipStream_t)stream : ctx->stream,
                            P, w->pos_xz, w->radius, w->flags, w->state, *in, io_state, io_flags, out_ticks);
-    SKCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipGetLastError());
     return NAVHIP_OK;
 }
 
@@ -661,7 +652,7 @@ int navhip_state_update_aux(navhip_ctx *ctx, const navhip_world *w, const navhip
             && (in->range_tiles_row[i] < 0 || in->range_tiles_row[i] >= rows)) return NAVHIP_ERR_INVALID;
         }
     }
-    SKCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     sk_arena A;
     const size_t o_rad = A.take(n * 4), o_fl = A.take(n * 4), o_st = A.take(n), o_fs = A.take(n), o_wt = A.take(n * 4),
@@ -678,17 +669,17 @@ int navhip_state_update_aux(navhip_ctx *ctx, const navhip_world *w, const navhip
                  o_stp = A.take(su ? n * 8 : 0), o_snp = A.take(su ? n * 8 : 0), o_sd = A.take(su ? n * 16 : 0),
                  o_svd = A.take(su ? n * 8 : 0), o_sout = A.take(su ? n * 8 : 0);
     char *base;
-    int rc = navhip_stage_reserve(ctx, SK_SLOT, A.total, (void**)&base);
+    int rc = nh_stage_reserve(ctx, NH_STAGE_STATE_ARENA, A.total, (void**)&base);
     if(rc) return rc;
-    SKCHK(ctx, hipMemcpyAsync(base + o_rad, w->radius, n * 4, hipMemcpyHostToDevice, s));
-    SKCHK(ctx, hipMemcpyAsync(base + o_fl, w->flags, n * 4, hipMemcpyHostToDevice, s));
-    SKCHK(ctx, hipMemcpyAsync(base + o_st, w->state, n, hipMemcpyHostToDevice, s));
-    SKCHK(ctx, hipMemcpyAsync(base + o_fs, in->fstate, n, hipMemcpyHostToDevice, s));
-    SKCHK(ctx, hipMemcpyAsync(base + o_wt, in->wait_ticks_left, n * 4, hipMemcpyHostToDevice, s));
-    SKCHK(ctx, hipMemcpyAsync(base + o_wp, in->wait_prev, n, hipMemcpyHostToDevice, s));
-    SKCHK(ctx, hipMemcpyAsync(base + o_np, in->new_pos_xz, n * 8, hipMemcpyHostToDevice, s));
-    SKCHK(ctx, hipMemcpyAsync(base + o_ios, io_state, n, hipMemcpyHostToDevice, s));
-    SKCHK(ctx, hipMemcpyAsync(base + o_iof, io_flags, n, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_rad, w->radius, n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_fl, w->flags, n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_st, w->state, n, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_fs, in->fstate, n, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_wt, in->wait_ticks_left, n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_wp, in->wait_prev, n, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_np, in->new_pos_xz, n * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_ios, io_state, n, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_iof, io_flags, n, hipMemcpyHostToDevice, s));
     navhip_world d = *w;
     d.radius = (const float*)(base + o_rad); d.flags = (const uint32_t*)(base + o_fl); d.state = (const uint8_t*)(base + o_st);
     d.pos_xz = nullptr;                          // (only the enter-range arm reads positions: staged below with its inputs)
@@ -697,13 +688,13 @@ int navhip_state_update_aux(navhip_ctx *ctx, const navhip_world *w, const navhip
     di.fstate = (const uint8_t*)(base + o_fs); di.wait_ticks_left = (const int32_t*)(base + o_wt);
     di.wait_prev = (const uint8_t*)(base + o_wp); di.new_pos_xz = (const float*)(base + o_np);
     if(rg) {
-        SKCHK(ctx, hipMemcpyAsync(base + o_pos, w->pos_xz, n * 8, hipMemcpyHostToDevice, s));
-        SKCHK(ctx, hipMemcpyAsync(base + o_rt, in->range_target, n * 4, hipMemcpyHostToDevice, s));
-        SKCHK(ctx, hipMemcpyAsync(base + o_rr, in->target_range, n * 4, hipMemcpyHostToDevice, s));
-        SKCHK(ctx, hipMemcpyAsync(base + o_rp, in->target_prev_xz, n * 8, hipMemcpyHostToDevice, s));
-        SKCHK(ctx, hipMemcpyAsync(base + o_row, in->range_tiles_row, n * 4, hipMemcpyHostToDevice, s));
-        SKCHK(ctx, hipMemcpyAsync(base + o_off, in->range_tiles_off, (rows + 1) * 4, hipMemcpyHostToDevice, s));
-        if(n_rt) SKCHK(ctx, hipMemcpyAsync(base + o_til, in->range_tiles, n_rt * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_pos, w->pos_xz, n * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_rt, in->range_target, n * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_rr, in->target_range, n * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_rp, in->target_prev_xz, n * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_row, in->range_tiles_row, n * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_off, in->range_tiles_off, (rows + 1) * 4, hipMemcpyHostToDevice, s));
+        if(n_rt) HIPCHK(ctx, hipMemcpyAsync(base + o_til, in->range_tiles, n_rt * 4, hipMemcpyHostToDevice, s));
         d.pos_xz = (const float*)(base + o_pos);
         di.range_target = (const int32_t*)(base + o_rt); di.target_range = (const float*)(base + o_rr);
         di.target_prev_xz = (const float*)(base + o_rp); di.range_tiles_row = (const int32_t*)(base + o_row);
@@ -711,21 +702,21 @@ int navhip_state_update_aux(navhip_ctx *ctx, const navhip_world *w, const navhip
         di.n_range_rows = in->n_range_rows;
     }
     if(in->ent_rot) {
-        SKCHK(ctx, hipMemcpyAsync(base + o_er, in->ent_rot, n * 16, hipMemcpyHostToDevice, s));
-        SKCHK(ctx, hipMemcpyAsync(base + o_td, in->target_dir, n * 16, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_er, in->ent_rot, n * 16, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_td, in->target_dir, n * 16, hipMemcpyHostToDevice, s));
         di.ent_rot = (const float*)(base + o_er); di.target_dir = (const float*)(base + o_td);
     }
     if(su) {
-        if(!rg) { SKCHK(ctx, hipMemcpyAsync(base + o_spos, w->pos_xz, n * 8, hipMemcpyHostToDevice, s)); d.pos_xz = (const float*)(base + o_spos); }
-        SKCHK(ctx, hipMemcpyAsync(base + o_svel, w->vel_xz, n * 8, hipMemcpyHostToDevice, s));
-        SKCHK(ctx, hipMemcpyAsync(base + o_sflock, w->flock, n * 4, hipMemcpyHostToDevice, s));
-        if(F) SKCHK(ctx, hipMemcpyAsync(base + o_sftgt, w->flock_target_xz, F * 8, hipMemcpyHostToDevice, s));
-        SKCHK(ctx, hipMemcpyAsync(base + o_stgt, in->surround_target, n * 4, hipMemcpyHostToDevice, s));
-        SKCHK(ctx, hipMemcpyAsync(base + o_sq, in->surround_query, n, hipMemcpyHostToDevice, s));
-        SKCHK(ctx, hipMemcpyAsync(base + o_stp, in->surround_target_prev_xz, n * 8, hipMemcpyHostToDevice, s));
-        SKCHK(ctx, hipMemcpyAsync(base + o_snp, in->surround_nearest_prev_xz, n * 8, hipMemcpyHostToDevice, s));
-        SKCHK(ctx, hipMemcpyAsync(base + o_sd, in->surround_dest_xz, n * 16, hipMemcpyHostToDevice, s));
-        SKCHK(ctx, hipMemcpyAsync(base + o_svd, in->vdes_xz, n * 8, hipMemcpyHostToDevice, s));
+        if(!rg) { HIPCHK(ctx, hipMemcpyAsync(base + o_spos, w->pos_xz, n * 8, hipMemcpyHostToDevice, s)); d.pos_xz = (const float*)(base + o_spos); }
+        HIPCHK(ctx, hipMemcpyAsync(base + o_svel, w->vel_xz, n * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_sflock, w->flock, n * 4, hipMemcpyHostToDevice, s));
+        if(F) HIPCHK(ctx, hipMemcpyAsync(base + o_sftgt, w->flock_target_xz, F * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_stgt, in->surround_target, n * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_sq, in->surround_query, n, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_stp, in->surround_target_prev_xz, n * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_snp, in->surround_nearest_prev_xz, n * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_sd, in->surround_dest_xz, n * 16, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_svd, in->vdes_xz, n * 8, hipMemcpyHostToDevice, s));
         d.vel_xz = (const float*)(base + o_svel); d.flock = (const int32_t*)(base + o_sflock);
         d.flock_target_xz = (const float*)(base + o_sftgt);
         di.surround_target = (const int32_t*)(base + o_stgt); di.surround_query = (const uint8_t*)(base + o_sq);
@@ -737,12 +728,12 @@ int navhip_state_update_aux(navhip_ctx *ctx, const navhip_world *w, const navhip
     if(rc) return rc;
     if(e > b) {
         const size_t lo = (size_t)b, cnt = (size_t)(e - b);
-        if(su) SKCHK(ctx, hipMemcpyAsync(in->out_surround_dest_xz + 2 * lo, base + o_sout + 8 * lo, cnt * 8, hipMemcpyDeviceToHost, s));
-        SKCHK(ctx, hipMemcpyAsync(io_state + lo, base + o_ios + lo, cnt, hipMemcpyDeviceToHost, s));
-        SKCHK(ctx, hipMemcpyAsync(io_flags + lo, base + o_iof + lo, cnt, hipMemcpyDeviceToHost, s));
-        SKCHK(ctx, hipMemcpyAsync(out_ticks + lo, base + o_ot + 4 * lo, cnt * 4, hipMemcpyDeviceToHost, s));
+        if(su) HIPCHK(ctx, hipMemcpyAsync(in->out_surround_dest_xz + 2 * lo, base + o_sout + 8 * lo, cnt * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(io_state + lo, base + o_ios + lo, cnt, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(io_flags + lo, base + o_iof + lo, cnt, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(out_ticks + lo, base + o_ot + 4 * lo, cnt * 4, hipMemcpyDeviceToHost, s));
     }
-    SKCHK(ctx, hipStreamSynchronize(s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
     return NAVHIP_OK;
 }
 
@@ -795,7 +786,7 @@ int navhip_state_pass(navhip_ctx *ctx, const navhip_world *w, const navhip_state
             && (X.range_tiles_row[i] < 0 || (size_t)X.range_tiles_row[i] >= rows)) return NAVHIP_ERR_INVALID;
         }
     }
-    SKCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     sk_arena A;
     struct up { size_t off; const void *src; size_t bytes; };
@@ -822,9 +813,9 @@ int navhip_state_pass(navhip_ctx *ctx, const navhip_world *w, const navhip_state
     // results
     const size_t r_vel = A.take(n * 8), r_np = A.take(n * 8), r_gate = A.take(n), r_st = A.take(n), r_fl = A.take(n), r_tk = A.take(n * 4);
     char *base;
-    int rc = navhip_stage_reserve(ctx, SK_SLOT, A.total, (void**)&base);
+    int rc = nh_stage_reserve(ctx, NH_STAGE_STATE_ARENA, A.total, (void**)&base);
     if(rc) return rc;
-    for(const up &u : ups) SKCHK(ctx, hipMemcpyAsync(base + u.off, u.src, u.bytes, hipMemcpyHostToDevice, s));
+    for(const up &u : ups) HIPCHK(ctx, hipMemcpyAsync(base + u.off, u.src, u.bytes, hipMemcpyHostToDevice, s));
     navhip_world d = *w;
     d.pos_xz = (const float*)(base + o_pos); d.vel_xz = (const float*)(base + o_vel); d.radius = (const float*)(base + o_rad);
     d.flags = (const uint32_t*)(base + o_flg); d.state = (const uint8_t*)(base + o_st); d.flock = (const int32_t*)(base + o_flock);
@@ -869,22 +860,19 @@ int navhip_state_pass(navhip_ctx *ctx, const navhip_world *w, const navhip_state
         hipLaunchKernelGGL(k_gate_host_rows, dim3((e - b + 255) / 256), dim3(256), 0, s, b, e, (const uint8_t*)(base + r_gate),
                            (const uint8_t*)(base + o_st), aux ? (const int32_t*)(base + o_wt) : (const int32_t*)nullptr,
                            (uint8_t*)(base + r_st), (uint8_t*)(base + r_fl), aux ? (int32_t*)(base + r_tk) : (int32_t*)nullptr);
-        SKCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipGetLastError());
         const size_t lo = (size_t)b, cnt = (size_t)(e - b);
-        SKCHK(ctx, hipMemcpyAsync(out->state + lo, base + r_st + lo, cnt, hipMemcpyDeviceToHost, s));
-        SKCHK(ctx, hipMemcpyAsync(out->flags + lo, base + r_fl + lo, cnt, hipMemcpyDeviceToHost, s));
-        SKCHK(ctx, hipMemcpyAsync(out->gate + lo, base + r_gate + lo, cnt, hipMemcpyDeviceToHost, s));
-        SKCHK(ctx, hipMemcpyAsync(out->new_pos_xz + 2 * lo, base + r_np + 8 * lo, cnt * 8, hipMemcpyDeviceToHost, s));
-        if(out->vel_xz) SKCHK(ctx, hipMemcpyAsync(out->vel_xz + 2 * lo, base + r_vel + 8 * lo, cnt * 8, hipMemcpyDeviceToHost, s));
-        if(aux) SKCHK(ctx, hipMemcpyAsync(out->wait_ticks_left + lo, base + r_tk + 4 * lo, cnt * 4, hipMemcpyDeviceToHost, s));
-        if(su) SKCHK(ctx, hipMemcpyAsync(X.out_surround_dest_xz + 2 * lo, base + r_sd + 8 * lo, cnt * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(out->state + lo, base + r_st + lo, cnt, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(out->flags + lo, base + r_fl + lo, cnt, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(out->gate + lo, base + r_gate + lo, cnt, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(out->new_pos_xz + 2 * lo, base + r_np + 8 * lo, cnt * 8, hipMemcpyDeviceToHost, s));
+        if(out->vel_xz) HIPCHK(ctx, hipMemcpyAsync(out->vel_xz + 2 * lo, base + r_vel + 8 * lo, cnt * 8, hipMemcpyDeviceToHost, s));
+        if(aux) HIPCHK(ctx, hipMemcpyAsync(out->wait_ticks_left + lo, base + r_tk + 4 * lo, cnt * 4, hipMemcpyDeviceToHost, s));
+        if(su) HIPCHK(ctx, hipMemcpyAsync(X.out_surround_dest_xz + 2 * lo, base + r_sd + 8 * lo, cnt * 8, hipMemcpyDeviceToHost, s));
     }
-    SKCHK(ctx, hipStreamSynchronize(s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
     return NAVHIP_OK;
 }
-
-#define SK_IN_SLOT  42          /* device slab of the resident pass's inputs  */
-#define SK_OUT_SLOT 31          /* ... and of its results                      */
 
 int navhip_state_pass_resident(navhip_ctx *ctx, const navhip_state_pass_in *in, const navhip_state_pass_out *out)
 {
@@ -940,7 +928,7 @@ int navhip_state_pass_resident(navhip_ctx *ctx, const navhip_state_pass_in *in, 
     if(su)
         for(size_t i = v0; i < v1; i++)
             if(X.surround_target[i] >= d.n_ents) return NAVHIP_ERR_INVALID;
-    SKCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     // ---- inputs: one device slab; pageable arrays are packed into the pinned slab and cross the bus as ONE transfer,
     // pinned ones (navhip_host_alloc) are transferred in place
@@ -984,8 +972,8 @@ int navhip_state_pass_resident(navhip_ctx *ctx, const navhip_state_pass_in *in, 
     for(auto &o : outs) { o.pinned = nh_is_pinned(o.dst); if(!o.pinned) { o.h_off = pack_out; pack_out += (o.cnt * o.row + 255) & ~(size_t)255; } }
     char *h_in = nullptr, *h_out = nullptr, *base = nullptr, *res = nullptr;
     int rc = nh_async_slabs(ctx, pack_in, pack_out, &h_in, &h_out);
-    if(!rc) rc = navhip_stage_reserve(ctx, SK_IN_SLOT, in_total + pack_in + 256, (void**)&base);
-    if(!rc) rc = navhip_stage_reserve(ctx, SK_OUT_SLOT, R.total + pack_out + 256, (void**)&res);
+    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_PASS_IN, in_total + pack_in + 256, (void**)&base);
+    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_PASS_OUT, R.total + pack_out + 256, (void**)&res);
     if(rc) return rc;
     // (the pageable inputs: packed, sent as one block behind the arrays' own region, then laid out by device-to-device
     // copies?  No: the layout IS the packing order -- every pageable item gets its device address inside the block)
@@ -995,7 +983,7 @@ int navhip_state_pass_resident(navhip_ctx *ctx, const navhip_state_pass_in *in, 
     for(size_t k = 0; k < items.size(); k++) {
         item &it = items[k];
         if(it.pinned) {
-            SKCHK(ctx, hipMemcpyAsync(base + it.off, it.src, it.bytes, hipMemcpyHostToDevice, s));
+            HIPCHK(ctx, hipMemcpyAsync(base + it.off, it.src, it.bytes, hipMemcpyHostToDevice, s));
             dev_of[k] = base + it.off;
         }else{
             memcpy(h_in + poff, it.src, it.bytes);
@@ -1003,7 +991,7 @@ int navhip_state_pass_resident(navhip_ctx *ctx, const navhip_state_pass_in *in, 
             poff += (it.bytes + 255) & ~(size_t)255;
         }
     }
-    if(poff) SKCHK(ctx, hipMemcpyAsync(d_block, h_in, poff, hipMemcpyHostToDevice, s));
+    if(poff) HIPCHK(ctx, hipMemcpyAsync(d_block, h_in, poff, hipMemcpyHostToDevice, s));
     auto dev = [&](size_t off) -> const char* {                // the device address of the item staged at arena offset `off`
         for(size_t k = 0; k < items.size(); k++) if(items[k].off == off) return dev_of[k];
         return base + off;                                     // (nothing staged there: an address nobody reads)
@@ -1016,19 +1004,19 @@ int navhip_state_pass_resident(navhip_ctx *ctx, const navhip_state_pass_in *in, 
         memset(&SR, 0, sizeof(SR));
         SR.n = (int)ns; SR.units = (const int32_t*)dev(o_units);
         if(turn) {
-            SKCHK(ctx, hipMemsetAsync(base + e_er, 0, n * 16, s)); SKCHK(ctx, hipMemsetAsync(base + e_td, 0, n * 16, s));
+            HIPCHK(ctx, hipMemsetAsync(base + e_er, 0, n * 16, s)); HIPCHK(ctx, hipMemsetAsync(base + e_td, 0, n * 16, s));
             SR.er = (const float*)a_er; SR.td = (const float*)a_td; SR.d_er = (float*)(base + e_er); SR.d_td = (float*)(base + e_td);
             a_er = base + e_er; a_td = base + e_td;
         }
         if(rg) {
-            SKCHK(ctx, hipMemsetAsync(base + e_rt, 0xfe, n * 4, s)); SKCHK(ctx, hipMemsetAsync(base + e_row, 0, n * 4, s));
+            HIPCHK(ctx, hipMemsetAsync(base + e_rt, 0xfe, n * 4, s)); HIPCHK(ctx, hipMemsetAsync(base + e_row, 0, n * 4, s));
             SR.rt = (const int32_t*)a_rt; SR.rr = (const float*)a_rr; SR.rp = (const float*)a_rp; SR.row = (const int32_t*)a_row;
             SR.d_rt = (int32_t*)(base + e_rt); SR.d_rr = (float*)(base + e_rr); SR.d_rp = (float*)(base + e_rp); SR.d_row = (int32_t*)(base + e_row);
             a_rt = base + e_rt; a_rr = base + e_rr; a_rp = base + e_rp; a_row = base + e_row;
         }
         if(su) {
-            SKCHK(ctx, hipMemsetAsync(base + e_stgt, 0xfe, n * 4, s)); SKCHK(ctx, hipMemsetAsync(base + e_sq, 0, n, s));
-            SKCHK(ctx, hipMemsetAsync(res + r_sd, 0, n * 8, s));
+            HIPCHK(ctx, hipMemsetAsync(base + e_stgt, 0xfe, n * 4, s)); HIPCHK(ctx, hipMemsetAsync(base + e_sq, 0, n, s));
+            HIPCHK(ctx, hipMemsetAsync(res + r_sd, 0, n * 8, s));
             SR.stgt = (const int32_t*)a_stgt; SR.sq = (const uint8_t*)a_sq; SR.stp = (const float*)a_stp; SR.snp = (const float*)a_snp;
             SR.sd = (const float*)a_sd;
             SR.d_stgt = (int32_t*)(base + e_stgt); SR.d_sq = (uint8_t*)(base + e_sq); SR.d_stp = (float*)(base + e_stp);
@@ -1037,7 +1025,7 @@ int navhip_state_pass_resident(navhip_ctx *ctx, const navhip_state_pass_in *in, 
         }
         if(ns) {
             hipLaunchKernelGGL(k_sparse_rows, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, s, SR);
-            SKCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, hipGetLastError());
         }
     }
     // ---- the three passes on the resident snapshot
@@ -1074,21 +1062,21 @@ int navhip_state_pass_resident(navhip_ctx *ctx, const navhip_state_pass_in *in, 
         hipLaunchKernelGGL(k_gate_host_rows, dim3((e - b + 255) / 256), dim3(256), 0, s, b, e, (const uint8_t*)(res + r_gate),
                            d.state, aux ? (const int32_t*)dev(o_wt) : (const int32_t*)nullptr,
                            (uint8_t*)(res + r_st), (uint8_t*)(res + r_fl), aux ? (int32_t*)(res + r_tk) : (int32_t*)nullptr);
-        SKCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipGetLastError());
         if(su && sp && ns) {
             hipLaunchKernelGGL(k_sparse_gather2, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, s, (int)ns, (const int32_t*)dev(o_units),
                                (const float*)(res + r_sd), (float*)(res + r_sdk));
-            SKCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, hipGetLastError());
         }
         // results: the pageable destinations' rows are gathered into one block on the device and cross the bus once
         char *d_oblock = res + R.total;
         for(auto &o : outs) {
-            if(o.pinned) SKCHK(ctx, hipMemcpyAsync((char*)o.dst + o.lo * o.row, res + o.dev_off + o.lo * o.row, o.cnt * o.row, hipMemcpyDeviceToHost, s));
-            else         SKCHK(ctx, hipMemcpyAsync(d_oblock + o.h_off, res + o.dev_off + o.lo * o.row, o.cnt * o.row, hipMemcpyDeviceToDevice, s));
+            if(o.pinned) HIPCHK(ctx, hipMemcpyAsync((char*)o.dst + o.lo * o.row, res + o.dev_off + o.lo * o.row, o.cnt * o.row, hipMemcpyDeviceToHost, s));
+            else         HIPCHK(ctx, hipMemcpyAsync(d_oblock + o.h_off, res + o.dev_off + o.lo * o.row, o.cnt * o.row, hipMemcpyDeviceToDevice, s));
         }
-        if(pack_out) SKCHK(ctx, hipMemcpyAsync(h_out, d_oblock, pack_out, hipMemcpyDeviceToHost, s));
+        if(pack_out) HIPCHK(ctx, hipMemcpyAsync(h_out, d_oblock, pack_out, hipMemcpyDeviceToHost, s));
     }
-    SKCHK(ctx, hipStreamSynchronize(s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
     if(e > b)
         for(auto &o : outs) if(!o.pinned) memcpy((char*)o.dst + o.lo * o.row, h_out + o.h_off, o.cnt * o.row);
     return NAVHIP_OK;
@@ -1116,7 +1104,7 @@ static int sk_settled_count(navhip_ctx *ctx, const navhip_world *w, int nq, cons
     // the spatial index over the snapshot, the circle queries and the count, all on the device: the ids of the queries
     // (the reference's visiting order, capped) never leave HBM -- only the uids go up and the counts come back
     const size_t n = (size_t)w->n_ents;
-    SKCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     navhip_world d; navhip_step_out so;
     const bool resident = use_resident && nh_async_resident(ctx, &d, &so) && d.n_ents == w->n_ents && d.pos_xz && d.radius && d.flags && d.state;
@@ -1129,20 +1117,20 @@ static int sk_settled_count(navhip_ctx *ctx, const navhip_world *w, int nq, cons
                  o_st = A.take(resident ? 0 : n), o_uid = A.take((size_t)nq * 4), o_q = A.take((size_t)nq * 8),
                  o_cnt = A.take((size_t)nq * 4), o_ids = A.take((size_t)nq * SK_QUERY_MAX * 4), o_out = A.take((size_t)nq * 4);
     char *base;
-    int rc = navhip_stage_reserve(ctx, SK_SLOT, A.total, (void**)&base);
+    int rc = nh_stage_reserve(ctx, NH_STAGE_STATE_ARENA, A.total, (void**)&base);
     if(rc) return rc;
     if(!resident) {
         // (a snapshot the velocity pass left on the device is read in place: the tick's tables are the same)
-        SKCHK(ctx, hipMemcpyAsync(base + o_pos, w->pos_xz, n * 8, hipMemcpyHostToDevice, s));
-        SKCHK(ctx, hipMemcpyAsync(base + o_rad, w->radius, n * 4, hipMemcpyHostToDevice, s));
-        SKCHK(ctx, hipMemcpyAsync(base + o_fl, w->flags, n * 4, hipMemcpyHostToDevice, s));
-        SKCHK(ctx, hipMemcpyAsync(base + o_st, w->state, n, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_pos, w->pos_xz, n * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_rad, w->radius, n * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_fl, w->flags, n * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_st, w->state, n, hipMemcpyHostToDevice, s));
         d = *w;
         d.pos_xz = (const float*)(base + o_pos); d.radius = (const float*)(base + o_rad);
         d.flags = (const uint32_t*)(base + o_fl); d.state = (const uint8_t*)(base + o_st);
     }
     d.grid_xmin = w->grid_xmin; d.grid_xmax = w->grid_xmax; d.grid_zmin = w->grid_zmin; d.grid_zmax = w->grid_zmax;
-    SKCHK(ctx, hipMemcpyAsync(base + o_uid, uids, (size_t)nq * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(base + o_uid, uids, (size_t)nq * 4, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_gather_query, dim3((nq + 255) / 256), dim3(256), 0, s, nq, (const int32_t*)(base + o_uid), d.pos_xz, (float*)(base + o_q));
     rc = nh_spatial_query_dev(ctx, &d, (const float*)(base + o_q), nq, SK_QUERY_R, SK_QUERY_MAX, (int32_t*)(base + o_cnt),
                               (uint32_t*)(base + o_ids), s);
@@ -1150,9 +1138,9 @@ static int sk_settled_count(navhip_ctx *ctx, const navhip_world *w, int nq, cons
     hipLaunchKernelGGL(k_settled_count, dim3((nq + 15) / 16), dim3(256), 0, s, nq, (const int32_t*)(base + o_uid),
                        d.pos_xz, d.radius, d.flags, d.state, (const int32_t*)(base + o_cnt), (const uint32_t*)(base + o_ids),
                        (int32_t*)(base + o_out));
-    SKCHK(ctx, hipGetLastError());
-    SKCHK(ctx, hipMemcpyAsync(out_counts, base + o_out, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-    SKCHK(ctx, hipStreamSynchronize(s));
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(out_counts, base + o_out, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
     return NAVHIP_OK;
 }
 
@@ -1166,12 +1154,12 @@ int navhip_arrival_settle_dev(navhip_ctx *ctx, const navhip_world *w, const navh
     || !in->progress_anchored || !in->stuck || !out->settle || !out->substate || !out->progress_anchor_xz
     || !out->progress_anchored || !out->stuck)
         return NAVHIP_ERR_INVALID;
-    SKCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
     nh_step_params P;
     sk_map_view(ctx, w, &P);
     hipLaunchKernelGGL(k_arrival_settle, dim3((in->nq + 15) / 16), dim3(256), 0, stream ? (hipStream_t)stream : ctx->stream,
                        P, w->vel_xz, w->radius, *in, *out);
-    SKCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipGetLastError());
     return NAVHIP_OK;
 }
 
@@ -1217,7 +1205,7 @@ static int sk_arrival_settle(navhip_ctx *ctx, const navhip_world *w, const navhi
     if((n_slots > 0 && (!in->slots_xz || !in->slot_ring)) || (n_keys > 0 && !in->region_keys)) return NAVHIP_ERR_INVALID;
     for(size_t q = 0; q < nq; q++)
         if(in->uid[q] < 0 || in->uid[q] >= w->n_ents || in->zone[q] < 0 || in->zone[q] >= in->n_zones) return NAVHIP_ERR_INVALID;
-    SKCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     sk_arena A;
     const size_t o_vel = A.take(resident ? 0 : n * 8), o_rad = A.take(resident ? 0 : n * 4);
@@ -1232,7 +1220,7 @@ static int sk_arrival_settle(navhip_ctx *ctx, const navhip_world *w, const navhi
                  r_set = A.take(nq), r_sub = A.take(nq), r_anc = A.take(nq * 8), r_and = A.take(nq), r_stk = A.take(nq * 4),
                  r_ns = A.take(count_here ? nq * 4 : 0);
     char *base;
-    int rc = navhip_stage_reserve(ctx, SK_SLOT, A.total, (void**)&base);
+    int rc = nh_stage_reserve(ctx, NH_STAGE_STATE_ARENA, A.total, (void**)&base);
     if(rc) return rc;
     struct up { size_t off; const void *src; size_t bytes; };
     const up ups[] = {{o_z, in->zones, nz * sizeof(navhip_arrival_zone)}, {o_sl, in->slots_xz, n_slots * 8}, {o_ring, in->slot_ring, n_slots * 4},
@@ -1248,14 +1236,14 @@ static int sk_arrival_settle(navhip_ctx *ctx, const navhip_world *w, const navhi
     char *h_in = nullptr, *h_out = nullptr;
     const bool packed = nh_async_slabs(ctx, in_end - o_z, A.total - r_set, &h_in, &h_out) == NAVHIP_OK;
     if(!resident) {
-        SKCHK(ctx, hipMemcpyAsync(base + o_vel, w->vel_xz, n * 8, hipMemcpyHostToDevice, s));
-        SKCHK(ctx, hipMemcpyAsync(base + o_rad, w->radius, n * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_vel, w->vel_xz, n * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_rad, w->radius, n * 4, hipMemcpyHostToDevice, s));
     }
     if(packed) {
         for(const up &u : ups) if(u.bytes) memcpy(h_in + (u.off - o_z), u.src, u.bytes);
-        SKCHK(ctx, hipMemcpyAsync(base + o_z, h_in, in_end - o_z, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(base + o_z, h_in, in_end - o_z, hipMemcpyHostToDevice, s));
     }else
-        for(const up &u : ups) if(u.bytes) SKCHK(ctx, hipMemcpyAsync(base + u.off, u.src, u.bytes, hipMemcpyHostToDevice, s));
+        for(const up &u : ups) if(u.bytes) HIPCHK(ctx, hipMemcpyAsync(base + u.off, u.src, u.bytes, hipMemcpyHostToDevice, s));
     navhip_world d = *w;
     // (the snapshot the velocity half left on the device is read in place: movestate.velocity and the radii are the tick's)
     d.vel_xz = resident ? rw.vel_xz : (const float*)(base + o_vel); d.radius = resident ? rw.radius : (const float*)(base + o_rad);
@@ -1269,7 +1257,7 @@ static int sk_arrival_settle(navhip_ctx *ctx, const navhip_world *w, const navhi
         hipLaunchKernelGGL(k_settled_count, dim3((in->nq + 15) / 16), dim3(256), 0, s, in->nq, (const int32_t*)(base + o_uid),
                            rw.pos_xz, rw.radius, rw.flags, rw.state, (const int32_t*)(base + o_cnt), (const uint32_t*)(base + o_ids),
                            (int32_t*)(base + r_ns));
-        SKCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipGetLastError());
     }
     navhip_settle_in di = *in;
     di.zones = (const navhip_arrival_zone*)(base + o_z); di.slots_xz = (const float*)(base + o_sl);
@@ -1284,9 +1272,9 @@ static int sk_arrival_settle(navhip_ctx *ctx, const navhip_world *w, const navhi
                               (uint8_t*)(base + r_and), (int32_t*)(base + r_stk), nullptr};
     rc = navhip_arrival_settle_dev(ctx, &d, &di, &dout, s);
     if(rc) return rc;
-    if(packed) SKCHK(ctx, hipMemcpyAsync(h_out, base + r_set, A.total - r_set, hipMemcpyDeviceToHost, s));
-    else for(const down &o : downs) if(o.bytes) SKCHK(ctx, hipMemcpyAsync(o.dst, base + o.off, o.bytes, hipMemcpyDeviceToHost, s));
-    SKCHK(ctx, hipStreamSynchronize(s));
+    if(packed) HIPCHK(ctx, hipMemcpyAsync(h_out, base + r_set, A.total - r_set, hipMemcpyDeviceToHost, s));
+    else for(const down &o : downs) if(o.bytes) HIPCHK(ctx, hipMemcpyAsync(o.dst, base + o.off, o.bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
     if(packed) for(const down &o : downs) if(o.bytes) memcpy(o.dst, h_out + (o.off - r_set), o.bytes);
     return NAVHIP_OK;
 }

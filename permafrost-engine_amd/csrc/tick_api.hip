@@ -19,14 +19,6 @@
 #include <ctime>
 #include <new>
 
-#define HIPCHK(ctx, expr)                                                                   \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if(_e != hipSuccess) {                                                              \
-            (ctx)->last_error = std::string(#expr) + ": " + hipGetErrorString(_e);          \
-            return NAVHIP_ERR_DEVICE;                                                       \
-        }                                                                                   \
-    } while(0)
 #define RCCHK(expr) do { int _rc = (expr); if(_rc) return _rc; } while(0)
 
 struct navhip_tick {

@@ -341,3 +341,32 @@ def test_makefile_builds_what_build_py_builds():
     flags = re.search(r"^FLAGS\s*=\s*(.*)$", mk, re.M).group(1).split()
     want = [f for f in nb.FLAGS if not f.startswith("-I")]
     assert [f for f in flags if not f.startswith("-I")] == want
+
+
+def test_staging_tables_cover_every_array_and_slots_are_named():
+    """csrc/navhip_internal.h keeps ONE list of the arrays of navhip_world (nh_world_rows) and one of navhip_step_out
+    (nh_out_rows) for every host-buffer path: each pointer member declared in include/navhip.h has exactly one row, and
+    nothing in csrc/ indexes the context's staging slots by a bare number."""
+    hdr = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    csrc = os.path.join(ROOT, "permafrost-engine_amd", "csrc")
+    internal = open(os.path.join(csrc, "navhip_internal.h")).read()
+    for struct, macro in (("navhip_world", "NH_WROW"), ("navhip_step_out", "NH_OROW")):
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), hdr, re.S).group(1)
+        members = re.findall(r"\*\s*(\w+)\s*;", body)
+        assert len(members) == len(set(members)) and members
+        rows = re.findall(r"\b%s\((\w+)," % macro, internal)
+        rows = [r for r in rows if r != "member"]                      # (the macro's own definition)
+        assert sorted(rows) == sorted(members), (struct, sorted(set(members) ^ set(rows)))
+    slots = re.search(r"enum nh_stage_slot \{(.*?)\};", internal, re.S).group(1)
+    slots = re.findall(r"\b(NH_STAGE_\w+)", re.sub(r"//[^\n]*", "", slots))
+    assert len(slots) == len(set(slots)) and slots[-1] == "NH_STAGE_COUNT"
+    row_slots = re.findall(r"\bNH_[WO]ROW\([^)]*?(NH_STAGE_\w+)", internal)
+    assert len(row_slots) == len(set(row_slots)) == 27 + 5, "two arrays share a staging slot"
+    assert not [s for s in row_slots if s.startswith("NH_STAGE_CALL")], "an array that outlives its call sits in call-local scratch"
+    bare = re.compile(r"stage\[[0-9]|stage_reserve\([^,]*, *[0-9]|_SLOT +[0-9]")
+    hits = []
+    for f in sorted(os.listdir(csrc)):
+        for i, line in enumerate(open(os.path.join(csrc, f), errors="replace"), 1):
+            if bare.search(line):
+                hits.append("%s:%d: %s" % (f, i, line.strip()))
+    assert not hits, "staging slots indexed by number:\n" + "\n".join(hits)
