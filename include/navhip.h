@@ -95,9 +95,14 @@ enum {
 typedef struct navhip_field_req {
     uint8_t  layer;          /* enum nav_layer                                         */
     uint8_t  type;           /* NAVHIP_TARGET_TILE / NAVHIP_TARGET_PORTAL              */
-    uint8_t  faction_id;     /* NAVHIP_FACTION_ID_NONE, or the pathing faction         */
+    uint8_t  faction_id;     /* NAVHIP_FACTION_ID_NONE, or the pathing faction (an "attacking
+                                path": tiles blocked by enemies only are passable, field.c:179).
+                                Either way the bit-parallel wave kernel builds the field when
+                                every passable cell of the chunk costs 1 (navhip_set_field_kernel) */
     uint8_t  flags;          /* NAVHIP_REQ_*                                           */
-    uint16_t enemies;        /* enemies_for_faction(faction_id) bitmask, field.c:166   */
+    uint16_t enemies;        /* enemies_for_faction(faction_id) bitmask, field.c:166: bit f set =
+                                faction f does not block.  Read with a faction only; without a
+                                resident factions plane no blocker stops such a request        */
     uint16_t chunk_r, chunk_c;
     uint8_t  tile_r, tile_c;                       /* TARGET_TILE: target.tile;
                                                       NEAREST_PATHABLE: the start tile  */
@@ -147,7 +152,11 @@ int  navhip_upload_plane(navhip_ctx *ctx, int layer, int plane, const void *host
 /* Upload one chunk of one plane (dirty-chunk update after N_Update, nav.c:2119). */
 int  navhip_upload_chunk(navhip_ctx *ctx, int layer, int plane, int chunk_r, int chunk_c,
                          const void *host, size_t bytes);
-/* Device pointer of a resident plane (NULL when never uploaded); for zero-copy producers. */
+/* Device pointer of a resident plane (NULL when never uploaded); for zero-copy producers.  The library keeps row
+ * masks derived from the cost_base, blockers AND factions planes; it rebuilds them after navhip_upload_plane /
+ * navhip_upload_chunk and after navhip_blockers_circles[_dev].  Whoever writes one of these three planes through this
+ * pointer re-uploads nothing but has to name the chunks it wrote: one navhip_upload_chunk of the chunk (any of the three
+ * planes, e.g. its own read-back) before the next build -- the factions plane is under the same rule as the other two. */
 void *navhip_plane_dev(navhip_ctx *ctx, int layer, int plane);
 
 /* Read a resident plane back (tests; host mirrors after device-side blocker updates). */
@@ -278,9 +287,15 @@ uint64_t navhip_flow_field_id(const navhip_field_req *req);
 enum { NAVHIP_FFID_ENEMIES = 2, NAVHIP_FFID_ENTITY = 4, NAVHIP_FFID_ZONE = 5 };
 uint64_t navhip_region_field_id(int kind, int layer, int chunk_r, int chunk_c, uint32_t a, int b, int c);
 
-/* kernel selection override for tests/bench: 0 = auto (bit-parallel BFS when every passable
- * cell of the chunk has cost 1, generic relaxation otherwise), 1 = force generic. */
+/* kernel selection override for tests/bench: 0 = auto, 1 = force generic.  Auto: the bit-parallel BFS (one wave per
+ * request) builds TILE / PORTAL requests -- with or without a faction, in place or not -- of chunks whose passable cells
+ * all cost 1; the generic relaxation (one workgroup per request) builds the requests of chunks with other costs and the
+ * two repair builds (NAVHIP_TARGET_NEAREST_PATHABLE, NAVHIP_REQ_ISLAND_NEAREST).  Both are bit-exact. */
 int  navhip_set_field_kernel(navhip_ctx *ctx, int mode);
+/* How the context's last chunk-field build (navhip_build_fields[_dev], navhip_pool_build) split its requests (waits for
+ * that build; its stream must still exist): out[0] = requests the BFS kernel kept (the ones a flag made it skip
+ * included), out[1] = requests the generic kernel built.  NAVHIP_ERR_INVALID before the first build. */
+int  navhip_last_fields_split(navhip_ctx *ctx, int32_t out[2]);
 
 /* ---- resident flow-field pool (SURVEY.md §8b "Ownership" / the reference's field cache) ------- */
 

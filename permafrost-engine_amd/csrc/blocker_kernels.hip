@@ -21,7 +21,8 @@
 //                      scratch arrays are applied with a wave prefix-popcount in row-major order.
 //                      Refcounts are updated with 32-bit atomics on the containing word.
 // k_refresh_touched    one wave per chunk: rebuild the passability row masks of chunks whose
-//                      blockers were touched, flag the chunk `changed` when any mask differs.
+//                      blockers were touched, flag the chunk `changed` when any mask differs; and
+//                      the facmask rows of the factions whose counters were touched there.
 // k_local_islands      one wave per chunk: bit-parallel flood fill per component, labels kept
 //                      bit-sliced, expanded to u16 and stored coalesced through LDS.
 #include "navhip_internal.h"
@@ -33,6 +34,7 @@ struct nh_blk_params {
     uint16_t *blockers[NAVHIP_NAV_LAYER_MAX];
     uint8_t  *factions[NAVHIP_NAV_LAYER_MAX];
     uint8_t  *touched[NAVHIP_NAV_LAYER_MAX];
+    uint32_t *fac_touched[NAVHIP_NAV_LAYER_MAX];
 };
 
 #define BLK_EPS 0.0009765625f      /* collision.c:64 EPSILON 1/1024 */
@@ -196,8 +198,10 @@ __global__ __launch_bounds__(256) void k_blockers_circles(nh_blk_params P, const
             uint16_t *bl = P.blockers[layer];
             if(!bl) continue;                                           // layer not resident
             uint8_t *fa = P.factions[layer];
+            const bool with_faction = fa && C.faction_id >= 0 && C.faction_id < NAVHIP_MAX_FACTIONS;
             for(int k = 0; k <= sidx; k++) {
                 uint64_t m = sets[k];
+                int noted = -1;             // the chunk whose fac_touched bit this lane set last (a row spans two at most)
                 while(m) {
                     const int b = __builtin_ctzll(m);
                     m &= m - 1;
@@ -205,9 +209,11 @@ __global__ __launch_bounds__(256) void k_blockers_circles(nh_blk_params P, const
                     const int chunk = (abs_r >> 6) * P.w + (ac >> 6);
                     const size_t cell = ((size_t)chunk << 12) + (abs_r & 63) * 64 + (ac & 63);
                     add_u16(bl + cell, C.delta);
-                    if(fa && C.faction_id >= 0 && C.faction_id < NAVHIP_MAX_FACTIONS)
+                    if(with_faction) {
                         add_u8(fa + ((size_t)chunk * NAVHIP_MAX_FACTIONS << 12)
                                   + ((size_t)C.faction_id << 12) + (abs_r & 63) * 64 + (ac & 63), C.delta);
+                        if(chunk != noted) { atomicOr(&P.fac_touched[layer][chunk], 1u << C.faction_id); noted = chunk; }
+                    }
                     P.touched[layer][chunk] = 1;
                 }
             }
@@ -216,12 +222,20 @@ __global__ __launch_bounds__(256) void k_blockers_circles(nh_blk_params P, const
 }
 
 // ---------------------------------------------------------------------------------------------
+// `changed` keeps its meaning: the passability WITHOUT a faction (passmask) of the chunk differs.  The faction rows are
+// refreshed for every touched chunk whether it differs or not -- a unit of another faction that steps on tiles which
+// are blocked already changes what an attacking path may cross while passmask stays what it is -- but only the rows of
+// the factions the circle kernel touched there (fac_touched).
 __global__ __launch_bounds__(256) void k_refresh_touched(const uint8_t *cost, const uint16_t *blockers,
                                                          uint64_t *passmask, uint64_t *probemask, uint8_t *unit_cost,
-                                                         uint8_t *touched, uint8_t *changed, int nchunks)
+                                                         uint8_t *touched, uint8_t *changed,
+                                                         const uint8_t *factions, uint64_t *facmask, uint16_t *facany,
+                                                         uint32_t *fac_touched, int nchunks)
 {
     const int chunk = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
     if(chunk >= nchunks || !touched[chunk]) return;
+    uint32_t ft = factions ? __builtin_amdgcn_readfirstlane((int)fac_touched[chunk]) : 0u;
+    uint32_t fany = ft ? facany[chunk] : 0u;
     const uint8_t  *cb = cost + ((size_t)chunk << 12);
     const uint16_t *bl = blockers + ((size_t)chunk << 12);
     uint64_t mine = 0, blocked = 0;
@@ -236,10 +250,19 @@ __global__ __launch_bounds__(256) void k_refresh_touched(const uint8_t *cost, co
     passmask[(size_t)chunk * 64 + lane] = mine;
     probemask[((size_t)chunk * 64 + lane) * 2 + 1] = blocked;       // (the cost half does not change here)
     const bool any_nonunit = __any(nonunit), any_diff = __any(differs);
+    const bool refaction = ft != 0;
+    while(ft) {
+        const int f = __builtin_ctz(ft);
+        ft &= ft - 1;
+        const uint64_t m = nz_row_mask(factions + ((size_t)chunk * NAVHIP_MAX_FACTIONS << 12) + ((size_t)f << 12) + lane * 64);
+        facmask[((size_t)chunk * NAVHIP_MAX_FACTIONS + f) * 64 + lane] = m;
+        fany = __ballot(m != 0) ? (fany | (1u << f)) : (fany & ~(1u << f));
+    }
     if(lane == 0) {
         unit_cost[chunk] = any_nonunit ? 0 : 1;
         if(any_diff) changed[chunk] = 1;
         touched[chunk] = 0;
+        if(refaction) { facany[chunk] = (uint16_t)fany; fac_touched[chunk] = 0; }
     }
 }
 
@@ -312,6 +335,7 @@ void nh_launch_blockers_circles(navhip_ctx *ctx, const navhip_circle *d_circles,
         P.blockers[l] = ctx->layers[l].blockers;
         P.factions[l] = ctx->layers[l].factions;
         P.touched[l]  = ctx->layers[l].touched;
+        P.fac_touched[l] = ctx->layers[l].fac_touched;
     }
     if(n > 0)
         hipLaunchKernelGGL(k_blockers_circles, dim3((n + 3) / 4), dim3(256), 0, s, P, d_circles, n);
@@ -320,7 +344,8 @@ void nh_launch_blockers_circles(navhip_ctx *ctx, const navhip_circle *d_circles,
         navhip_layer &L = ctx->layers[l];
         if(!L.blockers || !L.cost) continue;
         hipLaunchKernelGGL(k_refresh_touched, dim3((ctx->nchunks + 3) / 4), dim3(256), 0, s, L.cost,
-                           L.blockers, L.passmask, L.probemask, L.unit_cost, L.touched, L.changed, ctx->nchunks);
+                           L.blockers, L.passmask, L.probemask, L.unit_cost, L.touched, L.changed,
+                           L.factions, L.facmask, L.facany, L.fac_touched, ctx->nchunks);
         if(L.local_islands)
             hipLaunchKernelGGL(k_local_islands, dim3((ctx->nchunks + 3) / 4), dim3(256), 0, s,
                                L.passmask, L.local_islands, L.changed, ctx->nchunks);

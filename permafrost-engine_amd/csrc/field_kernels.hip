@@ -13,7 +13,10 @@
 //                   the chunk has cost 1 (the only value the reference's cost writers produce
 //                   besides 0xff: nav.c:339-342,416), so Dijkstra degenerates to a
 //                   level-synchronous BFS.  A row of the field is one 64-bit mask held in a
-//                   lane; a BFS level is ~20 VALU ops for the whole 64x64 field: W/E
+//                   lane (passmask; for a request with a faction -- an "attacking path",
+//                   field_tile_passable_no_enemies field.c:179 -- derived from the probemask
+//                   and facmask rows: the faction only changes WHICH cells are passable, every
+//                   one of them still costs 1); a BFS level is ~20 VALU ops for the whole 64x64 field: W/E
 //                   neighbours are 64-bit shifts, N/S neighbours are DPP wave shifts, the
 //                   "frontier empty" test is one wave ballot.  Distances are kept bit-sliced
 //                   (plane k of lane r = bit k of the distance of every cell of row r) and the
@@ -22,7 +25,8 @@
 //
 //  k_field_generic  one 256-thread workgroup per request, u32 integration tile in LDS,
 //                   chaotic min-plus relaxation to the fixpoint (== Dijkstra distances, integer
-//                   exact) for arbitrary u8 costs and for faction ("attacking") passability.
+//                   exact) for arbitrary u8 costs and for the two repair builds, with or without
+//                   a faction.
 //
 // Integer/bit work only: no MFMA.  Compile with -ffp-contract=off (only matters for the
 // int->float conversion of the optional integration output, which is exact anyway).
@@ -34,7 +38,6 @@ __device__ __forceinline__ bool req_uses_bfs(const nh_map_view &map, const navhi
                                              int force_generic)
 {
     if(force_generic) return false;
-    if(rq.faction_id != NAVHIP_FACTION_ID_NONE) return false;
     if(rq.type == NAVHIP_TARGET_NEAREST_PATHABLE || (rq.flags & NAVHIP_REQ_ISLAND_NEAREST)) return false;
     const nh_layer_view &L = map.layers[rq.layer];
     return L.unit_cost[(int)rq.chunk_r * map.w + rq.chunk_c] != 0;
@@ -119,6 +122,7 @@ __device__ __forceinline__ uint32_t portal_fix_dir(const navhip_field_req &rq)
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_derive(const uint8_t *cost, const uint16_t *blockers,
                                                 uint64_t *passmask, uint64_t *probemask, uint8_t *unit_cost,
+                                                const uint8_t *factions, uint64_t *facmask, uint16_t *facany,
                                                 const uint32_t *chunk_list, int n)
 {
     int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
@@ -142,6 +146,17 @@ __global__ __launch_bounds__(256) void k_derive(const uint8_t *cost, const uint1
     probemask[((size_t)chunk * 64 + lane) * 2 + 1] = blocked;
     bool any_nonunit = __any(nonunit);
     if(lane == 0) unit_cost[chunk] = any_nonunit ? 0 : 1;
+    if(factions) {
+        // faction rows: lane = row, 64 counters -> 64 bits (nz_row_mask)
+        const uint8_t *fa = factions + ((size_t)chunk * NAVHIP_MAX_FACTIONS << 12) + lane * 64;
+        uint32_t any = 0;
+        for(int f = 0; f < NAVHIP_MAX_FACTIONS; f++) {
+            const uint64_t m = nz_row_mask(fa + ((size_t)f << 12));
+            facmask[((size_t)chunk * NAVHIP_MAX_FACTIONS + f) * 64 + lane] = m;
+            if(__ballot(m != 0)) any |= 1u << f;
+        }
+        if(lane == 0) facany[chunk] = (uint16_t)any;
+    }
 }
 
 void nh_launch_derive(navhip_ctx *ctx, int layer, const uint32_t *d_chunk_list, int n, hipStream_t s)
@@ -149,12 +164,33 @@ void nh_launch_derive(navhip_ctx *ctx, int layer, const uint32_t *d_chunk_list, 
     navhip_layer &L = ctx->layers[layer];
     int blocks = (n + 3) / 4;
     hipLaunchKernelGGL(k_derive, dim3(blocks), dim3(256), 0, s, L.cost, L.blockers, L.passmask, L.probemask,
-                       L.unit_cost, d_chunk_list, n);
+                       L.unit_cost, L.factions, L.facmask, L.facany, d_chunk_list, n);
 }
 
 // ---------------------------------------------------------------------------------------------
 // k_field_bfs : one wave per request, lane = row
 // ---------------------------------------------------------------------------------------------
+// Row `lane` of the passability of a request WITH a faction (field_tile_passable_no_enemies, field.c:179-201): a
+// pathable tile is passable unless it is blocked AND a faction that is not among the request's enemies stands on it.
+// `path` / `blocked` are the two probemask words of the row; the factions that occur in the chunk (facany) and are no
+// enemies are walked with scalar control flow, one facmask row each.  No factions plane resident: nobody can be told
+// from an enemy, blockers do not count (what k_field_generic does when L.factions == nullptr).
+__device__ __forceinline__ uint64_t faction_pass_row(const nh_layer_view &L, int chunk, int lane, uint32_t enemies)
+{
+    const uint64_t *pm = L.probemask + ((size_t)chunk * 64 + lane) * 2;
+    const uint64_t path = pm[0], blocked = pm[1];
+    if(!L.facmask) return path;
+    uint64_t friends = 0;
+    uint32_t fs = __builtin_amdgcn_readfirstlane((int)(L.facany[chunk] & ~enemies & ((1u << NAVHIP_MAX_FACTIONS) - 1u)));
+    const uint64_t *fm = L.facmask + (size_t)chunk * NAVHIP_MAX_FACTIONS * 64 + lane;
+    while(fs) {
+        const int f = __builtin_ctz(fs);
+        fs &= fs - 1;
+        friends |= fm[f * 64];
+    }
+    return path & ~(blocked & friends);
+}
+
 #define NH_MAXP 12   /* distance bit-planes: unit-cost distances are < 4096 */
 #define BFS_WAVES 4    /* waves (= requests) per workgroup */
 
@@ -175,7 +211,7 @@ __global__ __launch_bounds__(BFS_WAVES * 64) void k_field_bfs(nh_map_view map, c
 
     navhip_field_req rq = reqs[wave];
     if(!req_uses_bfs(map, rq, force_generic)) {
-        // not a unit-cost BFS: hand the request to k_field_generic
+        // not a unit-cost BFS (costs other than 1 in the chunk, a repair build): hand the request to k_field_generic
         if(lane == 0) gen_list[2 + atomicAdd(&gen_list[gen_slot], 1)] = wave;
         return;
     }
@@ -183,7 +219,9 @@ __global__ __launch_bounds__(BFS_WAVES * 64) void k_field_bfs(nh_map_view map, c
 
     const nh_layer_view &L = map.layers[rq.layer];
     const int chunk = (int)rq.chunk_r * map.w + rq.chunk_c;
-    const u64x pass = mk(L.passmask[(size_t)chunk * 64 + lane]);
+    // (the branch is wave-uniform; everything behind `pass` is the same for both kinds of request)
+    const u64x pass = mk(rq.faction_id == NAVHIP_FACTION_ID_NONE ? L.passmask[(size_t)chunk * 64 + lane]
+                                                                 : faction_pass_row(L, chunk, lane, rq.enemies));
 
     // ---- initial frontier (field.c:1372) ----------------------------------------------------
     u64x seeds = u64x{0, 0};
@@ -668,8 +706,8 @@ __global__ __launch_bounds__(256) void k_field_generic(nh_map_view map, const na
 }
 
 // ---------------------------------------------------------------------------------------------
-void nh_launch_fields(navhip_ctx *ctx, const navhip_field_req *d_reqs, int n, uint8_t *d_dirs,
-                      float *d_integ, int32_t *d_gen_list, hipStream_t s, const int32_t *d_out_slot)
+int nh_launch_fields(navhip_ctx *ctx, const navhip_field_req *d_reqs, int n, uint8_t *d_dirs,
+                     float *d_integ, int32_t *d_gen_list, hipStream_t s, const int32_t *d_out_slot)
 {
     nh_map_view mv;
     nh_fill_map_view(ctx, &mv);
@@ -686,11 +724,12 @@ void nh_launch_fields(navhip_ctx *ctx, const navhip_field_req *d_reqs, int n, ui
                                d_integ, force_generic, d_gen_list, gen_slot, d_out_slot);
     }
     // The relaxation kernel strides over the requests the BFS kernel declined.  Usually that list is empty
-    // or short (repairs, attacking paths): 512 workgroups that mostly read one counter.  A map with real
+    // or short (repairs): 512 workgroups that mostly read one counter.  A map with real
     // cost gradients sends EVERY request there: eight workgroups per CU (20 KB of LDS each) instead of two.
     bool heavy = force_generic;
     for(int l = 0; l < NAVHIP_NAV_LAYER_MAX; l++) heavy = heavy || (ctx->layers[l].cost && ctx->layers[l].nonunit_costs);
     const int gmax = heavy ? 2048 : 512;
     hipLaunchKernelGGL(k_field_generic, dim3(n < gmax ? n : gmax), dim3(256), 0, s, mv, d_reqs, n, d_dirs,
                        d_integ, force_generic, force_generic ? (int32_t*)nullptr : d_gen_list, gen_slot, d_out_slot);
+    return force_generic ? -1 : gen_slot;
 }

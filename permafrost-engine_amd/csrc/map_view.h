@@ -14,6 +14,8 @@ struct nh_layer_view {
     const uint8_t  *changed;
     const uint16_t *islands;
     const uint64_t *probemask;     // [chunks][64][2] derived row bits: {cost_base != COST_IMPASSABLE, blockers > 0}
+    const uint64_t *facmask;       // [chunks][15][64] derived row bits: factions[f] != 0 (NULL: no factions plane resident)
+    const uint16_t *facany;        // [chunks]         bit f: faction f holds a tile of the chunk
 };
 struct nh_map_view {
     int w, h;

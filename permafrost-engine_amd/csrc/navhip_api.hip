@@ -10,6 +10,8 @@
 //   factions      u8  [chunks][15][64][64]   struct nav_chunk.factions       nav_data.h:141
 //   passmask      u64 [chunks][64]           derived: row bitmasks of field_tile_passable
 //   probemask     u64 [chunks][64][2]        derived: row bitmasks cost_base != 0xff | blockers > 0 (tile probes)
+//   facmask       u64 [chunks][15][64]       derived: row bitmasks factions[f] != 0 (attacking-path fields); with the
+//   facany        u16 [chunks]               derived: factions present in the chunk      factions plane only
 //   unit_cost     u8  [chunks]               derived: BFS kernel eligibility
 #include "navhip_internal.h"
 #include "agent_internal.h"
@@ -110,6 +112,7 @@ void navhip_ctx_destroy(navhip_ctx *ctx)
         hipFree(L.cost); hipFree(L.blockers); hipFree(L.local_islands); hipFree(L.factions);
         hipFree(L.islands);
         hipFree(L.passmask); hipFree(L.probemask); hipFree(L.unit_cost); hipFree(L.touched); hipFree(L.changed);
+        hipFree(L.facmask); hipFree(L.facany); hipFree(L.fac_touched);
         free(L.dirty);
     }
     nh_ctx_each_buf(ctx, [](nh_buf &b) { hipFree(b.p); });
@@ -177,6 +180,24 @@ int navhip_set_field_kernel(navhip_ctx *ctx, int mode)
     return NAVHIP_OK;
 }
 
+int navhip_last_fields_split(navhip_ctx *ctx, int32_t out[2])
+{
+    if(!ctx || !out) return NAVHIP_ERR_INVALID;
+    if(ctx->last_fields.n < 0) {
+        ctx->last_error = "navhip_last_fields_split: no chunk-field build yet";
+        return NAVHIP_ERR_INVALID;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int32_t generic = ctx->last_fields.n;           // (forced: no list, k_field_generic built every request)
+    if(ctx->last_fields.gen_slot >= 0)
+        // the counter the two kernels keep anyway: it stays until the launch after the next one zeroes it
+        HIPCHK(ctx, hipMemcpyAsync(&generic, (const int32_t*)ctx->gen_list.p + ctx->last_fields.gen_slot, sizeof(int32_t),
+                                   hipMemcpyDeviceToHost, ctx->last_fields.stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->last_fields.stream));
+    out[0] = ctx->last_fields.n - generic; out[1] = generic;
+    return NAVHIP_OK;
+}
+
 static int layer_prepare(navhip_ctx *ctx, int layer, int plane)
 {
     navhip_layer &L = ctx->layers[layer];
@@ -198,6 +219,16 @@ static int layer_prepare(navhip_ctx *ctx, int layer, int plane)
         L.dirty = (uint8_t*)calloc(ctx->nchunks, 1);
         if(!L.dirty) return NAVHIP_ERR_NOMEM;
     }
+    if(L.factions && !L.facmask) {
+        // the derived rows of the factions plane (all zero, like the plane itself until its first upload)
+        const size_t rows = (size_t)ctx->nchunks * NAVHIP_MAX_FACTIONS * 64 * sizeof(uint64_t);
+        HIPCHK(ctx, hipMalloc((void**)&L.facmask, rows));
+        HIPCHK(ctx, hipMalloc((void**)&L.facany, (size_t)ctx->nchunks * sizeof(uint16_t)));
+        HIPCHK(ctx, hipMalloc((void**)&L.fac_touched, (size_t)ctx->nchunks * sizeof(uint32_t)));
+        HIPCHK(ctx, hipMemsetAsync(L.facmask, 0, rows, ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(L.facany, 0, (size_t)ctx->nchunks * sizeof(uint16_t), ctx->stream));
+        HIPCHK(ctx, hipMemsetAsync(L.fac_touched, 0, (size_t)ctx->nchunks * sizeof(uint32_t), ctx->stream));
+    }
     return NAVHIP_OK;
 }
 
@@ -217,7 +248,7 @@ int navhip_upload_plane(navhip_ctx *ctx, int layer, int plane, const void *host,
     navhip_layer &L = ctx->layers[layer];
     HIPCHK(ctx, hipMemcpyAsync(*plane_slot(L, plane), host, bytes, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // caller may reuse `host` immediately
-    if(plane == NAVHIP_PLANE_COST_BASE || plane == NAVHIP_PLANE_BLOCKERS) {
+    if(plane == NAVHIP_PLANE_COST_BASE || plane == NAVHIP_PLANE_BLOCKERS || plane == NAVHIP_PLANE_FACTIONS) {
         memset(L.dirty, 1, ctx->nchunks);
         L.any_dirty = true;
     }
@@ -257,7 +288,7 @@ int navhip_upload_chunk(navhip_ctx *ctx, int layer, int plane, int chunk_r, int 
     HIPCHK(ctx, hipMemcpyAsync((char*)*plane_slot(L, plane) + (size_t)chunk * per, host, per,
                                hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if(plane == NAVHIP_PLANE_COST_BASE || plane == NAVHIP_PLANE_BLOCKERS) {
+    if(plane == NAVHIP_PLANE_COST_BASE || plane == NAVHIP_PLANE_BLOCKERS || plane == NAVHIP_PLANE_FACTIONS) {
         L.dirty[chunk] = 1;
         L.any_dirty = true;
     }
@@ -271,7 +302,7 @@ void *navhip_plane_dev(navhip_ctx *ctx, int layer, int plane)
     return *plane_slot(ctx->layers[layer], plane);
 }
 
-// rebuild passmask / probemask / unit_cost of chunks whose cost or blockers changed (after an upload: the
+// rebuild passmask / probemask / unit_cost / facmask of chunks whose cost, blockers or factions changed (after an upload: the
 // device-side blocker updates refresh their chunks themselves).  Whatever it launches has completed when it
 // returns, so consumers on any stream may follow.
 static int refresh_derived(navhip_ctx *ctx, hipStream_t s)
@@ -557,8 +588,9 @@ int nh_validate_field_reqs(navhip_ctx *ctx, const navhip_field_req *reqs, int n)
         }
         const navhip_layer &L = ctx->layers[r.layer];
         if(!L.cost || (r.type == NAVHIP_TARGET_PORTAL && !L.local_islands)
-        || ((r.flags & NAVHIP_REQ_ISLAND_NEAREST) && (!L.local_islands || !L.islands))
-        || (r.faction_id != NAVHIP_FACTION_ID_NONE && !L.factions && L.blockers)) {
+        || ((r.flags & NAVHIP_REQ_ISLAND_NEAREST) && (!L.local_islands || !L.islands))) {
+            // (a faction request on a layer without a factions plane is served: nobody can be told from an enemy, so no
+            // blocker stops it -- both kernels, and the device entry points always did)
             ctx->last_error = "navhip_build_fields: request " + std::to_string(i)
                             + " needs a plane that was never uploaded";
             return NAVHIP_ERR_NOT_UPLOADED;
@@ -577,7 +609,9 @@ static int build_fields_on(navhip_ctx *ctx, const navhip_field_req *dev_reqs, in
     rc = ensure_buf(ctx, ctx->gen_list, ((size_t)n + 2) * sizeof(int32_t));
     if(rc) return rc;
     if(ctx->gen_list.p != old_list) HIPCHK(ctx, hipMemsetAsync(ctx->gen_list.p, 0, 2 * sizeof(int32_t), s));
-    nh_launch_fields(ctx, dev_reqs, n, dev_inout_dirs, dev_out_integ, (int32_t*)ctx->gen_list.p, s, dev_slots);
+    ctx->last_fields.gen_slot = nh_launch_fields(ctx, dev_reqs, n, dev_inout_dirs, dev_out_integ, (int32_t*)ctx->gen_list.p,
+                                                 s, dev_slots);
+    ctx->last_fields.n = n; ctx->last_fields.stream = s;
     HIPCHK(ctx, hipGetLastError());
     ctx->counters.field_calls++; ctx->counters.chunk_fields += (uint64_t)n;
     return NAVHIP_OK;

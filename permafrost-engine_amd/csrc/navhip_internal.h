@@ -160,9 +160,15 @@ struct navhip_layer {
                                // what the agent kernels' tile probes read (16 bytes per tile row instead of
                                // a byte and a 16-bit word per tile in two planes)
                                //                (field_tile_passable, field.c:117)
+    uint64_t *facmask = nullptr;       // [nchunks][15][64] bit c of word (f, r) = factions[f] of cell (r,c) != 0: what a faction
+                               // request of k_field_bfs reads (7.5 KB per chunk instead of 60 KB); allocated with
+                               // the factions plane               (field_tile_passable_no_enemies, field.c:179)
+    uint16_t *facany = nullptr;        // [nchunks]      bit f = faction f holds a tile of the chunk (facmask row f not empty)
+    uint32_t *fac_touched = nullptr;   // [nchunks]      device: bit f = counters of faction f modified since the last refresh
     uint8_t  *unit_cost = nullptr;     // [nchunks]      1 when every cost != 0xff cell has cost 1
     uint8_t  *touched = nullptr;       // [nchunks]      device: blockers modified since the last refresh
-    uint8_t  *changed = nullptr;       // [nchunks]      device: passability changed since navhip_clear_changed
+    uint8_t  *changed = nullptr;       // [nchunks]      device: passability WITHOUT a faction (passmask) changed since
+                               //                navhip_clear_changed; faction counters alone never set it
     uint8_t  *dirty = nullptr;         // host side: [nchunks] derived state stale
     bool      any_dirty = false;
     bool      nonunit_costs = false;   // host side: a cost other than 1 / 0xff was uploaded for this layer
@@ -191,6 +197,9 @@ struct navhip_ctx {
     nh_buf       coh_plan;     // [n_flocks + 1] wave prefix of the cohesion launch
     nh_buf       gen_list;     // [2 + n] requests the BFS kernel left to k_field_generic: 2 counters, ids
     unsigned     gen_launches = 0; // parity selects the counter of a launch
+    // the last chunk-field build (navhip_last_fields_split): its requests, the counter of gen_list it used (-1: every
+    // request went to k_field_generic, no list), the stream it runs on
+    struct { int n = -1, gen_slot = -1; hipStream_t stream = nullptr; } last_fields;
     int          coh_flocks = -1, coh_members = -1, coh_parity = 0;   // layout of coh_plan + which perm buffer is next
     unsigned     coh_unique = 0;   // membership keys of slab steps whose caller gave no static_epoch: never equal
     unsigned     scratch_moves = 0; // step scratch reallocated or its lane grouping reset: either may enqueue on the caller's stream
@@ -238,7 +247,8 @@ static inline void nh_fill_map_view(const navhip_ctx *ctx, nh_map_view *mv)
     for(int l = 0; l < NAVHIP_NAV_LAYER_MAX; l++) {
         const navhip_layer &L = ctx->layers[l];
         mv->layers[l] = nh_layer_view{L.cost, L.blockers, L.local_islands, L.factions,
-                                      L.passmask, L.unit_cost, L.changed, L.islands, L.probemask};
+                                      L.passmask, L.unit_cost, L.changed, L.islands, L.probemask,
+                                      L.facmask, L.facany};
     }
 }
 
@@ -317,7 +327,7 @@ void nh_async_invalidate_static(navhip_ctx *ctx);   // the staging buffers were 
 bool nh_async_resident(navhip_ctx *ctx, navhip_world *w, navhip_step_out *o);   // snapshot + outputs the last completed submit left on the device
 int  nh_async_slabs(navhip_ctx *ctx, size_t in_bytes, size_t out_bytes, char **h_in, char **h_out);
 bool nh_is_pinned(const void *p);
-int  nh_refresh_derived(navhip_ctx *ctx, hipStream_t s);    // the derived row masks (passmask / probemask) of dirty chunks, rebuilt
+int  nh_refresh_derived(navhip_ctx *ctx, hipStream_t s);    // the derived row masks (passmask / probemask / facmask) of dirty chunks, rebuilt
 int  nh_spatial_query_dev(navhip_ctx *ctx, const navhip_world *dev_w, const float *d_query, int nq, float range, int maxout,
                           int32_t *d_counts, uint32_t *d_ids, hipStream_t s);
 const uint8_t *nh_pool_fields(const navhip_ctx *ctx);
@@ -328,7 +338,8 @@ int nh_pool_slots(const navhip_ctx *ctx);
 // launched by navhip_api.hip
 void nh_launch_derive(navhip_ctx *ctx, int layer, const uint32_t *d_chunk_list, int n,
                       hipStream_t s);
-void nh_launch_fields(navhip_ctx *ctx, const navhip_field_req *d_reqs, int n, uint8_t *d_dirs,
+// (returns the counter of d_gen_list that holds the number of requests left to k_field_generic, -1: all of them)
+int  nh_launch_fields(navhip_ctx *ctx, const navhip_field_req *d_reqs, int n, uint8_t *d_dirs,
                       float *d_integ, int32_t *d_gen_list, hipStream_t s,
                       const int32_t *d_out_slot = nullptr);
 

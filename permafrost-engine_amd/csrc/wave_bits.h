@@ -55,3 +55,23 @@ __device__ __forceinline__ u64x bfs_reach(u64x f, u64x open)
     const uint32_t b0 = nh_keep32(e.lo | s.lo), b1 = nh_keep32(e.hi | s.hi);
     return u64x{(a0 | b0) & open.lo, (a1 | b1) & open.hi};
 }
+
+// Row mask of 64 one-byte counters: bit c = row[c] != 0.  The lane that owns the row reads its 64 bytes as four 16-byte
+// words (a wave reads the 4 KB of a faction's tile back to back) and folds every dword to a nibble: the top bit of each
+// non-zero byte, gathered by one multiply (bits 0, 8, 16, 24 -> 21..24; no two partial products share a bit).
+__device__ __forceinline__ uint32_t nz_bytes4(uint32_t w)
+{
+    const uint32_t top = (((w & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w) & 0x80808080u;
+    return (((top >> 7) * 0x00204081u) >> 21) & 0xfu;
+}
+__device__ __forceinline__ uint64_t nz_row_mask(const uint8_t *row)
+{
+    uint64_t m = 0;
+#pragma unroll
+    for(int j = 0; j < 4; j++) {
+        const uint4 q = *(const uint4*)(row + j * 16);
+        const uint32_t n = nz_bytes4(q.x) | (nz_bytes4(q.y) << 4) | (nz_bytes4(q.z) << 8) | (nz_bytes4(q.w) << 12);
+        m |= (uint64_t)n << (16 * j);
+    }
+    return m;
+}

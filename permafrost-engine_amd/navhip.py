@@ -95,6 +95,7 @@ _SIGS = {
     "navhip_flow_field_id": (C.c_uint64, [C.c_void_p]),
     "navhip_region_field_id": (C.c_uint64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_int]),
     "navhip_set_field_kernel": (C.c_int, [C.c_void_p, C.c_int]),
+    "navhip_last_fields_split": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32 * 2)]),
     "navhip_debug_cp_attempts": (C.c_int, [C.c_void_p, C.c_int]),
     "navhip_comm_unique_id": (C.c_int, [C.c_void_p]),
     "navhip_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -254,6 +255,13 @@ class NavContext:
 
     def set_field_kernel(self, mode):
         self._chk(lib().navhip_set_field_kernel(self._h, mode), "navhip_set_field_kernel")
+
+    def last_fields_split(self):
+        """(requests the bit-parallel BFS kernel kept, requests the generic kernel built) of the last chunk-field
+        build of this context; waits for it."""
+        out = (C.c_int32 * 2)()
+        self._chk(lib().navhip_last_fields_split(self._h, C.byref(out)), "navhip_last_fields_split")
+        return int(out[0]), int(out[1])
 
     # -- flow fields ----------------------------------------------------------------------------
     def N_FlowFieldUpdate(self, reqs, inout=None, want_integ=False):

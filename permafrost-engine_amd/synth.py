@@ -115,6 +115,18 @@ def agents(grid, n, k_flocks, seed=7, radius=1.0, max_speed=20.0, hz=20, blocker
     }
 
 
+def faction_circles(grid, n, seed=11, n_factions=3, radius=(3.0, 10.0)):
+    """n unit circles (N_BlockersIncref arguments) on random passable cell centres, factions 0..n_factions-1 at
+    random: the standing armies of an attacking-path world.  Columns x, z, radius (f32), faction_id (i32)."""
+    rng = np.random.RandomState(seed)
+    h, w = grid.shape[0] // 64, grid.shape[1] // 64
+    cells = passable_cells(grid)
+    pick = cells[rng.randint(len(cells), size=n)]
+    pos = cell_centre(w, h, pick[:, 0], pick[:, 1])
+    return {"x": pos[:, 0].copy(), "z": pos[:, 1].copy(), "radius": rng.uniform(radius[0], radius[1], n).astype(np.float32),
+            "faction_id": rng.randint(0, n_factions, n).astype(np.int32)}
+
+
 # ------------------------------------------------------------------------------------------
 # synthetic request streams (what the reference's host-side planner would hand the kernels)
 # ------------------------------------------------------------------------------------------

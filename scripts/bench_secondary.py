@@ -9,6 +9,11 @@
   k_blockers_circles  10 000 circles (configs[4]'s obstacle count) + k_refresh_touched + k_local_islands
   k_local_islands     the relabel of every chunk of the map
   k_los_field         4 096 destination-chunk LOS fields
+  field_attacking     the 16 384 chunk fields of the benchmark map as ATTACKING paths (faction 0 at war with faction 1)
+                      on a map held by 4 000 units of three factions: k_field_bfs (mode 0), k_field_generic (mode 1)
+                      and the same requests without a faction, with navhip_last_fields_split beside each; and the
+                      blocker update of 10 000 circles with a resident factions plane (k_refresh_touched keeps the
+                      faction rows current)
 Prints one JSON object."""
 import json
 import os
@@ -32,10 +37,79 @@ def timed(fn, reps=5):
     return (time.perf_counter() - t0) / reps
 
 
+def field_attacking(torch, dev):
+    """Chunk fields with a faction against the same requests without one, and against the generic kernel."""
+    W, K = 16, 64
+    grid = synth.cost_grid(W, W, seed=1234)
+    dests = synth.destinations(grid, K, seed=42)
+    ctx = navhip.NavContext(W, W)
+    ctx.upload_plane(0, navhip.PLANE_COST_BASE, synth.to_chunks(grid))
+    ctx.upload_plane(0, navhip.PLANE_BLOCKERS, np.zeros((W, W, 64, 64), np.uint16))
+    ctx.upload_plane(0, navhip.PLANE_FACTIONS, np.zeros((W, W, 15, 64, 64), np.uint8))
+    ctx.relabel_local_islands(0)
+    cols = synth.planner_requests(grid, dests)             # the benchmark's request fixture
+    if cols is None:
+        cols = synth.whole_map_requests(grid, dests, synth.from_chunks(ctx.download_plane(0, navhip.PLANE_LOCAL_ISLANDS)))
+    plain = navhip.make_reqs(len(cols["type"]))
+    for k in synth.REQ_FIELDS:
+        plain[k] = cols[k]
+    attack = plain.copy()
+    attack["faction_id"], attack["enemies"] = 0, 0b010
+    c = synth.faction_circles(grid, 4000, seed=11)
+    circ = np.zeros(4000, navhip.CIRCLE_DTYPE)
+    for k in ("x", "z", "radius", "faction_id"):
+        circ[k] = c[k]
+    circ["delta"] = 1
+    ctx.N_BlockersUpdate(circ)
+    pool = torch.zeros((len(plain), 4096), dtype=torch.uint8, device=dev)
+    st = torch.cuda.Stream(device=dev)
+    has_split = hasattr(navhip.lib(), "navhip_last_fields_split")        # (an A/B build of an older revision)
+    res = {"chunk_fields": len(plain), "circles": len(circ), "what": "faction 0, enemies 0b010; 1024x1024 map, three factions"}
+    fields = {}
+    for name, reqs, mode, reps in (("attack_mode0", attack, 0, 10), ("attack_mode1", attack, 1, 3), ("plain_mode0", plain, 0, 10),
+                                   ("attack_mode0_again", attack, 0, 10)):
+        d_reqs = torch.from_numpy(reqs.view(np.uint8).reshape(len(reqs), 32)).to(dev)
+        ctx.set_field_kernel(mode)
+
+        def run():
+            ctx.build_fields_dev(d_reqs, len(reqs), pool, stream=st.cuda_stream)
+            st.synchronize()
+        t = timed(run, reps=reps)
+        res[name] = {"ms": t * 1e3, "split_bfs_generic": list(ctx.last_fields_split()) if has_split else None}
+        fields[name] = pool.clone()
+    ctx.set_field_kernel(0)
+    assert torch.equal(fields["attack_mode0"], fields["attack_mode1"]) and torch.equal(fields["attack_mode0"], fields["attack_mode0_again"])
+    res["attack_fields_differing_from_plain"] = int((fields["attack_mode0"] != fields["plain_mode0"]).any(1).sum().item())
+    res["attack_mode0_over_plain_mode0"] = res["attack_mode0"]["ms"] / res["plain_mode0"]["ms"]
+    res["attack_mode1_over_mode0"] = res["attack_mode1"]["ms"] / res["attack_mode0"]["ms"]
+
+    # the blocker update with faction counters: 10 000 circles in, the same out
+    rng = np.random.RandomState(5)
+    cells = synth.passable_cells(grid)
+    pos = synth.cell_centre(W, W, *cells[rng.randint(len(cells), size=10_000)].T)
+    big = np.zeros(10_000, navhip.CIRCLE_DTYPE)
+    big["x"], big["z"] = pos[:, 0], pos[:, 1]
+    big["radius"] = rng.uniform(2.0, 6.0, 10_000)
+    big["faction_id"] = rng.randint(0, 3, 10_000)
+    undo = big.copy()
+    big["delta"], undo["delta"] = 1, -1
+
+    def blk():
+        ctx.N_BlockersUpdate(big)
+        ctx.N_BlockersUpdate(undo)
+    t = timed(blk, reps=5)
+    res["blockers_circles_with_factions"] = {"circles_per_call": 10_000, "ms_per_call_host_api": t * 1e3 / 2}
+    ctx.close()
+    return res
+
+
 def main():
     import torch
     torch.cuda.init()
     dev = torch.device("cuda", 0)
+    if "--attacking-only" in sys.argv:
+        print(json.dumps({"field_attacking": field_attacking(torch, dev)}, indent=1))
+        return
     W, K = 16, 64
     rng = np.random.RandomState(5)
     grid = synth.cost_grid(W, W, seed=1234)
@@ -123,6 +197,7 @@ def main():
     t = timed(lambda: ctx.N_LOSFieldCreate(lr), reps=3)
     out["los_fields"] = {"fields": 4096, "ms_host_api": t * 1e3, "fields_per_s": 4096 / t}
     ctx.close()
+    out["field_attacking"] = field_attacking(torch, dev)
     print(json.dumps(out, indent=1))
 
 
