@@ -475,10 +475,210 @@ __global__ __launch_bounds__(256) void k_arrival_settle(nh_step_params P, const 
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-struct sk_arena {                     // one staging slot, carved up: offsets first, then the pointer
+// One staging slot, planned before it is reserved: input rows (a host source), scratch rows, and the rows of a scratch
+// row that go back to the host.  Rows are 256-byte aligned; reserve() gives every row its device address and writes it
+// to the member of the device-side struct the row was staged for (`twin`).  How the rows cross the bus is a policy:
+//   per row   (default)  one copy per row: the gate, the aux pass, the state pass, the settled count
+//   region()             rows that lie side by side travel as ONE region, mirrored in the page-locked slabs: the settle calls
+//   pack()               page-locked arrays travel in place, pageable ones as ONE block behind the rows: the resident pass
+struct sk_plan {
+    struct row { size_t off, bytes; const void *src; void **twin; char *dev; bool direct; size_t h_off; };
+    struct ret { int row; void *dst; size_t elem, lo, cnt, h_off; bool direct; };   // rows [lo, lo + cnt) of `row` -> dst
+    std::vector<row> rows;
+    std::vector<ret> rets;
     size_t total = 0;
-    size_t take(size_t bytes) { const size_t o = total; total += (bytes + 255) & ~(size_t)255; return o; }
+    size_t in_blk = 0, in_bytes = 0, out_blk = 0, out_bytes = 0;    // the block of each direction: offset in the slot, bytes
+    bool gather = false;                                            // pack(): the blocks lie behind the rows
+    char *base = nullptr, *h_in = nullptr, *h_out = nullptr;
+
+    static size_t up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+    // pad: tail bytes of a row whose array may be empty, so that a kernel is never handed the next row's address as its own
+    int in(const void *src, size_t bytes, size_t pad = 0, void **twin = nullptr)
+    {
+        rows.push_back({total, src ? bytes : 0, src, twin, nullptr, true, 0});
+        total += up(bytes + pad);
+        return (int)rows.size() - 1;
+    }
+    int scratch(size_t bytes, void **twin = nullptr) { return in(nullptr, bytes, 0, twin); }
+    void out(int row, void *dst, size_t elem, size_t lo, size_t cnt) { if(dst && cnt) rets.push_back({row, dst, elem, lo, cnt, 0, true}); }
+    template<class T> T *dev(int r) const { return (T*)rows[r].dev; }
+
+    // input rows [first, end) go up as one region, everything from row first_out on comes down as one -- when the
+    // context owns page-locked slabs (an asynchronous step path); per row otherwise
+    void region(navhip_ctx *ctx, int first, int end, int first_out)
+    {
+        const size_t i0 = rows[first].off, o0 = rows[first_out].off;
+        if(nh_async_slabs(ctx, rows[end].off - i0, total - o0, &h_in, &h_out) != NAVHIP_OK) return;
+        in_blk = i0; in_bytes = rows[end].off - i0; out_blk = o0; out_bytes = total - o0;
+        for(int i = first; i < end; i++) { rows[i].direct = false; rows[i].h_off = rows[i].off - i0; }
+        for(ret &o : rets) { o.direct = false; o.h_off = rows[o.row].off + o.lo * o.elem - o0; }
+    }
+    // in_bytes / out_bytes: what the caller asks nh_async_slabs for (h_in, h_out)
+    void pack()
+    {
+        gather = true;
+        for(row &r : rows) if(r.bytes && !(r.direct = nh_is_pinned(r.src))) { r.h_off = in_bytes; in_bytes += up(r.bytes); }
+        for(ret &o : rets) if(!(o.direct = nh_is_pinned(o.dst))) { o.h_off = out_bytes; out_bytes += up(o.cnt * o.elem); }
+        in_blk = total; out_blk = total + in_bytes;
+    }
+    int reserve(navhip_ctx *ctx, nh_stage_slot slot)
+    {
+        int rc = nh_stage_reserve(ctx, slot, total + (gather ? in_bytes + out_bytes + 256 : 0), (void**)&base);
+        if(rc) return rc;
+        for(row &r : rows) {
+            r.dev = base + (gather && !r.direct ? in_blk + r.h_off : r.off);
+            if(r.twin) *r.twin = r.dev;
+        }
+        return NAVHIP_OK;
+    }
+    int upload(navhip_ctx *ctx, hipStream_t s)
+    {
+        for(const row &r : rows) {
+            if(!r.bytes) continue;
+            if(r.direct) HIPCHK(ctx, hipMemcpyAsync(r.dev, r.src, r.bytes, hipMemcpyHostToDevice, s));
+            else         memcpy(h_in + r.h_off, r.src, r.bytes);
+        }
+        if(in_bytes) HIPCHK(ctx, hipMemcpyAsync(base + in_blk, h_in, in_bytes, hipMemcpyHostToDevice, s));
+        return NAVHIP_OK;
+    }
+    // the results, and the wait for them
+    int download(navhip_ctx *ctx, hipStream_t s)
+    {
+        for(const ret &o : rets) {
+            const char *d = rows[o.row].dev + o.lo * o.elem;
+            if(o.direct)    HIPCHK(ctx, hipMemcpyAsync((char*)o.dst + o.lo * o.elem, d, o.cnt * o.elem, hipMemcpyDeviceToHost, s));
+            else if(gather) HIPCHK(ctx, hipMemcpyAsync(base + out_blk + o.h_off, d, o.cnt * o.elem, hipMemcpyDeviceToDevice, s));
+        }
+        if(out_bytes) HIPCHK(ctx, hipMemcpyAsync(h_out, base + out_blk, out_bytes, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        for(const ret &o : rets) if(!o.direct) memcpy((char*)o.dst + o.lo * o.elem, h_out + o.h_off, o.cnt * o.elem);
+        return NAVHIP_OK;
+    }
 };
+
+// Which pointer member of an input / output struct is how large and when it travels: ONE list per struct for every
+// host-buffer path here (as nh_world_rows is for navhip_world).  sk_stage walks a list: staging a struct and building
+// its device twin is one loop.
+enum sk_len : uint8_t { SK_PER_UNIT, SK_PER_FLOCK, SK_PER_FLOCK_PLUS1, SK_PER_TILE, SK_PER_RANGE_ROW_PLUS1, SK_PER_RANGE_TILE,
+                        SK_PER_QUERY, SK_PER_ZONE, SK_PER_SLOT, SK_PER_KEY,
+                        SK_PER_ARM_ROW,       // a row per unit -- with sparse rows, per LISTED unit
+                        SK_PER_LISTED, SK_LEN_COUNT };
+enum sk_group : uint8_t { SK_ALWAYS, SK_SKIP, SK_TURN, SK_RANGE, SK_SURROUND, SK_INTERP, SK_SPARSE, SK_AUX, SK_GROUP_COUNT };
+struct sk_row { size_t off; uint16_t elem; uint8_t len, group, pad; bool out; };
+struct sk_dims {
+    size_t len[SK_LEN_COUNT] = {};
+    bool   on[SK_GROUP_COUNT] = {true};     // SK_ALWAYS
+    size_t pad = 0;                         // at least this much tail padding on every row
+    size_t lo = 0, cnt = 0;                 // the rows of a per-unit / per-query result that go back
+};
+#define SK_ROW(T, member, elem, len, group) {offsetof(T, member), elem, len, group, 0, false}
+#define SK_ROW_PAD(T, member, elem, len, group, pad) {offsetof(T, member), elem, len, group, pad, false}
+#define SK_ROW_OUT(T, member, elem, len, group) {offsetof(T, member), elem, len, group, 0, true}
+const sk_row sk_gate_rows[] = {
+    SK_ROW(navhip_gate_in, next_rot, 16, SK_PER_UNIT, SK_ALWAYS),       SK_ROW(navhip_gate_in, new_vel_xz, 8, SK_PER_UNIT, SK_ALWAYS),
+    SK_ROW(navhip_gate_in, vdes_xz, 8, SK_PER_UNIT, SK_ALWAYS),         SK_ROW(navhip_gate_in, interp_from_xz, 8, SK_PER_UNIT, SK_INTERP),
+    SK_ROW(navhip_gate_in, interp_step, 4, SK_PER_UNIT, SK_INTERP),
+};
+const sk_row sk_state_rows[] = {
+    SK_ROW(navhip_state_in, new_pos_xz, 8, SK_PER_UNIT, SK_ALWAYS),     SK_ROW(navhip_state_in, vdes_xz, 8, SK_PER_UNIT, SK_ALWAYS),
+    SK_ROW(navhip_state_in, skip, 1, SK_PER_UNIT, SK_SKIP),             SK_ROW(navhip_state_in, flock_layer, 1, SK_PER_FLOCK, SK_ALWAYS),
+    SK_ROW(navhip_state_in, flock_nearest_xz, 8, SK_PER_FLOCK, SK_ALWAYS),
+    SK_ROW(navhip_state_in, flock_tiles_off, 4, SK_PER_FLOCK_PLUS1, SK_ALWAYS),
+    SK_ROW(navhip_state_in, flock_tiles, 4, SK_PER_TILE, SK_ALWAYS),
+};
+const sk_row sk_aux_rows[] = {
+    SK_ROW(navhip_state_aux_in, fstate, 1, SK_PER_UNIT, SK_ALWAYS),     SK_ROW(navhip_state_aux_in, wait_ticks_left, 4, SK_PER_UNIT, SK_ALWAYS),
+    SK_ROW(navhip_state_aux_in, wait_prev, 1, SK_PER_UNIT, SK_ALWAYS),  SK_ROW(navhip_state_aux_in, new_pos_xz, 8, SK_PER_UNIT, SK_ALWAYS),
+    SK_ROW(navhip_state_aux_in, ent_rot, 16, SK_PER_ARM_ROW, SK_TURN),  SK_ROW(navhip_state_aux_in, target_dir, 16, SK_PER_ARM_ROW, SK_TURN),
+    SK_ROW(navhip_state_aux_in, range_target, 4, SK_PER_ARM_ROW, SK_RANGE),
+    SK_ROW(navhip_state_aux_in, target_range, 4, SK_PER_ARM_ROW, SK_RANGE),
+    SK_ROW(navhip_state_aux_in, target_prev_xz, 8, SK_PER_ARM_ROW, SK_RANGE),
+    SK_ROW(navhip_state_aux_in, range_tiles_row, 4, SK_PER_ARM_ROW, SK_RANGE),
+    SK_ROW(navhip_state_aux_in, range_tiles_off, 4, SK_PER_RANGE_ROW_PLUS1, SK_RANGE),
+    SK_ROW_PAD(navhip_state_aux_in, range_tiles, 4, SK_PER_RANGE_TILE, SK_RANGE, 4),
+    SK_ROW(navhip_state_aux_in, surround_target, 4, SK_PER_ARM_ROW, SK_SURROUND),
+    SK_ROW(navhip_state_aux_in, surround_query, 1, SK_PER_ARM_ROW, SK_SURROUND),
+    SK_ROW(navhip_state_aux_in, surround_target_prev_xz, 8, SK_PER_ARM_ROW, SK_SURROUND),
+    SK_ROW(navhip_state_aux_in, surround_nearest_prev_xz, 8, SK_PER_ARM_ROW, SK_SURROUND),
+    SK_ROW(navhip_state_aux_in, surround_dest_xz, 16, SK_PER_ARM_ROW, SK_SURROUND),
+    SK_ROW(navhip_state_aux_in, vdes_xz, 8, SK_PER_UNIT, SK_SURROUND),
+    SK_ROW_OUT(navhip_state_aux_in, out_surround_dest_xz, 8, SK_PER_UNIT, SK_SURROUND),
+    SK_ROW(navhip_state_aux_in, sparse_units, 4, SK_PER_LISTED, SK_SPARSE),
+};
+const sk_row sk_pass_out_rows[] = {
+    SK_ROW_OUT(navhip_state_pass_out, state, 1, SK_PER_UNIT, SK_ALWAYS),      SK_ROW_OUT(navhip_state_pass_out, flags, 1, SK_PER_UNIT, SK_ALWAYS),
+    SK_ROW_OUT(navhip_state_pass_out, gate, 1, SK_PER_UNIT, SK_ALWAYS),       SK_ROW_OUT(navhip_state_pass_out, new_pos_xz, 8, SK_PER_UNIT, SK_ALWAYS),
+    SK_ROW_OUT(navhip_state_pass_out, vel_xz, 8, SK_PER_UNIT, SK_ALWAYS),     SK_ROW_OUT(navhip_state_pass_out, wait_ticks_left, 4, SK_PER_UNIT, SK_AUX),
+};
+const sk_row sk_settle_in_rows[] = {
+    SK_ROW(navhip_settle_in, zones, sizeof(navhip_arrival_zone), SK_PER_ZONE, SK_ALWAYS),
+    SK_ROW_PAD(navhip_settle_in, slots_xz, 8, SK_PER_SLOT, SK_ALWAYS, 8),     SK_ROW_PAD(navhip_settle_in, slot_ring, 4, SK_PER_SLOT, SK_ALWAYS, 4),
+    SK_ROW_PAD(navhip_settle_in, region_keys, 8, SK_PER_KEY, SK_ALWAYS, 8),   SK_ROW(navhip_settle_in, uid, 4, SK_PER_QUERY, SK_ALWAYS),
+    SK_ROW(navhip_settle_in, zone, 4, SK_PER_QUERY, SK_ALWAYS),               SK_ROW(navhip_settle_in, new_pos_xz, 8, SK_PER_QUERY, SK_ALWAYS),
+    SK_ROW(navhip_settle_in, nsettled, 4, SK_PER_QUERY, SK_ALWAYS),           SK_ROW(navhip_settle_in, substate, 1, SK_PER_QUERY, SK_ALWAYS),
+    SK_ROW(navhip_settle_in, sink_valid, 1, SK_PER_QUERY, SK_ALWAYS),         SK_ROW(navhip_settle_in, sink_xz, 8, SK_PER_QUERY, SK_ALWAYS),
+    SK_ROW(navhip_settle_in, order_pos_xz, 8, SK_PER_QUERY, SK_ALWAYS),       SK_ROW(navhip_settle_in, progress_anchor_xz, 8, SK_PER_QUERY, SK_ALWAYS),
+    SK_ROW(navhip_settle_in, progress_anchored, 1, SK_PER_QUERY, SK_ALWAYS),  SK_ROW(navhip_settle_in, stuck, 4, SK_PER_QUERY, SK_ALWAYS),
+};
+const sk_row sk_settle_out_rows[] = {
+    SK_ROW_OUT(navhip_settle_out, settle, 1, SK_PER_QUERY, SK_ALWAYS),        SK_ROW_OUT(navhip_settle_out, substate, 1, SK_PER_QUERY, SK_ALWAYS),
+    SK_ROW_OUT(navhip_settle_out, progress_anchor_xz, 8, SK_PER_QUERY, SK_ALWAYS),
+    SK_ROW_OUT(navhip_settle_out, progress_anchored, 1, SK_PER_QUERY, SK_ALWAYS),
+    SK_ROW_OUT(navhip_settle_out, stuck, 4, SK_PER_QUERY, SK_ALWAYS),         SK_ROW_OUT(navhip_settle_out, nsettled, 4, SK_PER_QUERY, SK_ALWAYS),
+};
+#undef SK_ROW
+#undef SK_ROW_PAD
+#undef SK_ROW_OUT
+// a new pointer member breaks the build here until its list has a row for it
+#define SK_COVERS(tab, T, scalar_bytes) \
+    static_assert(sizeof(T) == sizeof(tab) / sizeof(tab[0]) * sizeof(void*) + (scalar_bytes), #T " changed: does " #tab " cover it?")
+SK_COVERS(sk_gate_rows, navhip_gate_in, 0);
+SK_COVERS(sk_state_rows, navhip_state_in, 0);
+SK_COVERS(sk_aux_rows, navhip_state_aux_in, 16);            // n_range_rows, n_sparse: 4 bytes and 4 of padding each
+SK_COVERS(sk_pass_out_rows, navhip_state_pass_out, 0);
+SK_COVERS(sk_settle_in_rows, navhip_settle_in, 8);          // n_zones, nq
+SK_COVERS(sk_settle_out_rows, navhip_settle_out, 0);
+#undef SK_COVERS
+
+bool sk_listed(std::initializer_list<size_t> members, size_t off)
+{
+    for(size_t m : members) if(m == off) return true;
+    return false;
+}
+
+// Stage the members of *in whose group is on, and have reserve() point the same members of *twin at the device copies.
+// elsewhere: members this caller does not take from *in (another pass produces them on the device): it sets them in *twin.
+template<class T, size_t N>
+void sk_stage(sk_plan &p, const sk_row (&tab)[N], const T *in, T *twin, const sk_dims &D, std::initializer_list<size_t> elsewhere = {})
+{
+    for(const sk_row &r : tab) {
+        if(!D.on[r.group] || sk_listed(elsewhere, r.off)) continue;
+        const size_t bytes = D.len[r.len] * r.elem;
+        if(r.out) p.out(p.scratch(bytes, &nh_member(twin, r.off)), (void*)nh_member(in, r.off), r.elem, D.lo, D.cnt);
+        else      p.in(nh_member(in, r.off), bytes, D.pad > r.pad ? D.pad : r.pad, &nh_member(twin, r.off));
+    }
+}
+
+// ... and the listed arrays of the snapshot (nh_world_rows knows their sizes)
+void sk_stage_world(sk_plan &p, const navhip_world *w, navhip_world *twin, const sk_dims &D, std::initializer_list<size_t> members,
+                    size_t nmembers = 0, size_t pad = 0)
+{
+    for(const nh_world_row &r : nh_world_rows) {
+        if(!sk_listed(members, r.off)) continue;
+        const size_t cnt = r.count == NH_PER_ENT ? D.len[SK_PER_UNIT] : r.count == NH_PER_FLOCK ? D.len[SK_PER_FLOCK]
+                         : r.count == NH_PER_FLOCK_PLUS1 ? D.len[SK_PER_FLOCK_PLUS1] : nmembers;
+        p.in(nh_member(w, r.off), cnt * r.row_bytes, D.pad > pad ? D.pad : pad, &nh_member(twin, r.off));
+    }
+}
+#define SK_W(member) offsetof(navhip_world, member)
+
+// the scalars of the world, no array: what is not staged must not travel as a host pointer
+navhip_world sk_device_world(const navhip_world *w)
+{
+    navhip_world d = *w;
+    for(const nh_world_row &r : nh_world_rows) nh_member(&d, r.off) = nullptr;
+    return d;
+}
 
 void sk_map_view(const navhip_ctx *ctx, const navhip_world *w, nh_step_params *P)
 {
@@ -488,39 +688,108 @@ void sk_map_view(const navhip_ctx *ctx, const navhip_world *w, nh_step_params *P
     P->n_ents = w->n_ents; P->hz = w->hz;
 }
 
-// the surround inputs come together, with the snapshot arrays the arm reads
-bool sk_surround_inputs_ok(const navhip_world *w, const navhip_state_aux_in *in)
-{
-    const int given = (in->surround_target != nullptr) + (in->surround_query != nullptr) + (in->surround_target_prev_xz != nullptr)
-                    + (in->surround_nearest_prev_xz != nullptr) + (in->surround_dest_xz != nullptr) + (in->vdes_xz != nullptr)
-                    + (in->out_surround_dest_xz != nullptr);
-    return given == 0 || (given == 7 && w->pos_xz && w->vel_xz && w->flock && (w->n_flocks == 0 || w->flock_target_xz));
-}
-
-// the six enter-range inputs come together, with the positions of the snapshot
-bool sk_range_inputs_ok(const navhip_world *w, const navhip_state_aux_in *in)
-{
-    const int given = (in->range_target != nullptr) + (in->target_range != nullptr) + (in->target_prev_xz != nullptr)
-                    + (in->range_tiles_row != nullptr) + (in->range_tiles_off != nullptr) + (in->range_tiles != nullptr);
-    return given == 0 || (given == 6 && w->pos_xz && in->n_range_rows >= 0);
-}
-
-// the interpolated position of a rate below 20 Hz: both arrays, the movement rate, and what names the unit's nav layer
-bool sk_interp_inputs_ok(const navhip_world *w, const navhip_gate_in *in)
-{
-    if((in->interp_from_xz != nullptr) != (in->interp_step != nullptr)) return false;
-    if(w->hz != 20 && w->hz != 10 && w->hz != 5 && w->hz != 1 && w->hz != 0) return false;
-    return !in->interp_from_xz || (w->radius && w->flags);
-}
-
-// sparse rows are navhip_state_pass_resident's
-bool sk_no_sparse(const navhip_state_aux_in *in) { return in->sparse_units == nullptr && in->n_sparse == 0; }
-
 bool sk_work_range(const navhip_world *w, int *b, int *e)
 {
     *b = w->work_begin; *e = w->work_end;
     if(*b == 0 && *e == 0) *e = w->n_ents;
     return *b >= 0 && *e <= w->n_ents && *b <= *e;
+}
+
+sk_dims sk_dims_of(const navhip_world *w, int b, int e)
+{
+    sk_dims D;
+    D.len[SK_PER_UNIT] = D.len[SK_PER_ARM_ROW] = (size_t)w->n_ents;
+    D.len[SK_PER_FLOCK] = (size_t)(w->n_flocks > 0 ? w->n_flocks : 0);
+    D.len[SK_PER_FLOCK_PLUS1] = D.len[SK_PER_FLOCK] + 1;
+    D.lo = (size_t)b; D.cnt = (size_t)(e - b);
+    return D;
+}
+
+// ---- one argument check per struct: the host-buffer calls, the passes and the _dev entry points all use them --------
+bool sk_csr_ok(const int32_t *off, size_t rows)
+{
+    for(size_t r = 0; r < rows; r++)
+        if(off[r] < 0 || off[r + 1] < off[r]) return false;
+    return true;
+}
+
+// the snapshot arrays the gate reads, its three inputs; the interpolated position of a rate below 20 Hz: both arrays,
+// the movement rate, and what names the unit's nav layer
+bool sk_check_gate(const navhip_world *w, const navhip_gate_in *in)
+{
+    if(!w->pos_xz || !w->vel_xz || !w->state || !in->next_rot || !in->new_vel_xz || !in->vdes_xz) return false;
+    if((in->interp_from_xz != nullptr) != (in->interp_step != nullptr)) return false;
+    if(w->hz != 20 && w->hz != 10 && w->hz != 5 && w->hz != 1 && w->hz != 0) return false;
+    return !in->interp_from_xz || (w->radius && w->flags);
+}
+
+// navhip_state_in inside a pass (new_pos_xz and vdes_xz are the gate's); navhip_state_update_dev checks the same and those two
+bool sk_check_state(const navhip_world *w, const navhip_state_in *in)
+{
+    return w->pos_xz && w->radius && w->flags && w->state && w->flock
+        && (w->n_flocks <= 0 || (w->flock_target_xz && w->flock_offsets && w->flock_members && in->flock_layer && in->flock_nearest_xz
+                                 && in->flock_tiles_off && in->flock_tiles));
+}
+
+enum sk_aux_caller {
+    SK_AUX_ALONE,       // navhip_state_update_aux[_dev]: every array is the caller's
+    SK_PASS,            // navhip_state_pass: new_pos_xz, vdes_xz and the snapshot of the surround arm are the pass's own
+    SK_PASS_RESIDENT,   // navhip_state_pass_resident: that, sparse rows are allowed, and range arrays without a range_target are
+                        // ignored, not refused, as that call always has
+};
+bool sk_check_aux(const navhip_world *w, const navhip_state_aux_in *in, sk_aux_caller by)
+{
+    if(!w->radius || !w->flags || !w->state || !in->fstate || !in->wait_ticks_left || !in->wait_prev
+    || (by == SK_AUX_ALONE && !in->new_pos_xz) || (in->ent_rot != nullptr) != (in->target_dir != nullptr)) return false;
+    // sparse rows are navhip_state_pass_resident's
+    if(by != SK_PASS_RESIDENT && (in->sparse_units != nullptr || in->n_sparse != 0)) return false;
+    // the six enter-range inputs come together, with the positions of the snapshot
+    const int range = (in->range_target != nullptr) + (in->target_range != nullptr) + (in->target_prev_xz != nullptr)
+                    + (in->range_tiles_row != nullptr) + (in->range_tiles_off != nullptr) + (in->range_tiles != nullptr);
+    if(!(by == SK_PASS_RESIDENT && !in->range_target) && range != 0 && !(range == 6 && w->pos_xz && in->n_range_rows >= 0)) return false;
+    // the surround inputs come together, with the snapshot arrays the arm reads (a pass supplies vdes and those itself:
+    // its caller gives the five query arrays and the output)
+    const int query = (in->surround_query != nullptr) + (in->surround_target_prev_xz != nullptr) + (in->surround_nearest_prev_xz != nullptr)
+                    + (in->surround_dest_xz != nullptr) + (in->out_surround_dest_xz != nullptr);
+    if(in->surround_target && query != 5) return false;
+    if(by != SK_AUX_ALONE) return true;
+    if(!in->surround_target) return query == 0 && !in->vdes_xz;
+    return in->vdes_xz && w->pos_xz && w->vel_xz && w->flock && (w->n_flocks == 0 || w->flock_target_xz);
+}
+
+// The per-unit rows of the enter-range and surround arms, rows [v0, v1) of their arrays; fills in which arms are given and how
+// long the range tables are.  hw: the snapshot where the host has it; NULL in the resident pass, where states and flocks
+// are on the device: then every row with a range target is checked whatever its unit's state, row 0 passes when there
+// are no rows at all (what a unit of another state holds), and a surround unit's flock is not looked at.
+bool sk_check_arm_rows(const navhip_state_aux_in *in, int n_ents, const navhip_world *hw, size_t v0, size_t v1, sk_dims *D)
+{
+    D->on[SK_TURN] = in->ent_rot != nullptr; D->on[SK_RANGE] = in->range_target != nullptr; D->on[SK_SURROUND] = in->surround_target != nullptr;
+    if(in->range_target) {
+        const size_t rows = (size_t)in->n_range_rows;
+        if(!sk_csr_ok(in->range_tiles_off, rows)) return false;
+        D->len[SK_PER_RANGE_ROW_PLUS1] = rows + 1;
+        D->len[SK_PER_RANGE_TILE] = rows ? (size_t)in->range_tiles_off[rows] : 0;
+        for(size_t i = v0; i < v1; i++) {
+            const int32_t t = in->range_target[i], r = in->range_tiles_row[i];
+            if(t >= n_ents) return false;
+            if(t >= 0 && (!hw || hw->state[i] == NAVHIP_STATE_ENTER_ENTITY_RANGE) && (r < 0 || (size_t)r >= (hw || rows ? rows : 1))) return false;
+        }
+    }
+    if(in->surround_target)
+        for(size_t i = v0; i < v1; i++) {
+            const int32_t t = in->surround_target[i];
+            if(t >= n_ents) return false;
+            if(hw && hw->state[i] == NAVHIP_STATE_SURROUND_ENTITY && t >= -1 && hw->flock[i] >= hw->n_flocks) return false;
+        }
+    return true;
+}
+
+// what every settle call needs of its two structs (nsettled aside: navhip_arrival_settle_resident can count on the device)
+bool sk_check_settle(const navhip_settle_in *in, const navhip_settle_out *out)
+{
+    return in->zones && in->n_zones >= 1 && in->uid && in->zone && in->new_pos_xz && in->substate && in->sink_valid && in->sink_xz
+        && in->order_pos_xz && in->progress_anchor_xz && in->progress_anchored && in->stuck && out->settle && out->substate
+        && out->progress_anchor_xz && out->progress_anchored && out->stuck;
 }
 
 }   // namespace
@@ -532,10 +801,8 @@ int navhip_heading_gate_dev(navhip_ctx *ctx, const navhip_world *w, const navhip
 {
     if(!ctx || !w || !in || !out_vel || !out_new_pos || !out_gate || w->n_ents < 0) return NAVHIP_ERR_INVALID;
     if(w->n_ents == 0) return NAVHIP_OK;
-    if(!w->pos_xz || !w->vel_xz || !w->state || !in->next_rot || !in->new_vel_xz || !in->vdes_xz) return NAVHIP_ERR_INVALID;
-    if(!sk_interp_inputs_ok(w, in)) return NAVHIP_ERR_INVALID;
     int b, e;
-    if(!sk_work_range(w, &b, &e)) return NAVHIP_ERR_INVALID;
+    if(!sk_check_gate(w, in) || !sk_work_range(w, &b, &e)) return NAVHIP_ERR_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if(in->interp_from_xz) {
         // (the accept test of the interpolated position probes the derived row masks: rebuilt here if a plane changed)
@@ -556,48 +823,28 @@ int navhip_heading_gate(navhip_ctx *ctx, const navhip_world *w, const navhip_gat
 {
     if(!ctx || !w || !in || !out_vel || !out_new_pos || !out_gate || w->n_ents < 0) return NAVHIP_ERR_INVALID;
     if(w->n_ents == 0) return NAVHIP_OK;
-    if(!w->pos_xz || !w->vel_xz || !w->state || !in->next_rot || !in->new_vel_xz || !in->vdes_xz) return NAVHIP_ERR_INVALID;
     int b, e;
-    if(!sk_work_range(w, &b, &e)) return NAVHIP_ERR_INVALID;
+    if(!sk_check_gate(w, in) || !sk_work_range(w, &b, &e)) return NAVHIP_ERR_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
+    sk_dims D = sk_dims_of(w, b, e);
+    D.on[SK_INTERP] = in->interp_from_xz != nullptr;
     const size_t n = (size_t)w->n_ents;
-    if(!sk_interp_inputs_ok(w, in)) return NAVHIP_ERR_INVALID;
-    const bool ip = in->interp_from_xz != nullptr;
-    sk_arena A;
-    const size_t o_pos = A.take(n * 8), o_vel = A.take(n * 8), o_state = A.take(n), o_rot = A.take(n * 16),
-                 o_nv = A.take(n * 8), o_vd = A.take(n * 8), o_ov = A.take(n * 8), o_op = A.take(n * 8), o_og = A.take(n),
-                 o_if = A.take(ip ? n * 8 : 0), o_is = A.take(ip ? n * 4 : 0), o_rad = A.take(ip ? n * 4 : 0), o_flg = A.take(ip ? n * 4 : 0);
-    char *base;
-    int rc = nh_stage_reserve(ctx, NH_STAGE_STATE_ARENA, A.total, (void**)&base);
-    if(rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(base + o_pos, w->pos_xz, n * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(base + o_vel, w->vel_xz, n * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(base + o_state, w->state, n, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(base + o_rot, in->next_rot, n * 16, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(base + o_nv, in->new_vel_xz, n * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(base + o_vd, in->vdes_xz, n * 8, hipMemcpyHostToDevice, s));
-    navhip_world d = *w;
-    d.pos_xz = (const float*)(base + o_pos); d.vel_xz = (const float*)(base + o_vel); d.state = (const uint8_t*)(base + o_state);
-    navhip_gate_in di = {(const float*)(base + o_rot), (const float*)(base + o_nv), (const float*)(base + o_vd), nullptr, nullptr};
-    if(ip) {
-        HIPCHK(ctx, hipMemcpyAsync(base + o_if, in->interp_from_xz, n * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(base + o_is, in->interp_step, n * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(base + o_rad, w->radius, n * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(base + o_flg, w->flags, n * 4, hipMemcpyHostToDevice, s));
-        di.interp_from_xz = (const float*)(base + o_if); di.interp_step = (const float*)(base + o_is);
-        d.radius = (const float*)(base + o_rad); d.flags = (const uint32_t*)(base + o_flg);
-    }
-    rc = navhip_heading_gate_dev(ctx, &d, &di, (float*)(base + o_ov), (float*)(base + o_op), (uint8_t*)(base + o_og), s);
-    if(rc) return rc;
-    if(e > b) {
-        const size_t lo = (size_t)b, cnt = (size_t)(e - b);
-        HIPCHK(ctx, hipMemcpyAsync(out_vel + 2 * lo, base + o_ov + 8 * lo, cnt * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipMemcpyAsync(out_new_pos + 2 * lo, base + o_op + 8 * lo, cnt * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipMemcpyAsync(out_gate + lo, base + o_og + lo, cnt, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return NAVHIP_OK;
+    sk_plan P;
+    navhip_world d = sk_device_world(w);
+    navhip_gate_in di = {};
+    sk_stage_world(P, w, &d, D, {SK_W(pos_xz), SK_W(vel_xz), SK_W(state)});
+    if(D.on[SK_INTERP]) sk_stage_world(P, w, &d, D, {SK_W(radius), SK_W(flags)});
+    sk_stage(P, sk_gate_rows, in, &di, D);
+    float *d_vel, *d_pos; uint8_t *d_gate;
+    P.out(P.scratch(n * 8, (void**)&d_vel), out_vel, 8, D.lo, D.cnt);
+    P.out(P.scratch(n * 8, (void**)&d_pos), out_new_pos, 8, D.lo, D.cnt);
+    P.out(P.scratch(n, (void**)&d_gate), out_gate, 1, D.lo, D.cnt);
+    int rc = P.reserve(ctx, NH_STAGE_STATE_ARENA);
+    if(!rc) rc = P.upload(ctx, s);
+    if(!rc) rc = navhip_heading_gate_dev(ctx, &d, &di, d_vel, d_pos, d_gate, s);
+    if(!rc) rc = P.download(ctx, s);
+    return rc;
 }
 
 int navhip_state_update_aux_dev(navhip_ctx *ctx, const navhip_world *w, const navhip_state_aux_in *in, uint8_t *io_state,
@@ -605,11 +852,8 @@ int navhip_state_update_aux_dev(navhip_ctx *ctx, const navhip_world *w, const na
 {
     if(!ctx || !w || !in || !io_state || !io_flags || !out_ticks || w->n_ents < 0) return NAVHIP_ERR_INVALID;
     if(w->n_ents == 0) return NAVHIP_OK;
-    if(!w->radius || !w->flags || !w->state || !in->fstate || !in->wait_ticks_left || !in->wait_prev || !in->new_pos_xz
-    || (in->ent_rot != nullptr) != (in->target_dir != nullptr) || !sk_range_inputs_ok(w, in) || !sk_surround_inputs_ok(w, in) || !sk_no_sparse(in))
-        return NAVHIP_ERR_INVALID;
     int b, e;
-    if(!sk_work_range(w, &b, &e)) return NAVHIP_ERR_INVALID;
+    if(!sk_check_aux(w, in, SK_AUX_ALONE) || !sk_work_range(w, &b, &e)) return NAVHIP_ERR_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     nh_step_params P;
     sk_map_view(ctx, w, &P);
@@ -627,113 +871,63 @@ int navhip_state_update_aux(navhip_ctx *ctx, const navhip_world *w, const navhip
 {
     if(!ctx || !w || !in || !io_state || !io_flags || !out_ticks || w->n_ents < 0) return NAVHIP_ERR_INVALID;
     if(w->n_ents == 0) return NAVHIP_OK;
-    if(!w->radius || !w->flags || !w->state || !in->fstate || !in->wait_ticks_left || !in->wait_prev || !in->new_pos_xz
-    || (in->ent_rot != nullptr) != (in->target_dir != nullptr) || !sk_range_inputs_ok(w, in) || !sk_surround_inputs_ok(w, in) || !sk_no_sparse(in))
-        return NAVHIP_ERR_INVALID;
     int b, e;
-    if(!sk_work_range(w, &b, &e)) return NAVHIP_ERR_INVALID;
-    const size_t n = (size_t)w->n_ents;
-    const bool su = in->surround_target != nullptr;
-    if(su) {
-        for(size_t i = (size_t)b; i < (size_t)e; i++) {
-            if(in->surround_target[i] >= w->n_ents) return NAVHIP_ERR_INVALID;
-            if(w->state[i] == NAVHIP_STATE_SURROUND_ENTITY && in->surround_target[i] >= -1 && w->flock[i] >= w->n_flocks) return NAVHIP_ERR_INVALID;
-        }
-    }
-    size_t n_rt = 0;
-    if(in->range_target) {
-        const int rows = in->n_range_rows;
-        for(int r = 0; r < rows; r++)
-            if(in->range_tiles_off[r] < 0 || in->range_tiles_off[r + 1] < in->range_tiles_off[r]) return NAVHIP_ERR_INVALID;
-        n_rt = rows ? (size_t)in->range_tiles_off[rows] : 0;
-        for(size_t i = (size_t)b; i < (size_t)e; i++) {
-            if(in->range_target[i] >= w->n_ents) return NAVHIP_ERR_INVALID;
-            if(in->range_target[i] >= 0 && w->state[i] == NAVHIP_STATE_ENTER_ENTITY_RANGE
-            && (in->range_tiles_row[i] < 0 || in->range_tiles_row[i] >= rows)) return NAVHIP_ERR_INVALID;
-        }
-    }
+    if(!sk_check_aux(w, in, SK_AUX_ALONE) || !sk_work_range(w, &b, &e)) return NAVHIP_ERR_INVALID;
+    sk_dims D = sk_dims_of(w, b, e);
+    if(!sk_check_arm_rows(in, w->n_ents, w, (size_t)b, (size_t)e, &D)) return NAVHIP_ERR_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    sk_arena A;
-    const size_t o_rad = A.take(n * 4), o_fl = A.take(n * 4), o_st = A.take(n), o_fs = A.take(n), o_wt = A.take(n * 4),
-                 o_wp = A.take(n), o_np = A.take(n * 8), o_ios = A.take(n), o_iof = A.take(n), o_ot = A.take(n * 4),
-                 o_er = A.take(in->ent_rot ? n * 16 : 0), o_td = A.take(in->ent_rot ? n * 16 : 0);
-    const bool rg = in->range_target != nullptr;
-    const size_t rows = rg ? (size_t)in->n_range_rows : 0;
-    const size_t o_pos = A.take(rg ? n * 8 : 0), o_rt = A.take(rg ? n * 4 : 0), o_rr = A.take(rg ? n * 4 : 0),
-                 o_rp = A.take(rg ? n * 8 : 0), o_row = A.take(rg ? n * 4 : 0), o_off = A.take(rg ? (rows + 1) * 4 : 0),
-                 o_til = A.take(rg ? n_rt * 4 + 4 : 0);
-    const size_t F = (size_t)(w->n_flocks > 0 ? w->n_flocks : 0);
-    const size_t o_spos = A.take(su && !rg ? n * 8 : 0), o_svel = A.take(su ? n * 8 : 0), o_sflock = A.take(su ? n * 4 : 0),
-                 o_sftgt = A.take(su ? F * 8 + 8 : 0), o_stgt = A.take(su ? n * 4 : 0), o_sq = A.take(su ? n : 0),
-                 o_stp = A.take(su ? n * 8 : 0), o_snp = A.take(su ? n * 8 : 0), o_sd = A.take(su ? n * 16 : 0),
-                 o_svd = A.take(su ? n * 8 : 0), o_sout = A.take(su ? n * 8 : 0);
-    char *base;
-    int rc = nh_stage_reserve(ctx, NH_STAGE_STATE_ARENA, A.total, (void**)&base);
+    const size_t n = (size_t)w->n_ents;
+    sk_plan P;
+    navhip_world d = sk_device_world(w);
+    navhip_state_aux_in di = {};
+    if(D.on[SK_RANGE]) di.n_range_rows = in->n_range_rows;
+    sk_stage_world(P, w, &d, D, {SK_W(radius), SK_W(flags), SK_W(state)});
+    // (only the enter-range and surround arms read positions)
+    if(D.on[SK_RANGE] || D.on[SK_SURROUND]) sk_stage_world(P, w, &d, D, {SK_W(pos_xz)});
+    if(D.on[SK_SURROUND]) {
+        sk_stage_world(P, w, &d, D, {SK_W(vel_xz), SK_W(flock)});
+        sk_stage_world(P, w, &d, D, {SK_W(flock_target_xz)}, 0, 8);
+    }
+    sk_stage(P, sk_aux_rows, in, &di, D);
+    uint8_t *d_state, *d_flags; int32_t *d_ticks;
+    P.out(P.in(io_state, n, 0, (void**)&d_state), io_state, 1, D.lo, D.cnt);
+    P.out(P.in(io_flags, n, 0, (void**)&d_flags), io_flags, 1, D.lo, D.cnt);
+    P.out(P.scratch(n * 4, (void**)&d_ticks), out_ticks, 4, D.lo, D.cnt);
+    int rc = P.reserve(ctx, NH_STAGE_STATE_ARENA);
+    if(!rc) rc = P.upload(ctx, s);
+    if(!rc) rc = navhip_state_update_aux_dev(ctx, &d, &di, d_state, d_flags, d_ticks, s);
+    if(!rc) rc = P.download(ctx, s);
+    return rc;
+}
+
+// gate -> state update on the gate's positions -> aux (da != NULL) -> the rows the gate leaves to the host; r: the device
+// twins of the results.  units / ns / listed_dest: sparse rows with a surround arm, whose positions go back per listed unit.
+static int sk_run_passes(navhip_ctx *ctx, const navhip_world *d, int b, int e, const navhip_gate_in &dg, navhip_state_in ds,
+                         navhip_state_aux_in *da, const navhip_state_pass_out &r, const int32_t *units, size_t ns,
+                         float *listed_dest, hipStream_t s)
+{
+    int rc = navhip_heading_gate_dev(ctx, d, &dg, r.vel_xz, r.new_pos_xz, r.gate, s);
     if(rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(base + o_rad, w->radius, n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(base + o_fl, w->flags, n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(base + o_st, w->state, n, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(base + o_fs, in->fstate, n, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(base + o_wt, in->wait_ticks_left, n * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(base + o_wp, in->wait_prev, n, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(base + o_np, in->new_pos_xz, n * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(base + o_ios, io_state, n, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(base + o_iof, io_flags, n, hipMemcpyHostToDevice, s));
-    navhip_world d = *w;
-    d.radius = (const float*)(base + o_rad); d.flags = (const uint32_t*)(base + o_fl); d.state = (const uint8_t*)(base + o_st);
-    d.pos_xz = nullptr;                          // (only the enter-range arm reads positions: staged below with its inputs)
-    navhip_state_aux_in di;
-    memset(&di, 0, sizeof(di));
-    di.fstate = (const uint8_t*)(base + o_fs); di.wait_ticks_left = (const int32_t*)(base + o_wt);
-    di.wait_prev = (const uint8_t*)(base + o_wp); di.new_pos_xz = (const float*)(base + o_np);
-    if(rg) {
-        HIPCHK(ctx, hipMemcpyAsync(base + o_pos, w->pos_xz, n * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(base + o_rt, in->range_target, n * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(base + o_rr, in->target_range, n * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(base + o_rp, in->target_prev_xz, n * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(base + o_row, in->range_tiles_row, n * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(base + o_off, in->range_tiles_off, (rows + 1) * 4, hipMemcpyHostToDevice, s));
-        if(n_rt) HIPCHK(ctx, hipMemcpyAsync(base + o_til, in->range_tiles, n_rt * 4, hipMemcpyHostToDevice, s));
-        d.pos_xz = (const float*)(base + o_pos);
-        di.range_target = (const int32_t*)(base + o_rt); di.target_range = (const float*)(base + o_rr);
-        di.target_prev_xz = (const float*)(base + o_rp); di.range_tiles_row = (const int32_t*)(base + o_row);
-        di.range_tiles_off = (const int32_t*)(base + o_off); di.range_tiles = (const int16_t*)(base + o_til);
-        di.n_range_rows = in->n_range_rows;
-    }
-    if(in->ent_rot) {
-        HIPCHK(ctx, hipMemcpyAsync(base + o_er, in->ent_rot, n * 16, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(base + o_td, in->target_dir, n * 16, hipMemcpyHostToDevice, s));
-        di.ent_rot = (const float*)(base + o_er); di.target_dir = (const float*)(base + o_td);
-    }
-    if(su) {
-        if(!rg) { HIPCHK(ctx, hipMemcpyAsync(base + o_spos, w->pos_xz, n * 8, hipMemcpyHostToDevice, s)); d.pos_xz = (const float*)(base + o_spos); }
-        HIPCHK(ctx, hipMemcpyAsync(base + o_svel, w->vel_xz, n * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(base + o_sflock, w->flock, n * 4, hipMemcpyHostToDevice, s));
-        if(F) HIPCHK(ctx, hipMemcpyAsync(base + o_sftgt, w->flock_target_xz, F * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(base + o_stgt, in->surround_target, n * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(base + o_sq, in->surround_query, n, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(base + o_stp, in->surround_target_prev_xz, n * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(base + o_snp, in->surround_nearest_prev_xz, n * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(base + o_sd, in->surround_dest_xz, n * 16, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(base + o_svd, in->vdes_xz, n * 8, hipMemcpyHostToDevice, s));
-        d.vel_xz = (const float*)(base + o_svel); d.flock = (const int32_t*)(base + o_sflock);
-        d.flock_target_xz = (const float*)(base + o_sftgt);
-        di.surround_target = (const int32_t*)(base + o_stgt); di.surround_query = (const uint8_t*)(base + o_sq);
-        di.surround_target_prev_xz = (const float*)(base + o_stp); di.surround_nearest_prev_xz = (const float*)(base + o_snp);
-        di.surround_dest_xz = (const float*)(base + o_sd); di.vdes_xz = (const float*)(base + o_svd);
-        di.out_surround_dest_xz = (float*)(base + o_sout);
-    }
-    rc = navhip_state_update_aux_dev(ctx, &d, &di, (uint8_t*)(base + o_ios), (uint8_t*)(base + o_iof), (int32_t*)(base + o_ot), s);
+    ds.new_pos_xz = r.new_pos_xz; ds.vdes_xz = dg.vdes_xz;
+    rc = navhip_state_update_dev(ctx, d, &ds, r.state, r.flags, s);
     if(rc) return rc;
+    if(da) {
+        da->new_pos_xz = r.new_pos_xz;
+        if(da->surround_target) da->vdes_xz = dg.vdes_xz;
+        rc = navhip_state_update_aux_dev(ctx, d, da, r.state, r.flags, r.wait_ticks_left, s);
+        if(rc) return rc;
+    }
     if(e > b) {
-        const size_t lo = (size_t)b, cnt = (size_t)(e - b);
-        if(su) HIPCHK(ctx, hipMemcpyAsync(in->out_surround_dest_xz + 2 * lo, base + o_sout + 8 * lo, cnt * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipMemcpyAsync(io_state + lo, base + o_ios + lo, cnt, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipMemcpyAsync(io_flags + lo, base + o_iof + lo, cnt, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipMemcpyAsync(out_ticks + lo, base + o_ot + 4 * lo, cnt * 4, hipMemcpyDeviceToHost, s));
+        hipLaunchKernelGGL(k_gate_host_rows, dim3((e - b + 255) / 256), dim3(256), 0, s, b, e, (const uint8_t*)r.gate, d->state,
+                           da ? da->wait_ticks_left : (const int32_t*)nullptr, r.state, r.flags, r.wait_ticks_left);
+        HIPCHK(ctx, hipGetLastError());
+        if(units && ns) {
+            hipLaunchKernelGGL(k_sparse_gather2, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, s, (int)ns, units,
+                               (const float*)da->out_surround_dest_xz, listed_dest);
+            HIPCHK(ctx, hipGetLastError());
+        }
     }
-    HIPCHK(ctx, hipStreamSynchronize(s));
     return NAVHIP_OK;
 }
 
@@ -744,134 +938,38 @@ int navhip_state_pass(navhip_ctx *ctx, const navhip_world *w, const navhip_state
     const navhip_gate_in &G = in->gate;
     const navhip_state_in &T = in->state;
     const navhip_state_aux_in &X = in->aux;
-    const bool aux = X.fstate != nullptr, turn = aux && X.ent_rot != nullptr, rg = aux && X.range_target != nullptr;
-    const bool su = aux && X.surround_target != nullptr, ip = G.interp_from_xz != nullptr;
-    const size_t n = (size_t)w->n_ents, F = (size_t)w->n_flocks;
-    if(!w->pos_xz || !w->vel_xz || !w->radius || !w->flags || !w->state || !w->flock || !G.next_rot || !G.new_vel_xz || !G.vdes_xz
-    || !out->state || !out->flags || !out->gate || !out->new_pos_xz
-    || (F > 0 && (!w->flock_target_xz || !w->flock_offsets || !w->flock_members || !T.flock_layer || !T.flock_nearest_xz
-                  || !T.flock_tiles_off || !T.flock_tiles))
-    || (aux && (!X.wait_ticks_left || !X.wait_prev || !out->wait_ticks_left || (X.ent_rot != nullptr) != (X.target_dir != nullptr)
-                || !sk_range_inputs_ok(w, &X) || !sk_no_sparse(&X)))
-    || !sk_interp_inputs_ok(w, &G))
-        return NAVHIP_ERR_INVALID;
-    if(su) {
-        // (the pass supplies vdes and the snapshot arrays itself: the caller gives the five query arrays and the output)
-        if(!X.surround_query || !X.surround_target_prev_xz || !X.surround_nearest_prev_xz || !X.surround_dest_xz
-        || !X.out_surround_dest_xz) return NAVHIP_ERR_INVALID;
-    }
+    const bool aux = X.fstate != nullptr;
     int b, e;
-    if(!sk_work_range(w, &b, &e)) return NAVHIP_ERR_INVALID;
-    if(su) {
-        for(size_t i = (size_t)b; i < (size_t)e; i++) {
-            if(X.surround_target[i] >= w->n_ents) return NAVHIP_ERR_INVALID;
-            if(w->state[i] == NAVHIP_STATE_SURROUND_ENTITY && X.surround_target[i] >= -1 && w->flock[i] >= w->n_flocks) return NAVHIP_ERR_INVALID;
-        }
-    }
+    // (a negative flock count never got past the offsets below)
+    if(w->n_flocks < 0 || !sk_check_gate(w, &G) || !sk_check_state(w, &T) || (aux && !sk_check_aux(w, &X, SK_PASS))
+    || !out->state || !out->flags || !out->gate || !out->new_pos_xz || (aux && !out->wait_ticks_left) || !sk_work_range(w, &b, &e))
+        return NAVHIP_ERR_INVALID;
+    sk_dims D = sk_dims_of(w, b, e);
+    const size_t n = (size_t)w->n_ents, F = D.len[SK_PER_FLOCK];
     // (offsets that are not a CSR become a huge size_t below -- INVALID, not NOMEM)
-    for(size_t f = 0; f < F; f++)
-        if(w->flock_offsets[f] < 0 || w->flock_offsets[f + 1] < w->flock_offsets[f] || T.flock_tiles_off[f] < 0
-        || T.flock_tiles_off[f + 1] < T.flock_tiles_off[f]) return NAVHIP_ERR_INVALID;
-    if(F && (size_t)w->flock_offsets[F] > n) return NAVHIP_ERR_INVALID;
-    const size_t nmembers = F ? (size_t)w->flock_offsets[F] : 0, ntiles = F ? (size_t)T.flock_tiles_off[F] : 0;
-    size_t rows = 0, n_rt = 0;
-    if(rg) {
-        rows = (size_t)X.n_range_rows;
-        for(size_t r = 0; r < rows; r++)
-            if(X.range_tiles_off[r] < 0 || X.range_tiles_off[r + 1] < X.range_tiles_off[r]) return NAVHIP_ERR_INVALID;
-        n_rt = rows ? (size_t)X.range_tiles_off[rows] : 0;
-        for(size_t i = (size_t)b; i < (size_t)e; i++) {
-            if(X.range_target[i] >= w->n_ents) return NAVHIP_ERR_INVALID;
-            if(X.range_target[i] >= 0 && w->state[i] == NAVHIP_STATE_ENTER_ENTITY_RANGE
-            && (X.range_tiles_row[i] < 0 || (size_t)X.range_tiles_row[i] >= rows)) return NAVHIP_ERR_INVALID;
-        }
-    }
+    if(!sk_csr_ok(w->flock_offsets, F) || !sk_csr_ok(T.flock_tiles_off, F) || (F && (size_t)w->flock_offsets[F] > n)
+    || (aux && !sk_check_arm_rows(&X, w->n_ents, w, (size_t)b, (size_t)e, &D))) return NAVHIP_ERR_INVALID;
+    D.len[SK_PER_TILE] = F ? (size_t)T.flock_tiles_off[F] : 0;
+    D.on[SK_SKIP] = T.skip != nullptr; D.on[SK_INTERP] = G.interp_from_xz != nullptr; D.on[SK_AUX] = aux;
+    D.pad = 8;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    sk_arena A;
-    struct up { size_t off; const void *src; size_t bytes; };
-    std::vector<up> ups;
-    auto stage = [&](const void *src, size_t bytes) { const size_t o = A.take(bytes + 8); if(src && bytes) ups.push_back({o, src, bytes}); return o; };
+    sk_plan P;
+    navhip_world d = sk_device_world(w);
+    navhip_gate_in dg = {}; navhip_state_in ds = {}; navhip_state_aux_in da = {}; navhip_state_pass_out r = {};
+    if(D.on[SK_RANGE]) da.n_range_rows = X.n_range_rows;
     // the snapshot, once
-    const size_t o_pos = stage(w->pos_xz, n * 8), o_vel = stage(w->vel_xz, n * 8), o_rad = stage(w->radius, n * 4),
-                 o_flg = stage(w->flags, n * 4), o_st = stage(w->state, n), o_flock = stage(w->flock, n * 4),
-                 o_ftgt = stage(w->flock_target_xz, F * 8), o_foff = stage(w->flock_offsets, (F + 1) * 4),
-                 o_fmem = stage(w->flock_members, nmembers * 4);
-    const size_t o_rot = stage(G.next_rot, n * 16), o_nv = stage(G.new_vel_xz, n * 8), o_vd = stage(G.vdes_xz, n * 8);
-    const size_t o_skip = stage(T.skip, T.skip ? n : 0), o_flay = stage(T.flock_layer, F), o_fnear = stage(T.flock_nearest_xz, F * 8),
-                 o_toff = stage(T.flock_tiles_off, (F + 1) * 4), o_tiles = stage(T.flock_tiles, ntiles * 4);
-    const size_t o_fs = stage(X.fstate, aux ? n : 0), o_wt = stage(X.wait_ticks_left, aux ? n * 4 : 0), o_wp = stage(X.wait_prev, aux ? n : 0),
-                 o_er = stage(X.ent_rot, turn ? n * 16 : 0), o_td = stage(X.target_dir, turn ? n * 16 : 0),
-                 o_rt = stage(X.range_target, rg ? n * 4 : 0), o_rr = stage(X.target_range, rg ? n * 4 : 0),
-                 o_rp = stage(X.target_prev_xz, rg ? n * 8 : 0), o_row = stage(X.range_tiles_row, rg ? n * 4 : 0),
-                 o_roff = stage(X.range_tiles_off, rg ? (rows + 1) * 4 : 0), o_rtil = stage(X.range_tiles, rg ? n_rt * 4 : 0);
-    const size_t o_if = stage(G.interp_from_xz, ip ? n * 8 : 0), o_is = stage(G.interp_step, ip ? n * 4 : 0);
-    const size_t o_stgt = stage(X.surround_target, su ? n * 4 : 0), o_sq = stage(X.surround_query, su ? n : 0),
-                 o_stp = stage(X.surround_target_prev_xz, su ? n * 8 : 0), o_snp = stage(X.surround_nearest_prev_xz, su ? n * 8 : 0),
-                 o_sd = stage(X.surround_dest_xz, su ? n * 16 : 0);
-    const size_t r_sd = A.take(su ? n * 8 : 0);
-    // results
-    const size_t r_vel = A.take(n * 8), r_np = A.take(n * 8), r_gate = A.take(n), r_st = A.take(n), r_fl = A.take(n), r_tk = A.take(n * 4);
-    char *base;
-    int rc = nh_stage_reserve(ctx, NH_STAGE_STATE_ARENA, A.total, (void**)&base);
-    if(rc) return rc;
-    for(const up &u : ups) HIPCHK(ctx, hipMemcpyAsync(base + u.off, u.src, u.bytes, hipMemcpyHostToDevice, s));
-    navhip_world d = *w;
-    d.pos_xz = (const float*)(base + o_pos); d.vel_xz = (const float*)(base + o_vel); d.radius = (const float*)(base + o_rad);
-    d.flags = (const uint32_t*)(base + o_flg); d.state = (const uint8_t*)(base + o_st); d.flock = (const int32_t*)(base + o_flock);
-    d.flock_target_xz = (const float*)(base + o_ftgt); d.flock_offsets = (const int32_t*)(base + o_foff);
-    d.flock_members = (const int32_t*)(base + o_fmem);
-    // (nothing else of the world is read by the three passes; what is not staged must not travel as a host pointer)
-    d.max_speed = d.speed = nullptr; d.has_dest_los = nullptr; d.vdes_xz = nullptr; d.flock_field_slot = nullptr; d.field_pool = nullptr;
-    d.form_ready = nullptr; d.cell_pos_xz = d.form_cohesion_xz = d.form_align_xz = d.form_drag_xz = nullptr;
-    d.arrival_sink_xz = nullptr; d.arrival_flags = nullptr; d.los_pool = nullptr; d.flock_los_slot = nullptr; d.los_pos_xz = nullptr;
-    d.region_row = nullptr; d.region_field_slot = nullptr;
-    navhip_gate_in dg = {(const float*)(base + o_rot), (const float*)(base + o_nv), (const float*)(base + o_vd),
-                         ip ? (const float*)(base + o_if) : nullptr, ip ? (const float*)(base + o_is) : nullptr};
-    rc = navhip_heading_gate_dev(ctx, &d, &dg, (float*)(base + r_vel), (float*)(base + r_np), (uint8_t*)(base + r_gate), s);
-    if(rc) return rc;
-    navhip_state_in ds = {(const float*)(base + r_np), (const float*)(base + o_vd), T.skip ? (const uint8_t*)(base + o_skip) : nullptr,
-                          (const uint8_t*)(base + o_flay), (const float*)(base + o_fnear), (const int32_t*)(base + o_toff),
-                          (const int16_t*)(base + o_tiles)};
-    rc = navhip_state_update_dev(ctx, &d, &ds, (uint8_t*)(base + r_st), (uint8_t*)(base + r_fl), s);
-    if(rc) return rc;
-    if(aux) {
-        navhip_state_aux_in da;
-        memset(&da, 0, sizeof(da));
-        da.fstate = (const uint8_t*)(base + o_fs); da.wait_ticks_left = (const int32_t*)(base + o_wt);
-        da.wait_prev = (const uint8_t*)(base + o_wp); da.new_pos_xz = (const float*)(base + r_np);
-        if(turn) { da.ent_rot = (const float*)(base + o_er); da.target_dir = (const float*)(base + o_td); }
-        if(rg) {
-            da.range_target = (const int32_t*)(base + o_rt); da.target_range = (const float*)(base + o_rr);
-            da.target_prev_xz = (const float*)(base + o_rp); da.range_tiles_row = (const int32_t*)(base + o_row);
-            da.range_tiles_off = (const int32_t*)(base + o_roff); da.range_tiles = (const int16_t*)(base + o_rtil);
-            da.n_range_rows = X.n_range_rows;
-        }
-        if(su) {
-            da.surround_target = (const int32_t*)(base + o_stgt); da.surround_query = (const uint8_t*)(base + o_sq);
-            da.surround_target_prev_xz = (const float*)(base + o_stp); da.surround_nearest_prev_xz = (const float*)(base + o_snp);
-            da.surround_dest_xz = (const float*)(base + o_sd); da.vdes_xz = (const float*)(base + o_vd);
-            da.out_surround_dest_xz = (float*)(base + r_sd);
-        }
-        rc = navhip_state_update_aux_dev(ctx, &d, &da, (uint8_t*)(base + r_st), (uint8_t*)(base + r_fl), (int32_t*)(base + r_tk), s);
-        if(rc) return rc;
-    }
-    if(e > b) {
-        hipLaunchKernelGGL(k_gate_host_rows, dim3((e - b + 255) / 256), dim3(256), 0, s, b, e, (const uint8_t*)(base + r_gate),
-                           (const uint8_t*)(base + o_st), aux ? (const int32_t*)(base + o_wt) : (const int32_t*)nullptr,
-                           (uint8_t*)(base + r_st), (uint8_t*)(base + r_fl), aux ? (int32_t*)(base + r_tk) : (int32_t*)nullptr);
-        HIPCHK(ctx, hipGetLastError());
-        const size_t lo = (size_t)b, cnt = (size_t)(e - b);
-        HIPCHK(ctx, hipMemcpyAsync(out->state + lo, base + r_st + lo, cnt, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipMemcpyAsync(out->flags + lo, base + r_fl + lo, cnt, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipMemcpyAsync(out->gate + lo, base + r_gate + lo, cnt, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipMemcpyAsync(out->new_pos_xz + 2 * lo, base + r_np + 8 * lo, cnt * 8, hipMemcpyDeviceToHost, s));
-        if(out->vel_xz) HIPCHK(ctx, hipMemcpyAsync(out->vel_xz + 2 * lo, base + r_vel + 8 * lo, cnt * 8, hipMemcpyDeviceToHost, s));
-        if(aux) HIPCHK(ctx, hipMemcpyAsync(out->wait_ticks_left + lo, base + r_tk + 4 * lo, cnt * 4, hipMemcpyDeviceToHost, s));
-        if(su) HIPCHK(ctx, hipMemcpyAsync(X.out_surround_dest_xz + 2 * lo, base + r_sd + 8 * lo, cnt * 8, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return NAVHIP_OK;
+    sk_stage_world(P, w, &d, D, {SK_W(pos_xz), SK_W(vel_xz), SK_W(radius), SK_W(flags), SK_W(state), SK_W(flock), SK_W(flock_target_xz),
+                                 SK_W(flock_offsets), SK_W(flock_members)}, F ? (size_t)w->flock_offsets[F] : 0);
+    sk_stage(P, sk_gate_rows, &G, &dg, D);
+    sk_stage(P, sk_state_rows, &T, &ds, D, {offsetof(navhip_state_in, new_pos_xz), offsetof(navhip_state_in, vdes_xz)});
+    if(aux) sk_stage(P, sk_aux_rows, &X, &da, D, {offsetof(navhip_state_aux_in, new_pos_xz), offsetof(navhip_state_aux_in, vdes_xz)});
+    sk_stage(P, sk_pass_out_rows, out, &r, D);
+    int rc = P.reserve(ctx, NH_STAGE_STATE_ARENA);
+    if(!rc) rc = P.upload(ctx, s);
+    if(!rc) rc = sk_run_passes(ctx, &d, b, e, dg, ds, aux ? &da : nullptr, r, nullptr, 0, nullptr, s);
+    if(!rc) rc = P.download(ctx, s);
+    return rc;
 }
 
 int navhip_state_pass_resident(navhip_ctx *ctx, const navhip_state_pass_in *in, const navhip_state_pass_out *out)
@@ -882,216 +980,93 @@ int navhip_state_pass_resident(navhip_ctx *ctx, const navhip_state_pass_in *in, 
         ctx->last_error = "navhip_state_pass_resident: no completed host-buffer step is resident on the device";
         return NAVHIP_ERR_INVALID;
     }
-    const navhip_gate_in &G = in->gate;
     const navhip_state_in &T = in->state;
     const navhip_state_aux_in &X = in->aux;
-    const bool aux = X.fstate != nullptr, turn = aux && X.ent_rot != nullptr, rg = aux && X.range_target != nullptr;
-    const bool su = aux && X.surround_target != nullptr, ip = G.interp_from_xz != nullptr;
-    const size_t n = (size_t)d.n_ents, F = (size_t)(d.n_flocks > 0 ? d.n_flocks : 0);
+    const bool aux = X.fstate != nullptr, su = aux && X.surround_target != nullptr;
+    const size_t n = (size_t)d.n_ents;
     if(n == 0) return NAVHIP_OK;
-    if(!d.pos_xz || !d.vel_xz || !d.radius || !d.flags || !d.state || !d.flock || !so.vel_xz || (!so.vdes_xz && !d.vdes_xz) || !G.next_rot
-    || !out->state || !out->flags || !out->gate || !out->new_pos_xz
-    || (F > 0 && (!d.flock_target_xz || !d.flock_offsets || !d.flock_members || !T.flock_layer || !T.flock_nearest_xz
-                  || !T.flock_tiles_off || !T.flock_tiles))
-    || (aux && (!X.wait_ticks_left || !X.wait_prev || !out->wait_ticks_left || (X.ent_rot != nullptr) != (X.target_dir != nullptr)))
-    || (ip && !G.interp_step) || (!ip && G.interp_step)
-    || (su && (!X.surround_query || !X.surround_target_prev_xz || !X.surround_nearest_prev_xz || !X.surround_dest_xz || !X.out_surround_dest_xz)))
-        return NAVHIP_ERR_INVALID;
-    if(rg) {
-        const int given = (X.target_range != nullptr) + (X.target_prev_xz != nullptr) + (X.range_tiles_row != nullptr)
-                        + (X.range_tiles_off != nullptr) + (X.range_tiles != nullptr);
-        if(given != 5 || X.n_range_rows < 0) return NAVHIP_ERR_INVALID;
-    }
+    navhip_gate_in G = in->gate;                                // (its new_vel_xz and vdes_xz are the step's own outputs)
+    G.new_vel_xz = so.vel_xz; G.vdes_xz = so.vdes_xz ? so.vdes_xz : d.vdes_xz;
     int b, e;
-    if(!sk_work_range(&d, &b, &e)) return NAVHIP_ERR_INVALID;
+    if(!sk_check_gate(&d, &G) || !sk_check_state(&d, &T) || (aux && !sk_check_aux(&d, &X, SK_PASS_RESIDENT))
+    || !out->state || !out->flags || !out->gate || !out->new_pos_xz || (aux && !out->wait_ticks_left) || !sk_work_range(&d, &b, &e))
+        return NAVHIP_ERR_INVALID;
     // sparse rows: the arrays of the three arms hold a row per LISTED unit (ns of them), the device lays them out
     const bool sp = aux && X.sparse_units != nullptr;
     if((X.sparse_units == nullptr && X.n_sparse != 0) || X.n_sparse < 0 || (X.sparse_units && !aux)) return NAVHIP_ERR_INVALID;
     const size_t ns = sp ? (size_t)X.n_sparse : 0;
-    const size_t nr = sp ? ns : n;                              // rows of an arm array
-    const size_t v0 = sp ? 0 : (size_t)b, v1 = sp ? ns : (size_t)e;   // ... and those the checks below walk
     for(size_t k = 0; k < ns; k++)
         if(X.sparse_units[k] < b || X.sparse_units[k] >= e) return NAVHIP_ERR_INVALID;
-    for(size_t f = 0; f < F; f++)
-        if(T.flock_tiles_off[f] < 0 || T.flock_tiles_off[f + 1] < T.flock_tiles_off[f]) return NAVHIP_ERR_INVALID;
-    const size_t ntiles = F ? (size_t)T.flock_tiles_off[F] : 0;
-    size_t rows = 0, n_rt = 0;
-    if(rg) {
-        rows = (size_t)X.n_range_rows;
-        for(size_t r = 0; r < rows; r++)
-            if(X.range_tiles_off[r] < 0 || X.range_tiles_off[r + 1] < X.range_tiles_off[r]) return NAVHIP_ERR_INVALID;
-        n_rt = rows ? (size_t)X.range_tiles_off[rows] : 0;
-        for(size_t i = v0; i < v1; i++)
-            if(X.range_target[i] >= d.n_ents
-            || (X.range_target[i] >= 0 && (X.range_tiles_row[i] < 0 || (size_t)X.range_tiles_row[i] >= (rows ? rows : 1)))) return NAVHIP_ERR_INVALID;
-    }
-    if(su)
-        for(size_t i = v0; i < v1; i++)
-            if(X.surround_target[i] >= d.n_ents) return NAVHIP_ERR_INVALID;
+    sk_dims D = sk_dims_of(&d, b, e);
+    const size_t F = D.len[SK_PER_FLOCK];
+    // (the checks of the arms walk the rows of their arrays: the listed units', or the slab's)
+    if(!sk_csr_ok(T.flock_tiles_off, F)
+    || (aux && !sk_check_arm_rows(&X, d.n_ents, nullptr, sp ? 0 : (size_t)b, sp ? ns : (size_t)e, &D))) return NAVHIP_ERR_INVALID;
+    D.len[SK_PER_TILE] = F ? (size_t)T.flock_tiles_off[F] : 0;
+    D.on[SK_SKIP] = T.skip != nullptr; D.on[SK_INTERP] = G.interp_from_xz != nullptr; D.on[SK_AUX] = aux; D.on[SK_SPARSE] = sp;
+    D.pad = 8;
+    if(sp) { D.len[SK_PER_ARM_ROW] = ns; D.len[SK_PER_LISTED] = ns; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     // ---- inputs: one device slab; pageable arrays are packed into the pinned slab and cross the bus as ONE transfer,
-    // pinned ones (navhip_host_alloc) are transferred in place
-    struct item { const void *src; size_t bytes; size_t off; bool pinned; };
-    std::vector<item> items;
-    sk_arena A;
-    auto stage = [&](const void *src, size_t bytes) { const size_t o = A.take(bytes + 8); if(src && bytes) items.push_back({src, bytes, o, nh_is_pinned(src)}); return o; };
-    const size_t o_rot = stage(G.next_rot, n * 16), o_if = stage(G.interp_from_xz, ip ? n * 8 : 0), o_is = stage(G.interp_step, ip ? n * 4 : 0);
-    const size_t o_skip = stage(T.skip, T.skip ? n : 0), o_flay = stage(T.flock_layer, F), o_fnear = stage(T.flock_nearest_xz, F * 8),
-                 o_toff = stage(T.flock_tiles_off, (F + 1) * 4), o_tiles = stage(T.flock_tiles, ntiles * 4);
-    const size_t o_fs = stage(X.fstate, aux ? n : 0), o_wt = stage(X.wait_ticks_left, aux ? n * 4 : 0), o_wp = stage(X.wait_prev, aux ? n : 0),
-                 o_er = stage(X.ent_rot, turn ? nr * 16 : 0), o_td = stage(X.target_dir, turn ? nr * 16 : 0),
-                 o_rt = stage(X.range_target, rg ? nr * 4 : 0), o_rr = stage(X.target_range, rg ? nr * 4 : 0),
-                 o_rp = stage(X.target_prev_xz, rg ? nr * 8 : 0), o_row = stage(X.range_tiles_row, rg ? nr * 4 : 0),
-                 o_roff = stage(X.range_tiles_off, rg ? (rows + 1) * 4 : 0), o_rtil = stage(X.range_tiles, rg ? n_rt * 4 : 0),
-                 o_stgt = stage(X.surround_target, su ? nr * 4 : 0), o_sq = stage(X.surround_query, su ? nr : 0),
-                 o_stp = stage(X.surround_target_prev_xz, su ? nr * 8 : 0), o_snp = stage(X.surround_nearest_prev_xz, su ? nr * 8 : 0),
-                 o_sd = stage(X.surround_dest_xz, su ? nr * 16 : 0), o_units = stage(X.sparse_units, ns * 4);
+    // pinned ones (navhip_host_alloc) are transferred in place.  Results: rows [b, e) of each, likewise
+    sk_plan I, R;
+    navhip_gate_in dg = {}; navhip_state_in ds = {}; navhip_state_aux_in da = {}, dense = {}; navhip_state_pass_out r = {};
+    if(D.on[SK_RANGE]) da.n_range_rows = X.n_range_rows;
+    sk_stage(I, sk_gate_rows, &G, &dg, D, {offsetof(navhip_gate_in, new_vel_xz), offsetof(navhip_gate_in, vdes_xz)});
+    sk_stage(I, sk_state_rows, &T, &ds, D, {offsetof(navhip_state_in, new_pos_xz), offsetof(navhip_state_in, vdes_xz)});
+    if(aux) sk_stage(I, sk_aux_rows, &X, &da, D, {offsetof(navhip_state_aux_in, new_pos_xz), offsetof(navhip_state_aux_in, vdes_xz),
+                                                  offsetof(navhip_state_aux_in, out_surround_dest_xz)});
     // (sparse: the dense twins the arm kernels read, filled on the device)
-    const size_t e_er = A.take(sp && turn ? n * 16 : 0), e_td = A.take(sp && turn ? n * 16 : 0),
-                 e_rt = A.take(sp && rg ? n * 4 : 0), e_rr = A.take(sp && rg ? n * 4 : 0), e_rp = A.take(sp && rg ? n * 8 : 0),
-                 e_row = A.take(sp && rg ? n * 4 : 0), e_stgt = A.take(sp && su ? n * 4 : 0), e_sq = A.take(sp && su ? n : 0),
-                 e_stp = A.take(sp && su ? n * 8 : 0), e_snp = A.take(sp && su ? n * 8 : 0), e_sd = A.take(sp && su ? n * 16 : 0);
-    const size_t in_total = A.total;
-    // ---- results: rows [b, e) of each, one device slab, one transfer for the pageable destinations
-    const size_t cnt = (size_t)(e - b), lo = (size_t)b;
-    sk_arena R;
-    const size_t r_vel = R.take(n * 8), r_np = R.take(n * 8), r_gate = R.take(n), r_st = R.take(n), r_fl = R.take(n),
-                 r_tk = R.take(aux ? n * 4 : 0), r_sd = R.take(su ? n * 8 : 0), r_vd = R.take(n * 8),
-                 r_sdk = R.take(sp && su ? ns * 8 : 0);           // (sparse: the surround positions of the listed units)
-    size_t pack_in = 0;
-    for(auto &it : items) if(!it.pinned) pack_in += (it.bytes + 255) & ~(size_t)255;
-    struct oitem { void *dst; size_t dev_off, row; size_t h_off; bool pinned; size_t lo, cnt; };     // rows [lo, lo + cnt) travel
-    std::vector<oitem> outs = {{out->state, r_st, 1, 0, false, lo, cnt}, {out->flags, r_fl, 1, 0, false, lo, cnt},
-                               {out->gate, r_gate, 1, 0, false, lo, cnt}, {out->new_pos_xz, r_np, 8, 0, false, lo, cnt}};
-    if(out->vel_xz) outs.push_back({out->vel_xz, r_vel, 8, 0, false, lo, cnt});
-    if(aux) outs.push_back({out->wait_ticks_left, r_tk, 4, 0, false, lo, cnt});
-    if(su && !sp) outs.push_back({X.out_surround_dest_xz, r_sd, 8, 0, false, lo, cnt});
-    if(su && sp && ns) outs.push_back({X.out_surround_dest_xz, r_sdk, 8, 0, false, 0, ns});
-    size_t pack_out = 0;
-    for(auto &o : outs) { o.pinned = nh_is_pinned(o.dst); if(!o.pinned) { o.h_off = pack_out; pack_out += (o.cnt * o.row + 255) & ~(size_t)255; } }
-    char *h_in = nullptr, *h_out = nullptr, *base = nullptr, *res = nullptr;
-    int rc = nh_async_slabs(ctx, pack_in, pack_out, &h_in, &h_out);
-    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_PASS_IN, in_total + pack_in + 256, (void**)&base);
-    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_PASS_OUT, R.total + pack_out + 256, (void**)&res);
+    if(sp) for(const sk_row &t : sk_aux_rows) if(t.len == SK_PER_ARM_ROW && D.on[t.group]) I.scratch(n * t.elem, &nh_member(&dense, t.off));
+    sk_stage(R, sk_pass_out_rows, out, &r, D);
+    float *d_vdes, *d_sdest = nullptr, *d_listed = nullptr;     // (sparse: the surround positions of the listed units)
+    R.scratch(n * 8, (void**)&d_vdes);
+    if(su) { const int k = R.scratch(n * 8, (void**)&d_sdest); if(!sp) R.out(k, X.out_surround_dest_xz, 8, D.lo, D.cnt); }
+    if(su && sp) R.out(R.scratch(ns * 8, (void**)&d_listed), X.out_surround_dest_xz, 8, 0, ns);
+    I.pack(); R.pack();
+    int rc = nh_async_slabs(ctx, I.in_bytes, R.out_bytes, &I.h_in, &R.h_out);
+    if(!rc) rc = I.reserve(ctx, NH_STAGE_PASS_IN);
+    if(!rc) rc = R.reserve(ctx, NH_STAGE_PASS_OUT);
+    if(!rc) rc = I.upload(ctx, s);
     if(rc) return rc;
-    // (the pageable inputs: packed, sent as one block behind the arrays' own region, then laid out by device-to-device
-    // copies?  No: the layout IS the packing order -- every pageable item gets its device address inside the block)
-    char *d_block = base + in_total;
-    size_t poff = 0;
-    std::vector<const char*> dev_of(items.size());
-    for(size_t k = 0; k < items.size(); k++) {
-        item &it = items[k];
-        if(it.pinned) {
-            HIPCHK(ctx, hipMemcpyAsync(base + it.off, it.src, it.bytes, hipMemcpyHostToDevice, s));
-            dev_of[k] = base + it.off;
-        }else{
-            memcpy(h_in + poff, it.src, it.bytes);
-            dev_of[k] = d_block + poff;
-            poff += (it.bytes + 255) & ~(size_t)255;
-        }
-    }
-    if(poff) HIPCHK(ctx, hipMemcpyAsync(d_block, h_in, poff, hipMemcpyHostToDevice, s));
-    auto dev = [&](size_t off) -> const char* {                // the device address of the item staged at arena offset `off`
-        for(size_t k = 0; k < items.size(); k++) if(items[k].off == off) return dev_of[k];
-        return base + off;                                     // (nothing staged there: an address nobody reads)
-    };
     // ---- sparse rows -> the dense arrays of the arms (targets default to "the host's", rotations and queries to zero)
-    const char *a_er = dev(o_er), *a_td = dev(o_td), *a_rt = dev(o_rt), *a_rr = dev(o_rr), *a_rp = dev(o_rp), *a_row = dev(o_row),
-               *a_stgt = dev(o_stgt), *a_sq = dev(o_sq), *a_stp = dev(o_stp), *a_snp = dev(o_snp), *a_sd = dev(o_sd);
+    const int32_t *units = da.sparse_units;
+    da.sparse_units = nullptr;
     if(sp) {
         sk_sparse_rows SR;
         memset(&SR, 0, sizeof(SR));
-        SR.n = (int)ns; SR.units = (const int32_t*)dev(o_units);
-        if(turn) {
-            HIPCHK(ctx, hipMemsetAsync(base + e_er, 0, n * 16, s)); HIPCHK(ctx, hipMemsetAsync(base + e_td, 0, n * 16, s));
-            SR.er = (const float*)a_er; SR.td = (const float*)a_td; SR.d_er = (float*)(base + e_er); SR.d_td = (float*)(base + e_td);
-            a_er = base + e_er; a_td = base + e_td;
+        SR.n = (int)ns; SR.units = units;
+        // (the rows become the kernel's source, their dense twin takes their place in front of the arm kernels)
+#define SK_DENSE(member, rows_, dense_) (SR.rows_ = da.member, SR.dense_ = (decltype(SR.dense_))dense.member, da.member = dense.member)
+        if(D.on[SK_TURN]) {
+            SK_DENSE(ent_rot, er, d_er); SK_DENSE(target_dir, td, d_td);
+            HIPCHK(ctx, hipMemsetAsync(SR.d_er, 0, n * 16, s)); HIPCHK(ctx, hipMemsetAsync(SR.d_td, 0, n * 16, s));
         }
-        if(rg) {
-            HIPCHK(ctx, hipMemsetAsync(base + e_rt, 0xfe, n * 4, s)); HIPCHK(ctx, hipMemsetAsync(base + e_row, 0, n * 4, s));
-            SR.rt = (const int32_t*)a_rt; SR.rr = (const float*)a_rr; SR.rp = (const float*)a_rp; SR.row = (const int32_t*)a_row;
-            SR.d_rt = (int32_t*)(base + e_rt); SR.d_rr = (float*)(base + e_rr); SR.d_rp = (float*)(base + e_rp); SR.d_row = (int32_t*)(base + e_row);
-            a_rt = base + e_rt; a_rr = base + e_rr; a_rp = base + e_rp; a_row = base + e_row;
+        if(D.on[SK_RANGE]) {
+            SK_DENSE(range_target, rt, d_rt); SK_DENSE(target_range, rr, d_rr); SK_DENSE(target_prev_xz, rp, d_rp);
+            SK_DENSE(range_tiles_row, row, d_row);
+            HIPCHK(ctx, hipMemsetAsync(SR.d_rt, 0xfe, n * 4, s)); HIPCHK(ctx, hipMemsetAsync(SR.d_row, 0, n * 4, s));
         }
         if(su) {
-            HIPCHK(ctx, hipMemsetAsync(base + e_stgt, 0xfe, n * 4, s)); HIPCHK(ctx, hipMemsetAsync(base + e_sq, 0, n, s));
-            HIPCHK(ctx, hipMemsetAsync(res + r_sd, 0, n * 8, s));
-            SR.stgt = (const int32_t*)a_stgt; SR.sq = (const uint8_t*)a_sq; SR.stp = (const float*)a_stp; SR.snp = (const float*)a_snp;
-            SR.sd = (const float*)a_sd;
-            SR.d_stgt = (int32_t*)(base + e_stgt); SR.d_sq = (uint8_t*)(base + e_sq); SR.d_stp = (float*)(base + e_stp);
-            SR.d_snp = (float*)(base + e_snp); SR.d_sd = (float*)(base + e_sd);
-            a_stgt = base + e_stgt; a_sq = base + e_sq; a_stp = base + e_stp; a_snp = base + e_snp; a_sd = base + e_sd;
+            SK_DENSE(surround_target, stgt, d_stgt); SK_DENSE(surround_query, sq, d_sq); SK_DENSE(surround_target_prev_xz, stp, d_stp);
+            SK_DENSE(surround_nearest_prev_xz, snp, d_snp); SK_DENSE(surround_dest_xz, sd, d_sd);
+            HIPCHK(ctx, hipMemsetAsync(SR.d_stgt, 0xfe, n * 4, s)); HIPCHK(ctx, hipMemsetAsync(SR.d_sq, 0, n, s));
+            HIPCHK(ctx, hipMemsetAsync(d_sdest, 0, n * 8, s));
         }
+#undef SK_DENSE
         if(ns) {
             hipLaunchKernelGGL(k_sparse_rows, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, s, SR);
             HIPCHK(ctx, hipGetLastError());
         }
     }
     // ---- the three passes on the resident snapshot
-    const float *d_vdes = (const float*)(res + r_vd);
-    if(e > b) hipLaunchKernelGGL(k_pick_vdes, dim3((e - b + 255) / 256), dim3(256), 0, s, b, e, d.vdes_xz, (const float*)so.vdes_xz, (float*)(res + r_vd));
-    navhip_gate_in dg = {(const float*)dev(o_rot), so.vel_xz, d_vdes, ip ? (const float*)dev(o_if) : nullptr, ip ? (const float*)dev(o_is) : nullptr};
-    rc = navhip_heading_gate_dev(ctx, &d, &dg, (float*)(res + r_vel), (float*)(res + r_np), (uint8_t*)(res + r_gate), s);
-    if(rc) return rc;
-    navhip_state_in ds = {(const float*)(res + r_np), d_vdes, T.skip ? (const uint8_t*)dev(o_skip) : nullptr, (const uint8_t*)dev(o_flay),
-                          (const float*)dev(o_fnear), (const int32_t*)dev(o_toff), (const int16_t*)dev(o_tiles)};
-    rc = navhip_state_update_dev(ctx, &d, &ds, (uint8_t*)(res + r_st), (uint8_t*)(res + r_fl), s);
-    if(rc) return rc;
-    if(aux) {
-        navhip_state_aux_in da;
-        memset(&da, 0, sizeof(da));
-        da.fstate = (const uint8_t*)dev(o_fs); da.wait_ticks_left = (const int32_t*)dev(o_wt);
-        da.wait_prev = (const uint8_t*)dev(o_wp); da.new_pos_xz = (const float*)(res + r_np);
-        if(turn) { da.ent_rot = (const float*)a_er; da.target_dir = (const float*)a_td; }
-        if(rg) {
-            da.range_target = (const int32_t*)a_rt; da.target_range = (const float*)a_rr;
-            da.target_prev_xz = (const float*)a_rp; da.range_tiles_row = (const int32_t*)a_row;
-            da.range_tiles_off = (const int32_t*)dev(o_roff); da.range_tiles = (const int16_t*)dev(o_rtil);
-            da.n_range_rows = X.n_range_rows;
-        }
-        if(su) {
-            da.surround_target = (const int32_t*)a_stgt; da.surround_query = (const uint8_t*)a_sq;
-            da.surround_target_prev_xz = (const float*)a_stp; da.surround_nearest_prev_xz = (const float*)a_snp;
-            da.surround_dest_xz = (const float*)a_sd; da.vdes_xz = d_vdes; da.out_surround_dest_xz = (float*)(res + r_sd);
-        }
-        rc = navhip_state_update_aux_dev(ctx, &d, &da, (uint8_t*)(res + r_st), (uint8_t*)(res + r_fl), (int32_t*)(res + r_tk), s);
-        if(rc) return rc;
-    }
-    if(e > b) {
-        hipLaunchKernelGGL(k_gate_host_rows, dim3((e - b + 255) / 256), dim3(256), 0, s, b, e, (const uint8_t*)(res + r_gate),
-                           d.state, aux ? (const int32_t*)dev(o_wt) : (const int32_t*)nullptr,
-                           (uint8_t*)(res + r_st), (uint8_t*)(res + r_fl), aux ? (int32_t*)(res + r_tk) : (int32_t*)nullptr);
-        HIPCHK(ctx, hipGetLastError());
-        if(su && sp && ns) {
-            hipLaunchKernelGGL(k_sparse_gather2, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, s, (int)ns, (const int32_t*)dev(o_units),
-                               (const float*)(res + r_sd), (float*)(res + r_sdk));
-            HIPCHK(ctx, hipGetLastError());
-        }
-        // results: the pageable destinations' rows are gathered into one block on the device and cross the bus once
-        char *d_oblock = res + R.total;
-        for(auto &o : outs) {
-            if(o.pinned) HIPCHK(ctx, hipMemcpyAsync((char*)o.dst + o.lo * o.row, res + o.dev_off + o.lo * o.row, o.cnt * o.row, hipMemcpyDeviceToHost, s));
-            else         HIPCHK(ctx, hipMemcpyAsync(d_oblock + o.h_off, res + o.dev_off + o.lo * o.row, o.cnt * o.row, hipMemcpyDeviceToDevice, s));
-        }
-        if(pack_out) HIPCHK(ctx, hipMemcpyAsync(h_out, d_oblock, pack_out, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    if(e > b)
-        for(auto &o : outs) if(!o.pinned) memcpy((char*)o.dst + o.lo * o.row, h_out + o.h_off, o.cnt * o.row);
-    return NAVHIP_OK;
-}
-
-static int sk_settled_count(navhip_ctx *ctx, const navhip_world *w, int nq, const int32_t *uids, int32_t *out_counts, bool use_resident);
-
-int navhip_settled_count(navhip_ctx *ctx, const navhip_world *w, int nq, const int32_t *uids, int32_t *out_counts)
-{
-    return sk_settled_count(ctx, w, nq, uids, out_counts, false);
-}
-
-int navhip_settled_count_resident(navhip_ctx *ctx, const navhip_world *w, int nq, const int32_t *uids, int32_t *out_counts)
-{
-    return sk_settled_count(ctx, w, nq, uids, out_counts, true);
+    if(e > b) hipLaunchKernelGGL(k_pick_vdes, dim3((e - b + 255) / 256), dim3(256), 0, s, b, e, d.vdes_xz, (const float*)so.vdes_xz, d_vdes);
+    dg.new_vel_xz = so.vel_xz; dg.vdes_xz = d_vdes;
+    da.out_surround_dest_xz = d_sdest;
+    rc = sk_run_passes(ctx, &d, b, e, dg, ds, aux ? &da : nullptr, r, su && sp ? units : nullptr, ns, d_listed, s);
+    if(!rc) rc = R.download(ctx, s);
+    return rc;
 }
 
 static int sk_settled_count(navhip_ctx *ctx, const navhip_world *w, int nq, const int32_t *uids, int32_t *out_counts, bool use_resident)
@@ -1103,7 +1078,6 @@ static int sk_settled_count(navhip_ctx *ctx, const navhip_world *w, int nq, cons
         if(uids[q] < 0 || uids[q] >= w->n_ents) return NAVHIP_ERR_INVALID;
     // the spatial index over the snapshot, the circle queries and the count, all on the device: the ids of the queries
     // (the reference's visiting order, capped) never leave HBM -- only the uids go up and the counts come back
-    const size_t n = (size_t)w->n_ents;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     navhip_world d; navhip_step_out so;
@@ -1112,36 +1086,37 @@ static int sk_settled_count(navhip_ctx *ctx, const navhip_world *w, int nq, cons
         ctx->last_error = "navhip_settled_count_resident: no completed host-buffer step of this size is resident on the device";
         return NAVHIP_ERR_INVALID;
     }
-    sk_arena A;
-    const size_t o_pos = A.take(resident ? 0 : n * 8), o_rad = A.take(resident ? 0 : n * 4), o_fl = A.take(resident ? 0 : n * 4),
-                 o_st = A.take(resident ? 0 : n), o_uid = A.take((size_t)nq * 4), o_q = A.take((size_t)nq * 8),
-                 o_cnt = A.take((size_t)nq * 4), o_ids = A.take((size_t)nq * SK_QUERY_MAX * 4), o_out = A.take((size_t)nq * 4);
-    char *base;
-    int rc = nh_stage_reserve(ctx, NH_STAGE_STATE_ARENA, A.total, (void**)&base);
-    if(rc) return rc;
+    sk_plan P;
     if(!resident) {
         // (a snapshot the velocity pass left on the device is read in place: the tick's tables are the same)
-        HIPCHK(ctx, hipMemcpyAsync(base + o_pos, w->pos_xz, n * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(base + o_rad, w->radius, n * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(base + o_fl, w->flags, n * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(base + o_st, w->state, n, hipMemcpyHostToDevice, s));
         d = *w;
-        d.pos_xz = (const float*)(base + o_pos); d.radius = (const float*)(base + o_rad);
-        d.flags = (const uint32_t*)(base + o_fl); d.state = (const uint8_t*)(base + o_st);
+        sk_stage_world(P, w, &d, sk_dims_of(w, 0, 0), {SK_W(pos_xz), SK_W(radius), SK_W(flags), SK_W(state)});
     }
     d.grid_xmin = w->grid_xmin; d.grid_xmax = w->grid_xmax; d.grid_zmin = w->grid_zmin; d.grid_zmax = w->grid_zmax;
-    HIPCHK(ctx, hipMemcpyAsync(base + o_uid, uids, (size_t)nq * 4, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_gather_query, dim3((nq + 255) / 256), dim3(256), 0, s, nq, (const int32_t*)(base + o_uid), d.pos_xz, (float*)(base + o_q));
-    rc = nh_spatial_query_dev(ctx, &d, (const float*)(base + o_q), nq, SK_QUERY_R, SK_QUERY_MAX, (int32_t*)(base + o_cnt),
-                              (uint32_t*)(base + o_ids), s);
+    int32_t *d_uid, *d_cnt, *d_out; float *d_q; uint32_t *d_ids;
+    P.in(uids, (size_t)nq * 4, 0, (void**)&d_uid);
+    P.scratch((size_t)nq * 8, (void**)&d_q); P.scratch((size_t)nq * 4, (void**)&d_cnt); P.scratch((size_t)nq * SK_QUERY_MAX * 4, (void**)&d_ids);
+    P.out(P.scratch((size_t)nq * 4, (void**)&d_out), out_counts, 4, 0, (size_t)nq);
+    int rc = P.reserve(ctx, NH_STAGE_STATE_ARENA);
+    if(!rc) rc = P.upload(ctx, s);
     if(rc) return rc;
-    hipLaunchKernelGGL(k_settled_count, dim3((nq + 15) / 16), dim3(256), 0, s, nq, (const int32_t*)(base + o_uid),
-                       d.pos_xz, d.radius, d.flags, d.state, (const int32_t*)(base + o_cnt), (const uint32_t*)(base + o_ids),
-                       (int32_t*)(base + o_out));
+    hipLaunchKernelGGL(k_gather_query, dim3((nq + 255) / 256), dim3(256), 0, s, nq, (const int32_t*)d_uid, d.pos_xz, d_q);
+    rc = nh_spatial_query_dev(ctx, &d, d_q, nq, SK_QUERY_R, SK_QUERY_MAX, d_cnt, d_ids, s);
+    if(rc) return rc;
+    hipLaunchKernelGGL(k_settled_count, dim3((nq + 15) / 16), dim3(256), 0, s, nq, (const int32_t*)d_uid,
+                       d.pos_xz, d.radius, d.flags, d.state, (const int32_t*)d_cnt, (const uint32_t*)d_ids, d_out);
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out_counts, base + o_out, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return NAVHIP_OK;
+    return P.download(ctx, s);
+}
+
+int navhip_settled_count(navhip_ctx *ctx, const navhip_world *w, int nq, const int32_t *uids, int32_t *out_counts)
+{
+    return sk_settled_count(ctx, w, nq, uids, out_counts, false);
+}
+
+int navhip_settled_count_resident(navhip_ctx *ctx, const navhip_world *w, int nq, const int32_t *uids, int32_t *out_counts)
+{
+    return sk_settled_count(ctx, w, nq, uids, out_counts, true);
 }
 
 int navhip_arrival_settle_dev(navhip_ctx *ctx, const navhip_world *w, const navhip_settle_in *in,
@@ -1149,11 +1124,7 @@ int navhip_arrival_settle_dev(navhip_ctx *ctx, const navhip_world *w, const navh
 {
     if(!ctx || !w || !in || !out || in->nq < 0 || in->n_zones < 0 || w->n_ents < 0) return NAVHIP_ERR_INVALID;
     if(in->nq == 0) return NAVHIP_OK;
-    if(!w->vel_xz || !w->radius || !in->zones || in->n_zones < 1 || !in->uid || !in->zone || !in->new_pos_xz
-    || !in->nsettled || !in->substate || !in->sink_valid || !in->sink_xz || !in->order_pos_xz || !in->progress_anchor_xz
-    || !in->progress_anchored || !in->stuck || !out->settle || !out->substate || !out->progress_anchor_xz
-    || !out->progress_anchored || !out->stuck)
-        return NAVHIP_ERR_INVALID;
+    if(!w->vel_xz || !w->radius || !in->nsettled || !sk_check_settle(in, out)) return NAVHIP_ERR_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     nh_step_params P;
     sk_map_view(ctx, w, &P);
@@ -1161,18 +1132,6 @@ int navhip_arrival_settle_dev(navhip_ctx *ctx, const navhip_world *w, const navh
                        P, w->vel_xz, w->radius, *in, *out);
     HIPCHK(ctx, hipGetLastError());
     return NAVHIP_OK;
-}
-
-static int sk_arrival_settle(navhip_ctx *ctx, const navhip_world *w, const navhip_settle_in *in, const navhip_settle_out *out, bool use_resident);
-
-int navhip_arrival_settle(navhip_ctx *ctx, const navhip_world *w, const navhip_settle_in *in, const navhip_settle_out *out)
-{
-    return sk_arrival_settle(ctx, w, in, out, false);
-}
-
-int navhip_arrival_settle_resident(navhip_ctx *ctx, const navhip_world *w, const navhip_settle_in *in, const navhip_settle_out *out)
-{
-    return sk_arrival_settle(ctx, w, in, out, true);
 }
 
 static int sk_arrival_settle(navhip_ctx *ctx, const navhip_world *w, const navhip_settle_in *in, const navhip_settle_out *out, bool use_resident)
@@ -1188,12 +1147,8 @@ static int sk_arrival_settle(navhip_ctx *ctx, const navhip_world *w, const navhi
         ctx->last_error = "navhip_arrival_settle_resident: no completed host-buffer step of this size is resident on the device";
         return NAVHIP_ERR_INVALID;
     }
-    if((!resident && (!w->vel_xz || !w->radius)) || !in->zones || in->n_zones < 1 || !in->uid || !in->zone || !in->new_pos_xz
-    || !in->substate || !in->sink_valid || !in->sink_xz || !in->order_pos_xz || !in->progress_anchor_xz
-    || !in->progress_anchored || !in->stuck || !out->settle || !out->substate || !out->progress_anchor_xz
-    || !out->progress_anchored || !out->stuck)
-        return NAVHIP_ERR_INVALID;
-    const size_t n = (size_t)w->n_ents, nq = (size_t)in->nq, nz = (size_t)in->n_zones;
+    if((!resident && (!w->vel_xz || !w->radius)) || !sk_check_settle(in, out)) return NAVHIP_ERR_INVALID;
+    const size_t nq = (size_t)in->nq, nz = (size_t)in->n_zones;
     size_t n_slots = 0, n_keys = 0;
     for(size_t z = 0; z < nz; z++) {
         const navhip_arrival_zone &Z = in->zones[z];
@@ -1207,76 +1162,54 @@ static int sk_arrival_settle(navhip_ctx *ctx, const navhip_world *w, const navhi
         if(in->uid[q] < 0 || in->uid[q] >= w->n_ents || in->zone[q] < 0 || in->zone[q] >= in->n_zones) return NAVHIP_ERR_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    sk_arena A;
-    const size_t o_vel = A.take(resident ? 0 : n * 8), o_rad = A.take(resident ? 0 : n * 4);
-    // (the inputs of the arm from here to in_end, the results from r_set to the end: each region crosses the bus once)
-    const size_t o_z = A.take(nz * sizeof(navhip_arrival_zone)),
-                 o_sl = A.take(n_slots * 8 + 8), o_ring = A.take(n_slots * 4 + 4), o_keys = A.take(n_keys * 8 + 8),
-                 o_uid = A.take(nq * 4), o_zone = A.take(nq * 4), o_np = A.take(nq * 8), o_ns = A.take(count_here ? 0 : nq * 4),
-                 o_sub = A.take(nq), o_sv = A.take(nq), o_sink = A.take(nq * 8), o_ord = A.take(nq * 8),
-                 o_anc = A.take(nq * 8), o_and = A.take(nq), o_stk = A.take(nq * 4), in_end = A.total,
-                 o_q = A.take(count_here ? nq * 8 : 0), o_cnt = A.take(count_here ? nq * 4 : 0),
-                 o_ids = A.take(count_here ? nq * SK_QUERY_MAX * 4 : 0),
-                 r_set = A.take(nq), r_sub = A.take(nq), r_anc = A.take(nq * 8), r_and = A.take(nq), r_stk = A.take(nq * 4),
-                 r_ns = A.take(count_here ? nq * 4 : 0);
-    char *base;
-    int rc = nh_stage_reserve(ctx, NH_STAGE_STATE_ARENA, A.total, (void**)&base);
-    if(rc) return rc;
-    struct up { size_t off; const void *src; size_t bytes; };
-    const up ups[] = {{o_z, in->zones, nz * sizeof(navhip_arrival_zone)}, {o_sl, in->slots_xz, n_slots * 8}, {o_ring, in->slot_ring, n_slots * 4},
-                      {o_keys, in->region_keys, n_keys * 8}, {o_uid, in->uid, nq * 4}, {o_zone, in->zone, nq * 4}, {o_np, in->new_pos_xz, nq * 8},
-                      {o_ns, in->nsettled, count_here ? 0 : nq * 4}, {o_sub, in->substate, nq}, {o_sv, in->sink_valid, nq},
-                      {o_sink, in->sink_xz, nq * 8}, {o_ord, in->order_pos_xz, nq * 8}, {o_anc, in->progress_anchor_xz, nq * 8},
-                      {o_and, in->progress_anchored, nq}, {o_stk, in->stuck, nq * 4}};
-    struct down { size_t off; void *dst; size_t bytes; };
-    const down downs[] = {{r_set, out->settle, nq}, {r_sub, out->substate, nq}, {r_anc, out->progress_anchor_xz, nq * 8},
-                          {r_and, out->progress_anchored, nq}, {r_stk, out->stuck, nq * 4},
-                          {r_ns, out->nsettled, count_here && out->nsettled ? nq * 4 : 0}};
-    // a context with an asynchronous step path owns page-locked slabs: the small arrays are packed into them
-    char *h_in = nullptr, *h_out = nullptr;
-    const bool packed = nh_async_slabs(ctx, in_end - o_z, A.total - r_set, &h_in, &h_out) == NAVHIP_OK;
-    if(!resident) {
-        HIPCHK(ctx, hipMemcpyAsync(base + o_vel, w->vel_xz, n * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(base + o_rad, w->radius, n * 4, hipMemcpyHostToDevice, s));
-    }
-    if(packed) {
-        for(const up &u : ups) if(u.bytes) memcpy(h_in + (u.off - o_z), u.src, u.bytes);
-        HIPCHK(ctx, hipMemcpyAsync(base + o_z, h_in, in_end - o_z, hipMemcpyHostToDevice, s));
-    }else
-        for(const up &u : ups) if(u.bytes) HIPCHK(ctx, hipMemcpyAsync(base + u.off, u.src, u.bytes, hipMemcpyHostToDevice, s));
+    sk_dims D = sk_dims_of(w, 0, 0);
+    D.len[SK_PER_ZONE] = nz; D.len[SK_PER_SLOT] = n_slots; D.len[SK_PER_KEY] = n_keys; D.len[SK_PER_QUERY] = nq;
+    D.cnt = nq;
+    sk_plan P;
     navhip_world d = *w;
     // (the snapshot the velocity half left on the device is read in place: movestate.velocity and the radii are the tick's)
-    d.vel_xz = resident ? rw.vel_xz : (const float*)(base + o_vel); d.radius = resident ? rw.radius : (const float*)(base + o_rad);
+    if(resident) { d.vel_xz = rw.vel_xz; d.radius = rw.radius; }
+    else sk_stage_world(P, w, &d, D, {SK_W(vel_xz), SK_W(radius)});
+    // (the inputs of the arm side by side, the results at the end: a context with an asynchronous step path owns
+    // page-locked slabs, and each region then crosses the bus once)
+    navhip_settle_in di = *in;
+    navhip_settle_out dout = {};
+    const int first_in = (int)P.rows.size();
+    sk_stage(P, sk_settle_in_rows, in, &di, D, {offsetof(navhip_settle_in, nsettled)});
+    if(!count_here) P.in(in->nsettled, nq * 4, 0, (void**)&di.nsettled);
+    float *d_q; int32_t *d_cnt; uint32_t *d_ids;
+    const int end_in = P.scratch(count_here ? nq * 8 : 0, (void**)&d_q);
+    P.scratch(count_here ? nq * 4 : 0, (void**)&d_cnt); P.scratch(count_here ? nq * SK_QUERY_MAX * 4 : 0, (void**)&d_ids);
+    const int first_out = (int)P.rows.size();
+    sk_stage(P, sk_settle_out_rows, out, &dout, D, {offsetof(navhip_settle_out, nsettled)});
+    if(count_here) P.out(P.scratch(nq * 4, (void**)&di.nsettled), out->nsettled, 4, 0, nq);
+    P.region(ctx, first_in, end_in, first_out);
+    int rc = P.reserve(ctx, NH_STAGE_STATE_ARENA);
+    if(!rc) rc = P.upload(ctx, s);
+    if(rc) return rc;
     if(count_here) {
         navhip_world dq = rw;
         dq.grid_xmin = w->grid_xmin; dq.grid_xmax = w->grid_xmax; dq.grid_zmin = w->grid_zmin; dq.grid_zmax = w->grid_zmax;
-        hipLaunchKernelGGL(k_gather_query, dim3((in->nq + 255) / 256), dim3(256), 0, s, in->nq, (const int32_t*)(base + o_uid), rw.pos_xz, (float*)(base + o_q));
-        rc = nh_spatial_query_dev(ctx, &dq, (const float*)(base + o_q), in->nq, SK_QUERY_R, SK_QUERY_MAX, (int32_t*)(base + o_cnt),
-                                  (uint32_t*)(base + o_ids), s);
+        hipLaunchKernelGGL(k_gather_query, dim3((in->nq + 255) / 256), dim3(256), 0, s, in->nq, di.uid, rw.pos_xz, d_q);
+        rc = nh_spatial_query_dev(ctx, &dq, d_q, in->nq, SK_QUERY_R, SK_QUERY_MAX, d_cnt, d_ids, s);
         if(rc) return rc;
-        hipLaunchKernelGGL(k_settled_count, dim3((in->nq + 15) / 16), dim3(256), 0, s, in->nq, (const int32_t*)(base + o_uid),
-                           rw.pos_xz, rw.radius, rw.flags, rw.state, (const int32_t*)(base + o_cnt), (const uint32_t*)(base + o_ids),
-                           (int32_t*)(base + r_ns));
+        hipLaunchKernelGGL(k_settled_count, dim3((in->nq + 15) / 16), dim3(256), 0, s, in->nq, di.uid,
+                           rw.pos_xz, rw.radius, rw.flags, rw.state, (const int32_t*)d_cnt, (const uint32_t*)d_ids, (int32_t*)di.nsettled);
         HIPCHK(ctx, hipGetLastError());
     }
-    navhip_settle_in di = *in;
-    di.zones = (const navhip_arrival_zone*)(base + o_z); di.slots_xz = (const float*)(base + o_sl);
-    di.slot_ring = (const int32_t*)(base + o_ring); di.region_keys = (const uint64_t*)(base + o_keys);
-    di.uid = (const int32_t*)(base + o_uid); di.zone = (const int32_t*)(base + o_zone);
-    di.new_pos_xz = (const float*)(base + o_np); di.nsettled = (const int32_t*)(base + (count_here ? r_ns : o_ns));
-    di.substate = (const uint8_t*)(base + o_sub); di.sink_valid = (const uint8_t*)(base + o_sv);
-    di.sink_xz = (const float*)(base + o_sink); di.order_pos_xz = (const float*)(base + o_ord);
-    di.progress_anchor_xz = (const float*)(base + o_anc); di.progress_anchored = (const uint8_t*)(base + o_and);
-    di.stuck = (const int32_t*)(base + o_stk);
-    navhip_settle_out dout = {(uint8_t*)(base + r_set), (uint8_t*)(base + r_sub), (float*)(base + r_anc),
-                              (uint8_t*)(base + r_and), (int32_t*)(base + r_stk), nullptr};
     rc = navhip_arrival_settle_dev(ctx, &d, &di, &dout, s);
-    if(rc) return rc;
-    if(packed) HIPCHK(ctx, hipMemcpyAsync(h_out, base + r_set, A.total - r_set, hipMemcpyDeviceToHost, s));
-    else for(const down &o : downs) if(o.bytes) HIPCHK(ctx, hipMemcpyAsync(o.dst, base + o.off, o.bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    if(packed) for(const down &o : downs) if(o.bytes) memcpy(o.dst, h_out + (o.off - r_set), o.bytes);
-    return NAVHIP_OK;
+    if(!rc) rc = P.download(ctx, s);
+    return rc;
+}
+
+int navhip_arrival_settle(navhip_ctx *ctx, const navhip_world *w, const navhip_settle_in *in, const navhip_settle_out *out)
+{
+    return sk_arrival_settle(ctx, w, in, out, false);
+}
+
+int navhip_arrival_settle_resident(navhip_ctx *ctx, const navhip_world *w, const navhip_settle_in *in, const navhip_settle_out *out)
+{
+    return sk_arrival_settle(ctx, w, in, out, true);
 }
 
 }   // extern "C"

@@ -762,6 +762,40 @@ def _ctx_region_lookup(self, pos_xz, rows, region_field_slot=None, field_pool=No
     return out, at
 
 
+def _tiles_csr(tile_lists):
+    """list of [k, 2] int16 arrays (absolute (row, col) tiles) -> (CSR offsets [len + 1] int32, the tiles [.., 2] int16 with
+    one spare row, so that the array is never empty)."""
+    offs = np.zeros(len(tile_lists) + 1, np.int32)
+    offs[1:] = np.cumsum([len(t) for t in tile_lists])
+    tiles = np.concatenate([np.asarray(t, np.int16).reshape(-1, 2) for t in tile_lists] + [np.zeros((1, 2), np.int16)])
+    return offs, np.ascontiguousarray(tiles)
+
+
+def _fill_aux_arms(ai, n, ent_rot=None, target_dir=None, range_in=None, surround=None):
+    """The turn / enter-range / surround members of the StateAuxIn `ai`.  range_in: dict(target [n] row or -1 / -2,
+    range [n], prev_xz [n][2], tiles_row [n], tiles: list of [k, 2] int16); surround: see _surround_arrays.
+    Returns (the arrays to keep alive, the surround output array or None)."""
+    f32 = lambda a, *shape: np.ascontiguousarray(a, np.float32).reshape(n, *shape)
+    keep, su_out = [], None
+    if ent_rot is not None:
+        keep += [f32(ent_rot, 4), f32(target_dir, 4)]
+        ai.ent_rot, ai.target_dir = keep[-2].ctypes.data, keep[-1].ctypes.data
+    if range_in is not None:
+        r = [np.ascontiguousarray(range_in["target"], np.int32), f32(range_in["range"]), f32(range_in["prev_xz"], 2),
+             np.ascontiguousarray(range_in["tiles_row"], np.int32), *_tiles_csr(range_in["tiles"])]
+        keep += r
+        ai.range_target, ai.target_range, ai.target_prev_xz, ai.range_tiles_row, ai.range_tiles_off, ai.range_tiles = \
+            [a.ctypes.data for a in r]
+        ai.n_range_rows = len(range_in["tiles"])
+    if surround is not None:
+        sa = _surround_arrays(n, surround)
+        keep += sa
+        ai.surround_target, ai.surround_query, ai.surround_target_prev_xz, ai.surround_nearest_prev_xz, ai.surround_dest_xz, \
+            ai.out_surround_dest_xz = [a.ctypes.data for a in sa]
+        su_out = sa[5]
+    return keep, su_out
+
+
 def _ctx_state_update(self, arrays, new_pos_xz, vdes_xz, flock_layer, flock_nearest_xz, flock_tiles, skip=None,
                       hz=20, work=None):
     """The arrival arm of entity_compute_update (movement.c:2303) for every unit of the snapshot `arrays`.
@@ -775,10 +809,7 @@ def _ctx_state_update(self, arrays, new_pos_xz, vdes_xz, flock_layer, flock_near
          "vd": np.ascontiguousarray(vdes_xz, np.float32).reshape(n, 2),
          "fl": np.ascontiguousarray(flock_layer, np.uint8),
          "fn": np.ascontiguousarray(flock_nearest_xz, np.float32).reshape(-1, 2)}
-    offs = np.zeros(len(flock_tiles) + 1, np.int32)
-    offs[1:] = np.cumsum([len(t) for t in flock_tiles])
-    tiles = np.concatenate([np.asarray(t, np.int16).reshape(-1, 2) for t in flock_tiles] + [np.zeros((1, 2), np.int16)])
-    k["to"], k["tt"] = offs, np.ascontiguousarray(tiles)
+    k["to"], k["tt"] = _tiles_csr(flock_tiles)
     si.new_pos_xz, si.vdes_xz = k["np"].ctypes.data, k["vd"].ctypes.data
     si.flock_layer, si.flock_nearest_xz = k["fl"].ctypes.data, k["fn"].ctypes.data
     si.flock_tiles_off, si.flock_tiles = k["to"].ctypes.data, k["tt"].ctypes.data
@@ -830,31 +861,16 @@ def _ctx_state_update_aux(self, arrays, fstate, wait_ticks_left, wait_prev, new_
     k = [np.ascontiguousarray(fstate, np.uint8), np.ascontiguousarray(wait_ticks_left, np.int32),
          np.ascontiguousarray(wait_prev, np.uint8), np.ascontiguousarray(new_pos_xz, np.float32).reshape(n, 2)]
     ai = StateAuxIn(*[a.ctypes.data for a in k])
-    if ent_rot is not None:
-        k += [np.ascontiguousarray(ent_rot, np.float32).reshape(n, 4), np.ascontiguousarray(target_dir, np.float32).reshape(n, 4)]
-        ai.ent_rot, ai.target_dir = k[-2].ctypes.data, k[-1].ctypes.data
-    if range_in is not None:
-        # range_in: dict(target [n] row or -1 / -2, range [n], prev_xz [n][2], tiles_row [n], tiles: list of [k, 2] int16)
-        offs = np.zeros(len(range_in["tiles"]) + 1, np.int32)
-        offs[1:] = np.cumsum([len(t) for t in range_in["tiles"]])
-        tiles = np.concatenate([np.asarray(t, np.int16).reshape(-1, 2) for t in range_in["tiles"]] + [np.zeros((1, 2), np.int16)])
-        r = [np.ascontiguousarray(range_in["target"], np.int32), np.ascontiguousarray(range_in["range"], np.float32),
-             np.ascontiguousarray(range_in["prev_xz"], np.float32).reshape(n, 2), np.ascontiguousarray(range_in["tiles_row"], np.int32),
-             offs, np.ascontiguousarray(tiles)]
-        k += r
-        ai.range_target, ai.target_range, ai.target_prev_xz, ai.range_tiles_row, ai.range_tiles_off, ai.range_tiles = \
-            [a.ctypes.data for a in r]
-        ai.n_range_rows = len(range_in["tiles"])
+    arms, su_out = _fill_aux_arms(ai, n, ent_rot, target_dir, range_in, surround)
+    k += arms
     if surround is not None:
-        sa = _surround_arrays(n, surround) + [np.ascontiguousarray(vdes_xz, np.float32).reshape(n, 2)]
-        k += sa
-        ai.surround_target, ai.surround_query, ai.surround_target_prev_xz, ai.surround_nearest_prev_xz, ai.surround_dest_xz, \
-            ai.out_surround_dest_xz, ai.vdes_xz = [a.ctypes.data for a in sa]
+        k.append(np.ascontiguousarray(vdes_xz, np.float32).reshape(n, 2))
+        ai.vdes_xz = k[-1].ctypes.data
     st, fl, ticks = np.array(state, np.uint8), np.array(flags, np.uint8), np.zeros(n, np.int32)
     self._chk(lib().navhip_state_update_aux(self._h, C.byref(w), C.byref(ai), _hp(st), _hp(fl), _hp(ticks)),
               "navhip_state_update_aux")
     if surround is not None:
-        return st, fl, ticks, sa[5]
+        return st, fl, ticks, su_out
     return st, fl, ticks
 
 
@@ -871,9 +887,7 @@ def _ctx_state_pass(self, arrays, next_rot, new_vel_xz, vdes_xz, flock_layer, fl
     f32 = lambda a, width: np.ascontiguousarray(a, np.float32).reshape(n, width)
     k = [f32(next_rot, 4), f32(new_vel_xz, 2), f32(vdes_xz, 2), np.ascontiguousarray(flock_layer, np.uint8),
          np.ascontiguousarray(flock_nearest_xz, np.float32).reshape(-1, 2)]
-    offs = np.zeros(len(flock_tiles) + 1, np.int32)
-    offs[1:] = np.cumsum([len(t) for t in flock_tiles])
-    tiles = np.ascontiguousarray(np.concatenate([np.asarray(t, np.int16).reshape(-1, 2) for t in flock_tiles] + [np.zeros((1, 2), np.int16)]))
+    offs, tiles = _tiles_csr(flock_tiles)
     k += [offs, tiles]
     pi = StatePassIn()
     pi.gate = GateIn(k[0].ctypes.data, k[1].ctypes.data, k[2].ctypes.data)
@@ -890,28 +904,8 @@ def _ctx_state_pass(self, arrays, next_rot, new_vel_xz, vdes_xz, flock_layer, fl
              np.ascontiguousarray(aux["wait_prev"], np.uint8)]
         k += a
         pi.aux.fstate, pi.aux.wait_ticks_left, pi.aux.wait_prev = [x.ctypes.data for x in a]
-        if aux.get("ent_rot") is not None:
-            r = [f32(aux["ent_rot"], 4), f32(aux["target_dir"], 4)]
-            k += r
-            pi.aux.ent_rot, pi.aux.target_dir = r[0].ctypes.data, r[1].ctypes.data
-        ri = aux.get("range_in")
-        if ri is not None:
-            ro = np.zeros(len(ri["tiles"]) + 1, np.int32)
-            ro[1:] = np.cumsum([len(t) for t in ri["tiles"]])
-            rt = np.ascontiguousarray(np.concatenate([np.asarray(t, np.int16).reshape(-1, 2) for t in ri["tiles"]] + [np.zeros((1, 2), np.int16)]))
-            r = [np.ascontiguousarray(ri["target"], np.int32), np.ascontiguousarray(ri["range"], np.float32), f32(ri["prev_xz"], 2),
-                 np.ascontiguousarray(ri["tiles_row"], np.int32), ro, rt]
-            k += r
-            pi.aux.range_target, pi.aux.target_range, pi.aux.target_prev_xz, pi.aux.range_tiles_row, pi.aux.range_tiles_off, \
-                pi.aux.range_tiles = [x.ctypes.data for x in r]
-            pi.aux.n_range_rows = len(ri["tiles"])
-        su_out = None
-        if aux.get("surround") is not None:
-            sa = _surround_arrays(n, aux["surround"])
-            k += sa
-            pi.aux.surround_target, pi.aux.surround_query, pi.aux.surround_target_prev_xz, pi.aux.surround_nearest_prev_xz, \
-                pi.aux.surround_dest_xz, pi.aux.out_surround_dest_xz = [x.ctypes.data for x in sa]
-            su_out = sa[5]
+        arms, su_out = _fill_aux_arms(pi.aux, n, aux.get("ent_rot"), aux.get("target_dir"), aux.get("range_in"), aux.get("surround"))
+        k += arms
     res = {"state": np.zeros(n, np.uint8), "flags": np.zeros(n, np.uint8), "gate": np.zeros(n, np.uint8),
            "new_pos_xz": np.zeros((n, 2), np.float32), "vel_xz": np.zeros((n, 2), np.float32),
            "wait_ticks_left": np.zeros(n, np.int32)}
