@@ -1,4 +1,4 @@
-// agent_internal.h -- launch interface of agent_kernels.hip (used by navhip_api.hip).
+// agent_internal.h -- launch interface of agent_kernels.hip (used by step_api.hip, navhip_api.hip, state_kernels.hip).
 #pragma once
 #define NH_SCAN_T 256      /* threads (= cells) per block of the two-pass scans */
 #include "navhip_internal.h"
@@ -33,7 +33,7 @@ void nh_launch_cohesion_regroup(const nh_step_params &P, int32_t *scratch, int *
 int nh_worklist_cap(int n_work);
 bool nh_launch_agent_finish(const nh_step_params &P, const nh_nbr &NB, float *d_coh, nh_mid_rec *d_mid,
                             nh_worklists WL, int parity, const nh_step_outs &O, hipStream_t s,
-                            hipStream_t side, navhip_ctx *ctx);
+                            hipStream_t side, navhip_ctx *ctx, bool *forked);
 void nh_launch_state_update(const nh_step_params &P, const navhip_state_in &in, float4 *d_arrived, int32_t *d_arrived_n, uint8_t *d_state, uint8_t *d_flags,
                             hipStream_t s);
 void nh_launch_region_lookup(const nh_step_params &P, int nq, const float *d_pos, const int32_t *d_rows,

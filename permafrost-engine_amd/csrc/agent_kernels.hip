@@ -14,7 +14,7 @@
 // Arithmetic mirrors the reference's C expression by expression (agent_math.h); all
 // order-dependent float sums are evaluated in the reference's own order.
 //
-// Kernels of one tick (navhip_api.hip wires the streams):
+// Kernels of one tick (step_api.hip wires the streams):
 //   k_sp_count .. k_sp_place   device spatial hash: fixed-point cell binning, scan, and the POOL -- one
 //                 16-byte record {pos, radius, flag bits | uid} + one velocity per inserted entity, in
 //                 the cell order and per-cell order bg_ent_cleanup produces after inserting uids
@@ -1887,10 +1887,11 @@ int nh_worklist_cap(int n_work)
 // k_agent_mid + the consumers of its work lists.  The list counters alternate between two sets:
 // a launch sequence uses one and zeroes the other for its successor (no memset on the stream).
 // Returns whether anything was launched (the caller flips the parity only then: a step that launches nothing
-// does not clear the other set either).
+// does not clear the other set either); *forked: the second chain went onto `side`, so NH_HO_MID says when the work lists
+// were complete and NH_HO_END when the step had ended on s.
 bool nh_launch_agent_finish(const nh_step_params &P, const nh_nbr &NB, float *d_coh, nh_mid_rec *d_mid,
                             nh_worklists WL, int parity, const nh_step_outs &O, hipStream_t s,
-                            hipStream_t side, navhip_ctx *ctx)
+                            hipStream_t side, navhip_ctx *ctx, bool *forked)
 {
     const int nwork = P.work_end - P.work_begin;
     if(!(P.n_ents > 0 && nwork > 0)) return false;
@@ -1910,7 +1911,7 @@ bool nh_launch_agent_finish(const nh_step_params &P, const nh_nbr &NB, float *d_
     const bool fork = side != nullptr && side != s;
     hipStream_t sh = fork ? side : s;
     const nh_signal lists_ready = fork ? nh_handover_by_kernel(ctx, NH_HO_MID, s) : nh_signal{nullptr, 0};
-    ctx->lists_signalled = fork;
+    *forked = fork;
     const int nblk = min(4096 / CP_WAVES, (nwork + 15) / 16 + 1);      // 4096 persistent waves: four per SIMD
     const int nblk_rows = min(4096 / CPR_WAVES, (nwork + 15) / 16 * (CP_WAVES / CPR_WAVES) + 1);
     // (the rows first: behind a host that is not ahead of the device -- the tick after a synchronisation -- every
@@ -1927,13 +1928,9 @@ bool nh_launch_agent_finish(const nh_step_params &P, const nh_nbr &NB, float *d_
     if(fork) nh_handover_signal(ctx, NH_HO_CP, sh);
     hipLaunchKernelGGL(k_agent_full, dim3(min(1024, (nwork + AG_WAVES - 1) / AG_WAVES)), dim3(AG_WAVES * 64), 0, s, P,
                        (const float*)d_coh, (const nh_mid_rec*)d_mid, WL, O, smf, thresh, (int32_t*)nullptr);
-    if(fork) {
-        // the join; the waiting kernel also says that the step has ended on s: a prefetch that follows directly starts its
-        // side streams behind that (NAVHIP_PREFETCH_FOLLOWS_STEP)
-        nh_handover_wait(ctx, NH_HO_CP, s, -1, NH_HO_END);
-        ctx->step_end_on = ctx->ho->by_events ? nullptr : s;         // (an event is no word: nobody can follow it that way)
-        ctx->step_end_signalled = true;
-    }
+    // the join; the waiting kernel also says that the step has ended on s: a prefetch that follows directly starts its
+    // side streams behind that (NAVHIP_PREFETCH_FOLLOWS_STEP)
+    if(fork) nh_handover_wait(ctx, NH_HO_CP, s, -1, NH_HO_END);
     return true;
 }
 

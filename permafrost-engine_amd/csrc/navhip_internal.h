@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <string>
 #include <vector>
+#include <initializer_list>
 #include <stddef.h>
 #include "navhip.h"
 #include "map_view.h"
@@ -41,9 +42,6 @@ enum nh_stage_slot {
     NH_STAGE_OUT_VEL, NH_STAGE_OUT_NEW_POS, NH_STAGE_OUT_VDES, NH_STAGE_OUT_VPREF, NH_STAGE_OUT_STATUS,
     // navhip_agent_step_submit: the device slabs of its pageable inputs and outputs
     NH_STAGE_SUBMIT_IN, NH_STAGE_SUBMIT_OUT,
-    // navhip_state_update: the arrays of navhip_state_in, {state, flags} out
-    NH_STAGE_SIN_NEW_POS, NH_STAGE_SIN_VDES, NH_STAGE_SIN_SKIP, NH_STAGE_SIN_FLOCK_LAYER, NH_STAGE_SIN_FLOCK_NEAREST,
-    NH_STAGE_SIN_TILES_OFF, NH_STAGE_SIN_TILES, NH_STAGE_SIN_OUT,
     // state_kernels.hip: the arena its host-buffer entry points carve up; the two slabs of the resident state pass
     NH_STAGE_STATE_ARENA, NH_STAGE_PASS_IN, NH_STAGE_PASS_OUT,
     // navhip_build_los_dev: the per-request overlay (the launch may still run when the call returns)
@@ -55,7 +53,7 @@ enum nh_stage_slot {
     NH_STAGE_COUNT
 };
 
-// Which array of navhip_world is staged where, and how large it is: ONE list for every host-buffer path (stage_world,
+// Which array of navhip_world is staged where, and how large it is: ONE list for every host-buffer path (nh_stage_world,
 // navhip_agent_step_submit, navhip_state_update, navhip_spatial_query).  The order is the order of the copies.
 enum nh_row_count { NH_PER_ENT, NH_PER_FLOCK, NH_PER_FLOCK_PLUS1, NH_PER_MEMBER, NH_PER_FLOCK_CHUNK, NH_PER_FIELD_SLOT,
                     NH_PER_LOS_SLOT, NH_PER_REGION_ROW_CHUNK };
@@ -174,6 +172,73 @@ struct navhip_layer {
     bool      nonunit_costs = false;   // host side: a cost other than 1 / 0xff was uploaded for this layer
 };
 
+// The scratch of the agent step (step_api.hip), one buffer per NAME: grown on demand, reused every tick.  What a fresh
+// allocation holds before its first use is said where each group is sized (hash_ensure, walk_ensure).
+enum nh_step_buf {
+    // the spatial hash
+    NH_SB_ENT_CELL, NH_SB_ENT_RANK,     // [n] cell and arrival rank of every entity
+    NH_SB_CELL_COUNT,                   // [ncells] zero between builds (the kernels keep it so)
+    NH_SB_CELL_START,                   // [ncells + 1]
+    NH_SB_TMP_ID,                       // [n] cell-sorted uids
+    NH_SB_BLOCK_SUM,                    // scan scratch
+    NH_SB_SLAB_BOX,                     // two slab boxes + the length of the slab's list of walks
+    NH_SB_REC_A, NH_SB_REC_V,           // [n] pool records
+    NH_SB_POOL_OF,                      // [n]
+    // the neighbour walk: separation force, counts, neighbour lists
+    NH_SB_SEP, NH_SB_CNT, NH_SB_REC,
+    NH_SB_MIDREC,                       // per-entity record k_agent_mid leaves for the work-list consumers
+    // the work lists: 2 x NH_WL_COUNTERS counters (alternating), ids
+    NH_SB_WL_COUNT, NH_SB_WL_IDS,
+    NH_SB_COH,                          // cohesion force per entity
+    NH_SB_COH_PLAN,                     // [n_flocks + 1] wave prefix of the cohesion launch + its lane grouping
+    NH_SB_COUNT
+};
+
+// what a prefetch was started for: everything the side streams baked into their results.  Compared as bytes: zero-filled
+// before it is filled (step_api.hip: prefetch_key)
+struct nh_prefetch_key {
+    const float *pos_xz, *vel_xz, *radius, *arrival_sink_xz; const uint32_t *flags;
+    const uint8_t *state, *arrival_flags; const int32_t *flock_members, *flock_offsets;
+    int n_ents, n_flocks, hz, work_begin, work_end;
+    int32_t origin_x, origin_y; int grid_w, grid_h;
+};
+
+// What the agent step keeps between calls (step_api.hip; tick_api.hip sets serial_step and reads step_end_signalled).
+struct nh_step_state {
+    nh_buf       buf[NH_SB_COUNT];
+    unsigned     scratch_moves = 0; // step scratch reallocated or its lane grouping reset: either may enqueue on the caller's stream
+    unsigned     sp_builds = 0;     // spatial-hash builds so far: parity selects the slab box of a build
+    int          wl_parity = 0;     // which set of list counters the next step uses
+    int32_t     *lists_pinned = nullptr;   // pinned host copy of a step's list counters (navhip_step_lists_peek)
+    // the side streams (spatial hash | cohesion; the ClearPath side chain): BORROWED from the process's set (nh_streams_for)
+    hipStream_t  aux[2] = {nullptr, nullptr};
+    hipStream_t  aux_main = nullptr;          // the main stream the side streams were chosen for
+    hipEvent_t   ev_regroup = nullptr;        // side stream 1 has finished the lane regrouping (the only event of the step: rare, off the critical path)
+    bool         serial_step = false;       // navhip_agent_step_dev runs EVERYTHING on the caller's stream (no side streams, no events):
+                                    // the tick of a small world is a chain of dependent launches, and every cross-stream
+                                    // edge costs more than the overlap it buys (tick_api.hip, NAVHIP_TICK_SERIAL)
+    // what the last prefetch did
+    struct { bool valid = false; nh_prefetch_key key = {}; } pre;   // the snapshot it was started for: the step that follows joins it only for the very same
+    bool         snapshot_held = false;     // its NAVHIP_PREFETCH_SNAPSHOT_HELD
+    hipStream_t  front_stream = nullptr;    // the stream it ran the front of the step on
+    bool         join0_signalled = false;   // NH_HO_NBR has been (or: is going to be, by a launch already enqueued) stored behind its front
+    int          start_flag = NH_HO_START;  // what its side streams wait for: NH_HO_START, or NH_HO_END of the step it follows,
+    int32_t      start_seq = 0;             // ... and the word's number then (later steps advance it)
+    bool         regroup_pending = false;   // a lane regrouping it launched has not been joined yet
+    // what the last step did
+    bool         lists_signalled = false;   // it forked: NH_HO_MID says when its work lists were complete
+    bool         step_end_signalled = false; // it forked: NH_HO_END (word or event) says when it had ended
+    hipStream_t  step_end_on = nullptr;     // the stream on which it stored NH_HO_END behind its last kernel, or NULL
+    // the cohesion term's lane grouping
+    int          coh_flocks = -1, coh_members = -1, coh_parity = 0;   // layout of the plan + which perm buffer is next
+    unsigned     coh_unique = 0;   // membership keys of slab steps whose caller gave no static_epoch: never equal
+    int64_t      coh_regroup_key[4] = {-1, -1, -1, -1}; int coh_regroup_age = 0;   // what the last regrouping was built for, ticks since
+    // optional per-kernel-group timing of the agent step (navhip_set_profiling)
+    bool         profiling = false;
+    hipEvent_t   ev[6] = {};   // start | hash built | neighbour walk | cohesion | regroup | finish
+    bool         ev_valid = false;
+};
+
 struct navhip_ctx {
     int          device = 0;
     int          w = 0, h = 0, nchunks = 0;
@@ -183,56 +248,16 @@ struct navhip_ctx {
     // scratch for the host-buffer entry points
     nh_buf       d_reqs, d_dirs, d_integ;   // navhip_build_fields: requests, directions, integration values
     nh_buf       d_dirty_list;              // chunks whose derived masks are rebuilt
-    // agent-step scratch (grown on demand, reused every tick)
-    nh_buf       sp[10];       // spatial hash: ent_cell, ent_rank, cell_count, cell_start, tmp_id,
-                               //               block_sum, slab box, recA, recV, pool_of
-    unsigned     sp_builds = 0; // spatial-hash builds so far: parity selects the slab box of a build
-    nh_buf       nbr[3];       // neighbour walk: separation force, counts, neighbour lists
-    nh_buf       arrived[2];   // state update: {x, z, radius, uid} of every flock's ARRIVED members, compacted; counts
-    nh_buf       midrec;       // per-entity record k_agent_mid leaves for the work-list consumers
-    nh_buf       wl[2];        // work lists: 2 x NH_WL_COUNT counters (alternating), ids
-    int          wl_parity = 0;
-    int32_t     *lists_pinned = nullptr;   // pinned host copy of a step's list counters (navhip_step_lists_peek)
-    nh_buf       coh;          // cohesion force per entity
-    nh_buf       coh_plan;     // [n_flocks + 1] wave prefix of the cohesion launch
     nh_buf       gen_list;     // [2 + n] requests the BFS kernel left to k_field_generic: 2 counters, ids
     unsigned     gen_launches = 0; // parity selects the counter of a launch
     // the last chunk-field build (navhip_last_fields_split): its requests, the counter of gen_list it used (-1: every
     // request went to k_field_generic, no list), the stream it runs on
     struct { int n = -1, gen_slot = -1; hipStream_t stream = nullptr; } last_fields;
-    int          coh_flocks = -1, coh_members = -1, coh_parity = 0;   // layout of coh_plan + which perm buffer is next
-    unsigned     coh_unique = 0;   // membership keys of slab steps whose caller gave no static_epoch: never equal
-    unsigned     scratch_moves = 0; // step scratch reallocated or its lane grouping reset: either may enqueue on the caller's stream
     nh_buf       stage[NH_STAGE_COUNT];    // device copies of host buffers for the host-pointer entry points
-    // side streams for navhip_agent_prefetch_dev (spatial hash | cohesion) + fork/join events; BORROWED from the process's
-    // set (nh_device_stream)
-    hipStream_t  aux[2] = {nullptr, nullptr};
-    hipStream_t  aux_main = nullptr;          // the main stream the side streams were chosen for
-    hipEvent_t   ev_regroup = nullptr;        // side stream 1 has finished the lane regrouping (the only event of the step: rare, off the critical path)
     navhip_counters counters = {};  // navhip_get_counters
-    bool         snapshot_held = false;     // NAVHIP_PREFETCH_SNAPSHOT_HELD of the last prefetch
-    bool         join0_signalled = false;   // NH_HO_NBR has been (or: is going to be, by a launch already enqueued) stored behind the front of the last prefetch
-    bool         lists_signalled = false;   // the last step forked: NH_HO_MID says when its work lists were complete
-    int          start_flag = NH_HO_START;  // what the side streams of the last prefetch wait for: NH_HO_START, or NH_HO_END of the step it follows,
-    int32_t      start_seq = 0;             // ... and the word's number then (later steps advance it)
-    bool         step_end_signalled = false; // the last step forked: NH_HO_END (word or event) says when it had ended
-    hipStream_t  step_end_on = nullptr;     // the stream on which the last step stored NH_HO_START behind its last kernel, or NULL
-    hipStream_t  front_stream = nullptr;    // the stream the last prefetch ran the front of the step on
-    bool         regroup_pending = false;   // a lane regrouping launched by the prefetch has not been joined yet
-    bool         serial_step = false;       // navhip_agent_step_dev runs EVERYTHING on the caller's stream (no side streams, no events):
-                                    // the tick of a small world is a chain of dependent launches, and every cross-stream
-                                    // edge costs more than the overlap it buys (tick_api.hip, NAVHIP_TICK_SERIAL)
-    int64_t      coh_regroup_key[4] = {-1, -1, -1, -1}; int coh_regroup_age = 0;   // what the last regrouping was built for, ticks since
-    // the snapshot a prefetch was started for: everything the side streams baked into their results
-    struct { bool valid; const float *pos_xz, *vel_xz, *radius, *arrival_sink_xz; const uint32_t *flags;
-             const uint8_t *state, *arrival_flags; const int32_t *flock_members, *flock_offsets;
-             int n_ents, n_flocks, hz, work_begin, work_end;
-             struct nh_grid_store { int32_t origin_x, origin_y; int grid_w, grid_h; } g;
-             } pre = {};
-    // optional per-kernel-group timing of the agent step (navhip_set_profiling)
-    bool         profiling = false;
-    hipEvent_t   ev[6] = {};   // start | hash built | neighbour walk | cohesion | regroup | finish
-    bool         ev_valid = false;
+    nh_buf       state_arrived, state_arrived_n;   // state_kernels.hip, navhip_state_update_dev: {x, z, radius, uid} of every
+                                               // flock's ARRIVED members, compacted; their count per flock
+    nh_step_state step;                 // the agent step: its scratch and what it remembers between calls (step_api.hip)
     std::string  last_error;
     struct nh_handover *ho = nullptr;    // hand-overs between the step's streams through device memory (stream_set.hip) or NULL
     struct nh_pool  *pool = nullptr;     // resident flow-field pool (navhip_pool_*, pool_api.hip) or NULL
@@ -255,13 +280,10 @@ static inline void nh_fill_map_view(const navhip_ctx *ctx, nh_map_view *mv)
 // every device buffer of the context that nh_ensure grows, for navhip_ctx_destroy
 template<class F> static inline void nh_ctx_each_buf(navhip_ctx *ctx, F f)
 {
-    nh_buf *one[] = {&ctx->d_reqs, &ctx->d_dirs, &ctx->d_integ, &ctx->d_dirty_list, &ctx->midrec, &ctx->coh, &ctx->coh_plan,
-                     &ctx->gen_list};
+    nh_buf *one[] = {&ctx->d_reqs, &ctx->d_dirs, &ctx->d_integ, &ctx->d_dirty_list, &ctx->gen_list, &ctx->state_arrived,
+                     &ctx->state_arrived_n};
     for(nh_buf *b : one) f(*b);
-    for(auto &b : ctx->sp) f(b);
-    for(auto &b : ctx->nbr) f(b);
-    for(auto &b : ctx->arrived) f(b);
-    for(auto &b : ctx->wl) f(b);
+    for(auto &b : ctx->step.buf) f(b);
     for(auto &b : ctx->stage) f(b);
 }
 
@@ -278,7 +300,7 @@ int         nh_streams_for(navhip_ctx *ctx, hipStream_t main, hipStream_t out[NH
 hipStream_t nh_stream_partial_for(navhip_ctx *ctx, hipStream_t main, int cu_begin, int cu_count);   // nullptr: ctx->last_error says why
 bool        nh_streams_alive(int device);
 void        nh_streams_forget(int device, hipStream_t s);
-int         nh_prepare_step_streams(navhip_ctx *ctx, hipStream_t main);      // the side streams of steps whose main chain runs on `main`
+int         nh_ensure_side_streams(navhip_ctx *ctx, hipStream_t main);       // the side streams of steps whose main chain runs on `main` (step_api.hip)
 
 // a number for a word, as a kernel argument: stored by a kernel that FOLLOWS the producer on its stream (its first
 // workgroup, when it starts).  flag == nullptr: nobody waits.
@@ -316,11 +338,16 @@ int32_t  nh_handover_seq(navhip_ctx *ctx, int flag);                            
 void     nh_handover_wait_for(navhip_ctx *ctx, int flag, int32_t want, hipStream_t consumer); // ... of an earlier one (nh_handover_seq then)
 bool     nh_handover_failed(navhip_ctx *ctx);                                   // a wait gave up: ctx->last_error says so
 
-// pool_api.hip <-> navhip_api.hip
+// pool_api.hip, state_kernels.hip, step_api.hip <-> navhip_api.hip
 extern "C" int nh_validate_field_reqs(navhip_ctx *ctx, const navhip_field_req *reqs, int n);   /* (library internal) */
 int  navhip_build_fields_slots_dev(navhip_ctx *ctx, const navhip_field_req *dev_reqs, int n, uint8_t *dev_fields,
                                    const int32_t *dev_slots, hipStream_t s);
 int  nh_ensure(navhip_ctx *ctx, nh_buf &b, size_t need);          // b holds at least `need` bytes (contents are not kept)
+int  nh_ensure_buf(navhip_ctx *ctx, nh_buf &b, size_t need);      // the step's scratch and the staging slots: at least 16 bytes, a buffer that moved is counted
+// step_api.hip: a host array copied to its staging slot (*dst: the device copy, NULL stays NULL); the world's arrays, row
+// by row of nh_world_rows, `only`: just these members (their offsets)
+int  nh_stage_in(navhip_ctx *ctx, nh_stage_slot slot, const void *host, size_t bytes, const void **dst, hipStream_t s);
+int  nh_stage_world(navhip_ctx *ctx, const navhip_world *w, navhip_world *d, hipStream_t s, std::initializer_list<size_t> only = {});
 int  nh_stage_reserve(navhip_ctx *ctx, nh_stage_slot slot, size_t bytes, void **dev);
 void nh_async_destroy(navhip_ctx *ctx);
 void nh_async_invalidate_static(navhip_ctx *ctx);   // the staging buffers were used by someone else

@@ -723,7 +723,7 @@ bool sk_check_gate(const navhip_world *w, const navhip_gate_in *in)
     return !in->interp_from_xz || (w->radius && w->flags);
 }
 
-// navhip_state_in inside a pass (new_pos_xz and vdes_xz are the gate's); navhip_state_update_dev checks the same and those two
+// navhip_state_in inside a pass (new_pos_xz and vdes_xz are the gate's); navhip_state_update_dev checks this and those two
 bool sk_check_state(const navhip_world *w, const navhip_state_in *in)
 {
     return w->pos_xz && w->radius && w->flags && w->state && w->flock
@@ -843,6 +843,76 @@ int navhip_heading_gate(navhip_ctx *ctx, const navhip_world *w, const navhip_gat
     int rc = P.reserve(ctx, NH_STAGE_STATE_ARENA);
     if(!rc) rc = P.upload(ctx, s);
     if(!rc) rc = navhip_heading_gate_dev(ctx, &d, &di, d_vel, d_pos, d_gate, s);
+    if(!rc) rc = P.download(ctx, s);
+    return rc;
+}
+
+// k_state_update and k_arrived_compact (agent_kernels.hip) on device arrays
+int navhip_state_update_dev(navhip_ctx *ctx, const navhip_world *w, const navhip_state_in *in, uint8_t *out_state,
+                            uint8_t *out_flags, void *stream)
+{
+    if(!ctx || !w || !in || !out_state || !out_flags || w->n_ents < 0) return NAVHIP_ERR_INVALID;
+    if(w->n_ents == 0) return NAVHIP_OK;
+    if(!sk_check_state(w, in) || !in->new_pos_xz || !in->vdes_xz) return NAVHIP_ERR_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = nh_refresh_derived(ctx, ctx->stream);
+    if(rc) return rc;
+    nh_step_params P;
+    sk_map_view(ctx, w, &P);
+    P.n_flocks = w->n_flocks;
+    if(!sk_work_range(w, &P.work_begin, &P.work_end)) return NAVHIP_ERR_INVALID;
+    P.pos_xz = w->pos_xz; P.radius = w->radius; P.flags = w->flags; P.state = w->state; P.flock = w->flock;
+    P.flock_target_xz = w->flock_target_xz; P.flock_offsets = w->flock_offsets; P.flock_members = w->flock_members;
+    // (scratch of the arrived-flock-mate rule: the ARRIVED members of every flock, compacted -- every entity belongs to at
+    // most one flock)
+    rc = nh_ensure_buf(ctx, ctx->state_arrived, 16 * (size_t)w->n_ents);
+    if(!rc) rc = nh_ensure_buf(ctx, ctx->state_arrived_n, 4 * (size_t)(w->n_flocks > 0 ? w->n_flocks : 1));
+    if(rc) return rc;
+    nh_launch_state_update(P, *in, (float4*)ctx->state_arrived.p, (int32_t*)ctx->state_arrived_n.p, out_state, out_flags,
+                           stream ? (hipStream_t)stream : ctx->stream);
+    HIPCHK(ctx, hipGetLastError());
+    return NAVHIP_OK;
+}
+
+int navhip_state_update(navhip_ctx *ctx, const navhip_world *w, const navhip_state_in *in, uint8_t *out_state, uint8_t *out_flags)
+{
+    if(!ctx || !w || !in || !out_state || !out_flags) return NAVHIP_ERR_INVALID;
+    if(w->n_ents <= 0) return w->n_ents == 0 ? NAVHIP_OK : NAVHIP_ERR_INVALID;
+    if(w->n_flocks > 0 && (!w->flock_offsets || !in->flock_tiles_off)) return NAVHIP_ERR_INVALID;
+    int b, e;
+    if(!sk_work_range(w, &b, &e)) return NAVHIP_ERR_INVALID;
+    sk_dims D = sk_dims_of(w, b, e);
+    const size_t n = (size_t)w->n_ents, F = D.len[SK_PER_FLOCK];
+    D.len[SK_PER_TILE] = F ? (size_t)in->flock_tiles_off[F] : 0;
+    if(F && (size_t)w->flock_offsets[F] > n) {     // (an entity belongs to at most one flock: the scratch of the arrived-mate rule is sized by it)
+        ctx->last_error = "navhip_state_update: more flock members than entities";
+        return NAVHIP_ERR_INVALID;
+    }
+    D.on[SK_SKIP] = in->skip != nullptr;
+    // (no destination has island tiles: the kernel still wants a pointer of its own -- nothing is read from it, and none
+    // need be given)
+    D.pad = 4;
+    // (what is staged below is never NULL on the device: an array the caller left out is refused here)
+    if(!in->new_pos_xz || !in->vdes_xz
+    || (F && (!in->flock_layer || !in->flock_nearest_xz || (!in->flock_tiles && D.len[SK_PER_TILE])))) return NAVHIP_ERR_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    // the arrays of the snapshot that k_state_update reads: the world's own staging slots (nh_world_rows)
+    navhip_world d;
+    int rc = nh_stage_world(ctx, w, &d, s, {SK_W(pos_xz), SK_W(radius), SK_W(flags), SK_W(state), SK_W(flock), SK_W(flock_target_xz),
+                                            SK_W(flock_offsets), SK_W(flock_members)});
+    if(rc) return rc;
+    // navhip_state_in and the two results: one copy per row
+    sk_plan P;
+    navhip_state_in di = {};
+    sk_stage(P, sk_state_rows, in, &di, D);
+    uint8_t *d_state, *d_flags;
+    P.out(P.scratch(n, (void**)&d_state), out_state, 1, D.lo, D.cnt);
+    P.out(P.scratch(n, (void**)&d_flags), out_flags, 1, D.lo, D.cnt);
+    rc = P.reserve(ctx, NH_STAGE_STATE_ARENA);
+    if(!rc) rc = P.upload(ctx, s);
+    nh_async_invalidate_static(ctx);
+    if(!rc) rc = navhip_state_update_dev(ctx, &d, &di, d_state, d_flags, s);
     if(!rc) rc = P.download(ctx, s);
     return rc;
 }

@@ -109,9 +109,9 @@ static int compute_plain(navhip_tick *T)
         RCCHK(build_fields(T, T->pool[0], T->s));
         if(T->d.dev_moves) RCCHK(navhip_clear_changed(ctx, (void*)T->s));
         if(T->comm_pending) HIPCHK(ctx, hipStreamWaitEvent(T->s, T->ev_comm, 0));
-        ctx->serial_step = true;
+        ctx->step.serial_step = true;
         int rc = navhip_agent_step_dev(ctx, w, &T->O[p], (void*)T->s);
-        ctx->serial_step = false;
+        ctx->step.serial_step = false;
         if(rc) return rc;
         T->step_flagged = false;
         if(T->pipelined) HIPCHK(ctx, hipEventRecord(T->ev_step, T->s));
@@ -134,7 +134,7 @@ static int compute_plain(navhip_tick *T)
         if(T->comm_pending) HIPCHK(ctx, hipStreamWaitEvent(T->s, T->ev_comm, 0));   // the other ranks' rows of the snapshot
         RCCHK(navhip_agent_step_dev(ctx, w, &T->O[p], (void*)T->s));
         // (a step that forked has said in device memory that it ended: the exchange waits for that word, not for an event)
-        T->step_flagged = ctx->step_end_signalled;
+        T->step_flagged = ctx->step.step_end_signalled;
         if(T->pipelined && !T->step_flagged) HIPCHK(ctx, hipEventRecord(T->ev_step, T->s));
         // the fields of the NEXT tick: enqueued behind the step -- the step's own wait for the cohesion term is the
         // launch that says "the neighbour walk is done" -- and started by the device as soon as that is so
@@ -239,7 +239,7 @@ int navhip_tick_create(navhip_ctx *ctx, const navhip_tick_desc *desc, navhip_tic
     T->comm = (hipStream_t)desc->comm_stream;
     if(!T->comm && T->pipelined) T->comm = own[NH_STREAM_COMM];
     // (the step's side streams are chosen for THIS stream, whatever stream a prefetch runs on)
-    if(nh_prepare_step_streams(ctx, T->s) != NAVHIP_OK) { navhip_tick_destroy(T); return NAVHIP_ERR_DEVICE; }
+    if(nh_ensure_side_streams(ctx, T->s) != NAVHIP_OK) { navhip_tick_destroy(T); return NAVHIP_ERR_DEVICE; }
     hipEvent_t *evs[] = {&T->ev_fields[0], &T->ev_fields[1], &T->ev_step, &T->ev_comm, &T->ev_tmp};
     for(hipEvent_t *e : evs) if(hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return fail("navhip_tick_create: event");
     if(T->time_fields)

@@ -195,8 +195,15 @@ def clearpath_team(ent, des_v, dyn, n_dyn, stat, n_stat):
 
 # ---- the WHOLE library on the emulator: every translation unit of csrc/ compiled for the host against fakehip/ ----------
 EMU_LIB = os.path.join(HERE, "_navhip_emu.so")
-EMU_SOURCES = ["navhip_api", "pool_api", "field_kernels", "agent_kernels", "blocker_kernels", "los_kernels",
-               "region_kernels", "comm_api", "state_kernels", "tick_api", "stream_set"]
+def _emu_sources():
+    """The translation units of the library: the list permafrost_engine_amd/build.py compiles, without the suffix."""
+    import importlib
+    import sys
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    return [os.path.splitext(s)[0] for s in importlib.import_module("permafrost_engine_amd.build").SOURCES]
+
+
 # the two statements of the device sources a host compiler cannot take (a register clobber that pins the allocation of
 # k_cp_rows; an unsized extern array for dynamic LDS) -- replaced in the copies that are compiled, nothing else is
 _EMU_PATCHES = [
@@ -219,7 +226,7 @@ def build_navhip_emu():
         return EMU_LIB
     os.makedirs(src_dir, exist_ok=True)
     objs = []
-    for name in EMU_SOURCES:
+    for name in _emu_sources():
         text = open(os.path.join(CSRC, name + ".hip")).read()
         for old, new in _EMU_PATCHES:
             text = text.replace(old, new)

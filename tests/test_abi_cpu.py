@@ -372,6 +372,53 @@ def test_staging_tables_cover_every_array_and_slots_are_named():
     assert not hits, "staging slots indexed by number:\n" + "\n".join(hits)
 
 
+# the members of navhip_ctx that were the agent step's state between calls before struct nh_step_state held them
+OLD_STEP_STATE = ("aux", "aux_main", "ev_regroup", "snapshot_held", "join0_signalled", "lists_signalled", "start_flag", "start_seq",
+                  "step_end_signalled", "step_end_on", "front_stream", "regroup_pending", "serial_step", "coh_flocks", "coh_members",
+                  "coh_parity", "coh_unique", "coh_regroup_key", "coh_regroup_age", "scratch_moves", "wl_parity", "lists_pinned",
+                  "sp_builds", "pre", "profiling", "ev", "ev_valid")
+
+
+def test_step_host_code_is_one_unit_with_named_scratch_and_one_state_struct():
+    """The host side of the agent step is csrc/step_api.hip, a unit without kernels; its scratch is ctx->step.buf[], one
+    buffer per name of enum nh_step_buf, never indexed by a bare number; what the step keeps between calls is struct
+    nh_step_state and nothing of it is left in navhip_ctx; navhip_state_update stages through the state unit's plan, and
+    its eight staging slots are gone."""
+    csrc = os.path.join(ROOT, "permafrost-engine_amd", "csrc")
+    strip = lambda s: re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", s, flags=re.S))      # noqa: E731
+    internal = strip(open(os.path.join(csrc, "navhip_internal.h")).read())
+    # scratch arrays of the step, under their old names and the new one, indexed by a digit
+    bare = re.compile(r"\b(?:sp|nbr|wl|arrived|buf)\[[0-9]")
+    hits, sin = [], []
+    for f in sorted(os.listdir(csrc)):
+        for i, line in enumerate(open(os.path.join(csrc, f), errors="replace"), 1):
+            if bare.search(line):
+                hits.append("%s:%d: %s" % (f, i, line.strip()))
+            if "NH_STAGE_SIN_" in line:
+                sin.append("%s:%d" % (f, i))
+    assert not hits, "step scratch indexed by number:\n" + "\n".join(hits)
+    assert not sin, sin
+    names = re.search(r"enum nh_step_buf \{(.*?)\};", internal, re.S).group(1)
+    names = re.findall(r"\b(NH_SB_\w+)", names)
+    assert len(names) == len(set(names)) == 19 and names[-1] == "NH_SB_COUNT"         # 10 hash + 3 walk + midrec + 2 lists + 2 cohesion
+    step_src = open(os.path.join(csrc, "step_api.hip")).read()
+    assert "__global__" not in step_src and "hipLaunchKernelGGL" not in step_src
+    for moved in ("navhip_agent_prefetch_dev_ex", "navhip_agent_step_dev", "navhip_stream_wait_stage", "navhip_agent_step",
+                  "navhip_spatial_query", "navhip_step_lists_peek"):
+        assert re.search(r"^int %s\(" % moved, step_src, re.M), moved
+        assert not re.search(r"^int %s\(" % moved, open(os.path.join(csrc, "navhip_api.hip")).read(), re.M), moved
+    assert re.search(r"^int navhip_state_update\(", open(os.path.join(csrc, "state_kernels.hip")).read(), re.M)
+    # every old member: declared inside struct nh_step_state, named nowhere else in the header (`ev` is also what struct
+    # nh_handover calls its events: for that one name, nowhere else in navhip_ctx)
+    m = re.search(r"struct nh_step_state \{(.*?)\n\};", internal, re.S)
+    state, rest = m.group(1), internal[:m.start()] + internal[m.end():]
+    ctx_body = re.search(r"struct navhip_ctx \{(.*?)\n\};", internal, re.S).group(1)
+    assert re.search(r"\bnh_step_state\s+step\s*;", ctx_body)
+    for name in OLD_STEP_STATE:
+        assert re.search(r"\b%s\b" % name, state), name
+        assert not re.search(r"\b%s\b" % name, ctx_body if name == "ev" else rest), name
+
+
 def test_state_staging_tables_cover_every_array():
     """csrc/state_kernels.hip stages the input and output structs of the state half of the tick from ONE list per
     struct (sk_gate_rows, sk_state_rows, sk_aux_rows, sk_pass_out_rows, sk_settle_in_rows, sk_settle_out_rows): each

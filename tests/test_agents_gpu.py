@@ -449,6 +449,90 @@ def test_lane_grouping_carried_between_ticks_is_only_a_hint(navlib):
     shared.close()
 
 
+def _device_snapshot(navlib, arrays):
+    """(navhip_world over device copies of `arrays`, device outputs, keepalive, fetch()).  Device memory is torch's -- or,
+    where the library named by NAVHIP_LIB is the host emulator, page-locked memory of the library's own (navhip_host_alloc):
+    a kernel may be handed that on a GPU too, so the emulator's strict pointer check accepts it, whatever the heap
+    addresses were used for by the tests before."""
+    import os
+    n = len(arrays["pos_xz"])
+    arrays = {k: None if arrays.get(k) is None else np.ascontiguousarray(arrays[k], dtype=dt) for k, dt in navlib._WORLD_ARRAYS}
+    outs = {"vel_xz": ((n, 2), np.float32), "new_pos_xz": ((n, 2), np.float32), "vdes_xz": ((n, 2), np.float32),
+            "vpref_xz": ((n, 2), np.float32), "status": ((n,), np.uint8)}
+    bufs = []                           # (page-locked stand-ins, freed by the caller: navlib.host_free)
+    if os.path.basename(os.environ.get("NAVHIP_LIB", "")) == "_navhip_emu.so":
+
+        def pinned(shape, dt):
+            bufs.append(navlib.host_alloc(max(int(np.prod(shape)) * np.dtype(dt).itemsize, 16)))
+            a = np.frombuffer(bufs[-1], dtype=dt, count=int(np.prod(shape))).reshape(shape)
+            a[...] = 0
+            return a
+        dev = {}
+        for k, a in arrays.items():
+            dev[k] = None if a is None else pinned(a.shape, a.dtype)
+            if a is not None:
+                dev[k][...] = a
+        o = {k: pinned(shape, dt) for k, (shape, dt) in outs.items()}
+        ptr = lambda a: a.ctypes.data                                         # noqa: E731
+        fetch = lambda: {k: a.copy() for k, a in o.items()}                   # noqa: E731
+    else:
+        import torch
+        view = lambda a: a.view(np.int32) if a.dtype == np.uint32 else a      # noqa: E731  (torch has no uint32)
+        dev = {k: None if a is None else torch.from_numpy(view(np.ascontiguousarray(a))).cuda() for k, a in arrays.items()}
+        o = {k: torch.zeros(shape, dtype=getattr(torch, np.dtype(dt).name), device="cuda") for k, (shape, dt) in outs.items()}
+        torch.cuda.synchronize()
+        ptr = lambda a: a.data_ptr()                                          # noqa: E731
+
+        def fetch():
+            torch.cuda.synchronize()
+            return {k: a.cpu().numpy() for k, a in o.items()}
+    w, keep = navlib.make_world(2, 2, dev)
+    so = navlib.StepOut()
+    for k, a in o.items():
+        setattr(so, k, ptr(a))
+    return w, so, (keep, dev, o, bufs), fetch
+
+
+def test_step_scratch_regrows_and_is_reused_between_snapshots(navlib):
+    """Every named buffer of the step's scratch (csrc/step_api.hip) on ONE context: snapshot A (600 agents, 4 flocks), B
+    (1 500 agents, 9 flocks), A again -- A -> B regrows every buffer and resets the lane grouping, B -> A steps in
+    oversized ones; 600 and 1 500 lie on either side of the one-workgroup hash build (SP_SMALL_N = 1 024).  First each
+    through navhip_agent_prefetch_dev (FRONT_INLINE | SNAPSHOT_HELD) and the step that joins it, on the library's main
+    stream; then the same three through the plain device step.  All five outputs of every step are bit-identical to the
+    same snapshot stepped in a context of its own: a wrong size or a swapped name shows here (and on the emulator, where
+    an allocation ends at an unmapped page, before a GPU sees it)."""
+    grid, nav = cases.ref_nav_for(2, 2, seed=21)
+    snaps = {}
+    for name, n, k, seed in (("A", 600, 4, 5), ("B", 1500, 9, 6)):
+        world = cases.make_agents(grid, n, k, seed=seed, clustered=False)
+        vdes = np.zeros((n, 2), np.float32)
+        vdes[:, 0] = 1.0
+        w, so, keep, fetch = _device_snapshot(navlib, cases.step_arrays(world, vdes))
+        fresh = _upload(navlib, nav)
+        fresh.agent_step_dev(w, so, stream=fresh.stream_main())
+        fresh.sync()
+        exp = fetch()
+        fresh.close()
+        assert np.abs(exp["vel_xz"]).max() > 0
+        snaps[name] = (w, so, keep, fetch, exp)
+    shared = _upload(navlib, nav)
+    s = shared.stream_main()
+    for prefetch in (True, False):
+        for name in "ABA":
+            w, so, keep, fetch, exp = snaps[name]
+            if prefetch:
+                shared.agent_prefetch_dev(w, stream=s, flags=navlib.PREFETCH_FRONT_INLINE | navlib.PREFETCH_SNAPSHOT_HELD)
+            shared.agent_step_dev(w, so, stream=s)
+            shared.sync()
+            got = fetch()
+            for k in ("vel_xz", "new_pos_xz", "vdes_xz", "vpref_xz", "status"):
+                assert np.array_equal(got[k].view(np.uint8), exp[k].view(np.uint8)), (prefetch, name, k)
+    shared.close()
+    for _, _, keep, _, _ in snaps.values():
+        for b in keep[-1]:
+            navlib.host_free(b)
+
+
 @pytest.mark.parametrize("epoch", [0, 7])
 def test_slab_lane_grouping_survives_membership_changes(navlib, epoch):
     """A rank that steps a uid slab gives cohesion lanes to the slab's members only and carries that grouping to
