@@ -263,8 +263,11 @@ class OracleNav:
         return a, c, s
 
 
-def spatial_query(chunk_w, chunk_h, pos_xz, query_xz, rng, maxout):
+def spatial_query(chunk_w, chunk_h, pos_xz, query_xz, rng, maxout, bounds=None):
+    """bounds: (xmin, xmax, zmin, zmax) of the index instead of the map's (bg_ent_init takes any)."""
     w, keep = make_world(chunk_w, chunk_h, {"pos_xz": np.ascontiguousarray(pos_xz, np.float32)})
+    if bounds is not None:
+        w.grid_xmin, w.grid_xmax, w.grid_zmin, w.grid_zmax = (float(b) for b in bounds)
     q = np.ascontiguousarray(query_xz, np.float32).reshape(-1, 2)
     counts = np.zeros(len(q), np.int32)
     ids = np.zeros((len(q), maxout), np.uint32)

@@ -608,9 +608,12 @@ def _ctx_agent_prefetch_dev(self, world, stream=None, flags=0):
               "navhip_agent_prefetch_dev")
 
 
-def _ctx_spatial_query(self, pos_xz, query_xz, rng, maxout):
-    """G_Pos_EntsInCircleFrom candidate lists (bitmap_grid.h:1376 order) for each query."""
+def _ctx_spatial_query(self, pos_xz, query_xz, rng, maxout, bounds=None):
+    """G_Pos_EntsInCircleFrom candidate lists (bitmap_grid.h:1376 order) for each query.
+    bounds: (xmin, xmax, zmin, zmax) of the index instead of the map's (the C ABI takes any)."""
     w, keep = make_world(self.w, self.h, {"pos_xz": np.ascontiguousarray(pos_xz, np.float32)})
+    if bounds is not None:
+        w.grid_xmin, w.grid_xmax, w.grid_zmin, w.grid_zmax = (float(b) for b in bounds)
     q = np.ascontiguousarray(query_xz, np.float32).reshape(-1, 2)
     counts = np.zeros(len(q), np.int32)
     ids = np.zeros((len(q), maxout), np.uint32)

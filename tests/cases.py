@@ -505,3 +505,203 @@ def arrival_zone_at(grid, cell, rad, rng, fill, active_row, num_rows, unit_radiu
             "unit_radius": float(unit_radius), "fill_frac": fill, "active_row": active_row, "num_rows": num_rows,
             "slots_xz": slots, "slot_ring": rng.randint(0, num_rows, len(slots)).astype(np.int32), "region_xz": region_xz,
             "tiles": tiles}
+
+
+# ---------------------------------------------------------------------------------------------
+# the spatial index (bitmap_grid.h): its geometry as plain arithmetic, and worlds for it
+# ---------------------------------------------------------------------------------------------
+def sp_scale(v):
+    """BG_SCALE_F (bitmap_grid.h:196): lrintf(v * 256.0f) -- a float32 product rounded half to even; int64 out."""
+    return np.rint(np.asarray(v, np.float32) * np.float32(256.0)).astype(np.int64)
+
+
+def sp_geometry(bounds):
+    """bg_<name>_init (bitmap_grid.h:959): (origin_x, origin_y, grid_w, grid_h) in x256 fixed point and 16-wu cells."""
+    ox, x1, oy, y1 = (int(sp_scale(b)) for b in bounds)
+    assert x1 > ox and y1 > oy
+    return ox, oy, max(1, (x1 - ox + 4095) >> 12), max(1, (y1 - oy + 4095) >> 12)
+
+
+def sp_extent(bounds, query_xz, r):
+    """_bg_cell_extent and the wide rule of bg_<name>_inrange_circle (bitmap_grid.h:1236, 1391-1399) for every query:
+    dict of arrays -- miss (the box misses the grid, or r < 0), cx_lo .. cy_hi (fine cells), wide, ncx / ncy (coarse 8 x 8
+    blocks the box touches per row / column) and ir (scalar)."""
+    ox, oy, gw, gh = sp_geometry(bounds)
+    q = np.asarray(query_xz, np.float32).reshape(-1, 2)
+    icx, icy, ir = sp_scale(q[:, 0]), sp_scale(q[:, 1]), int(sp_scale(r))
+    miss = (icx + ir < ox) | (icy + ir < oy) | (icx - ir >= ox + (gw << 12)) | (icy - ir >= oy + (gh << 12))
+    if np.float32(r) < 0:
+        miss = np.ones(len(q), bool)
+    cx_lo = np.clip((icx - ir - ox) >> 12, 0, None)
+    cy_lo = np.clip((icy - ir - oy) >> 12, 0, None)
+    cx_hi = np.clip((icx + ir - ox) >> 12, None, gw - 1)
+    cy_hi = np.clip((icy + ir - oy) >> 12, None, gh - 1)
+    wide = ~miss & ((cx_hi - cx_lo + 1) * (cy_hi - cy_lo + 1) * 4 >= gw * gh * 3)
+    # (on_rule: extent * 4 == total * 3 exactly -- wide by the rule's `>=` alone)
+    on_rule = ~miss & ((cx_hi - cx_lo + 1) * (cy_hi - cy_lo + 1) * 4 == gw * gh * 3)
+    return {"miss": miss, "cx_lo": cx_lo, "cx_hi": cx_hi, "cy_lo": cy_lo, "cy_hi": cy_hi, "wide": wide, "ir": ir, "on_rule": on_rule,
+            "ncx": (cx_hi >> 3) - (cx_lo >> 3) + 1, "ncy": (cy_hi >> 3) - (cy_lo >> 3) + 1}
+
+
+def sp_centre(bounds):
+    """The whole-wu point the worlds call the centre of their grid."""
+    xmin, xmax, zmin, zmax = (float(np.float32(b)) for b in bounds)
+    return float(np.floor((xmin + xmax) / 2)), float(np.floor((zmin + zmax) / 2))
+
+
+def _sp_wide_threshold(bounds, q):
+    """(r_below, r_above): the largest radius whose query about q is NOT wide and the smallest that is (one x256 step
+    apart; both exact in float32), by bisection on the rule of sp_extent -- the box only grows with r."""
+    lo, hi = 0, 1 << 22
+    assert not sp_extent(bounds, q, 0.0)["wide"][0] and sp_extent(bounds, q, hi / 256.0)["wide"][0]
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if sp_extent(bounds, q, mid / 256.0)["wide"][0]:
+            hi = mid
+        else:
+            lo = mid
+    return lo / 256.0, hi / 256.0
+
+
+def _sp_world(bounds, n, seed, parts=(), big_radii=(200.0, 400.0), many=False):
+    """One world of exactly n entities: `parts` (arrays of points) + the edge points every case carries + a uniform
+    background, uids shuffled.  Returns (pos_xz, query_xz, [(range, cap), ...])."""
+    rng = np.random.RandomState(seed)
+    ox, oy, gw, gh = sp_geometry(bounds)
+    xmin, xmax, zmin, zmax = (float(np.float32(b)) for b in bounds)
+    xc, zc = sp_centre(bounds)
+    fx = lambda i: i / 256.0                                       # (fixed point -> wu: exact in float32 below 2^15 wu)
+    # the radii: the fixed ones that are not wide about the centre of this grid, the two around its wide threshold, 1400
+    centre = np.array([[xc, zc]], np.float32)
+    below, above = _sp_wide_threshold(bounds, centre)
+    radii = [0.0, 10.0, 30.0, 62.5, 62.51] + [r for r in big_radii if r < below]
+    # exact-distance ties about the integer point Q: an entity AT distance r on the axis, one a x256 step beyond it,
+    # and the 3-4-5 point of r = 30
+    Q = (xc + 3.0, zc - 2.0)
+    ties = [Q, (Q[0] + 18.0, Q[1] + 24.0)]
+    for r in radii[1:] + [below]:
+        ir = int(sp_scale(r))
+        ties += [(Q[0] + fx(ir), Q[1]), (Q[0], Q[1] - fx(ir + 1))]
+    # cell boundaries (multiples of 16 wu from the origin) and the last x256 step before them
+    edge = []
+    for kx, ky in ((1, 1), (gw // 2, gh // 2), (gw - 1, gh - 1), (gw // 2, 0), (0, gh // 2), (min(8, gw - 1), min(8, gh - 1))):
+        edge += [(fx(ox + 4096 * kx), fx(oy + 4096 * ky)), (fx(ox + 4096 * kx - 1), fx(oy + 4096 * ky - 1))]
+    # k/512: ties of the x256 rounding, towards an even and towards an odd step, on both sides of zero
+    for m in (0, 1, 2, 3, -1, -2, -3, -4):
+        edge.append((xc - 20.0 + (2 * m + 1) / 512.0, zc + 9.0 - (2 * m + 1) / 512.0))
+    edge += [((2 * m + 1) / 512.0, -(2 * m + 1) / 512.0) for m in (0, 1, -1, -2)
+             if xmin < -1 and xmax > 1 and zmin < -1 and zmax > 1]
+    # the four corners, points exactly on xmax / zmax
+    edge += [(xmin, zmin), (xmin, zmax), (xmax, zmin), (xmax, zmax), (xmax, zc + 1.5), (xc - 2.5, zmax)]
+    # up to 40 wu OUTSIDE the bounds: bg_ent_insert (bitmap_grid.h:1110) takes them -- _bg_cell_x_from_int clamps the cell
+    # index into the grid, nothing asserts or rejects -- so they sit in border cells with their true coordinates
+    edge += [(xmax + 40.0, zc), (xmin - 39.5, zc + 3.0), (xc, zmax + 17.0), (xc - 5.0, zmin - 40.0),
+             (xmin - 20.0, zmin - 20.0), (xmax + 0.00390625, zmax + 33.0)]
+    if many:
+        # ... and two far outside: farther from any query that reaches their border cell than a 32-bit square holds
+        edge += [(xmax + 200.0, zmin + 5.0), (xc + 7.0, zmax + 1000.0)]
+    fixed = np.concatenate([np.asarray(p, np.float64).reshape(-1, 2) for p in list(parts) + [ties, edge]])
+    assert len(fixed) <= n, (len(fixed), n)
+    back = np.stack([rng.uniform(xmin, xmax, n - len(fixed)), rng.uniform(zmin, zmax, n - len(fixed))], 1)
+    pos = np.concatenate([fixed, back])[rng.permutation(n)].astype(np.float32)
+    # queries: every k-th entity, the centres of the parts, corners + centre, the tie point, and points outside the grid
+    # at distances on either side of every radius
+    step = max(1, -(-n // 100))
+    qs = [pos[::step], [np.mean(np.asarray(p, np.float64).reshape(-1, 2), axis=0) for p in parts] or np.zeros((0, 2)),
+          [(xmin, zmin), (xmin, zmax), (xmax, zmin), (xmax, zmax), (xc, zc), Q]]
+    for d in (0.5, 8.0, 29.9, 30.0, 62.0, 199.0, 390.0, 525.0, 1390.0, 1401.0, 5000.0):
+        qs.append([(xmax + d, zc), (xc, zmin - d), (xmin - d, zmax + d)])
+    if gw % 4 == 0 and gh * 8 <= 1400:
+        # r = 1400 from beyond xmax: every row and exactly the last 3/4 of the columns -- extent * 4 == total * 3, wide
+        # by the `>=` of the rule alone -- and one column fewer
+        qs.append([(xmin + 1400.0 + 16.0 * (gw // 4) + 4.0, zc), (xmin + 1400.0 + 16.0 * (gw // 4) + 20.0, zc)])
+    query = np.concatenate([np.asarray(x, np.float64).reshape(-1, 2) for x in qs]).astype(np.float32)
+    assert len(query) <= 300, len(query)
+    over = n + 5                                                   # a cap no result can reach
+    pairs = [(0.0, 63), (0.0, 64), (0.0, 65), (10.0, 512), (10.0, 7), (10.0, 1), (30.0, 128), (30.0, 63), (30.0, 65),
+             (62.5, 128), (62.5, over), (62.51, 128), (62.51, 64)]
+    caps = {200.0: (512, 65), 400.0: (over, 64), 530.0: (512, 1)}
+    pairs += [(r, c) for r in radii[5:] for c in caps[r]]
+    pairs += [(below, over), (below, 128), (above, over), (above, 128), (1400.0, 256), (1400.0, over)]
+    # a negative range: bg_<name>_inrange_circle returns 0 for it before anything else (bitmap_grid.h:1380)
+    pairs.append((-1.0, 64))
+    return pos, query, pairs
+
+
+def _sp_in_cells(bounds, cells, per, rng):
+    """`per` points inside each of the fine cells `cells` (indices row-major)."""
+    ox, oy, gw, gh = sp_geometry(bounds)
+    c = np.repeat(np.asarray(cells), per)
+    ix = ox + (c % gw) * 4096 + rng.randint(1, 4095, len(c))
+    iy = oy + (c // gw) * 4096 + rng.randint(1, 4095, len(c))
+    return np.stack([ix, iy], 1) / 256.0
+
+
+_SPATIAL_CASES = None
+
+
+def spatial_cases():
+    """Worlds for the spatial index: {name: (bounds, pos_xz, query_xz, [(range, cap), ...])}, deterministic and built
+    once.  A cell is 16 wu, a coarse block 8 cells, a chunk 16 x 16 cells; bounds are map bounds (a multiple of 256 wu,
+    centred) except `ragged*`.  Every world but `one` carries points on cell boundaries, at the k/512 ties of the x256
+    rounding, on the corners and on xmax / zmax, up to 40 wu outside the bounds, and entities exactly at (and one step
+    beyond) every radius from an integer query point.  Radii per world: 0, 10, 30, 62.5 | 62.51 (either side of the
+    32-bit distance arm), 200 / 400 / 530 where a query about the centre is not wide with them, the two radii one
+    x256 step apart around the wide threshold of a central query, 1400, and a negative one."""
+    global _SPATIAL_CASES
+    if _SPATIAL_CASES is not None:
+        return _SPATIAL_CASES
+    from permafrost_engine_amd.navhip import grid_bounds
+    out = {}
+    # the smallest world
+    b = grid_bounds(1, 1)
+    out["one"] = (b, np.array([[3.0, -2.0]], np.float32),
+                  np.array([[3.0, -2.0], [0, 0], [13.0, -2.0], [13.00390625, -2.0], [-128, -128], [128, 128], [200, 0], [0, -2000]],
+                           np.float32),
+                  [(0.0, 1), (10.0, 1), (10.0, 64), (30.0, 128), (62.5, 7), (62.51, 7), (1400.0, 256), (-1.0, 64)])
+
+    def piles(rng):
+        # 300 entities inside ONE cell (x in [32, 48), z in [-80, -64)) and 70 at one identical point
+        return [np.stack([rng.uniform(32.1, 47.9, 300), rng.uniform(-79.9, -64.1, 300)], 1), np.tile([[-77.25, 33.5]], (70, 1))]
+
+    # the largest n of the one-workgroup build and the smallest n of the five-launch build, a cell of hundreds in both
+    out["small_full"] = (b,) + _sp_world(b, 1024, 11, piles(np.random.RandomState(1)))
+    out["large_min"] = (b,) + _sp_world(b, 1025, 12, piles(np.random.RandomState(2)))
+    # ncells = 8192 exactly: the one-workgroup build with all 32 chunks of its scan; 16 block columns (8 x 4) and 16
+    # block rows (4 x 8) under one non-wide query
+    for w, h in ((8, 4), (4, 8)):
+        b = grid_bounds(w, h)
+        rng = np.random.RandomState(13 + w)
+        out["small_cells_max_%dx%d" % (w, h)] = (b,) + _sp_world(
+            b, 1000, 14 + w, [rng.normal([w * 40.0, -h * 30.0], 9.0, (150, 2))], big_radii=(200.0, 400.0, 530.0))
+    # the five-launch build chosen by the cell count alone (10 240 cells)
+    b = grid_bounds(8, 5)
+    rng = np.random.RandomState(15)
+    out["large_by_cells"] = (b,) + _sp_world(b, 1000, 16, [rng.normal([-300.0, 100.0], 9.0, (150, 2))],
+                                             big_radii=(200.0, 400.0, 530.0))
+    # a background, two blobs, a cell of 300 and 70 entities on one point
+    b = grid_bounds(4, 4)
+    rng = np.random.RandomState(17)
+    pile = [np.stack([rng.uniform(160.1, 175.9, 300), rng.uniform(48.1, 63.9, 300)], 1), np.tile([[-77.25, 333.5]], (70, 1))]
+    out["blobs"] = (b,) + _sp_world(b, 3000, 18, [rng.normal([100, -200], 6.0, (400, 2)), rng.normal([-300, 250], 14.0, (300, 2))] + pile,
+                                    many=True)
+    # 512 x 512 cells = 1 024 scan blocks (k_sp_scan_add strides over the block sums four times): entities in the first
+    # and the last cells, on either side of cell 255 | 256 and of the first cell of the last scan block
+    b = grid_bounds(32, 32)
+    rng = np.random.RandomState(19)
+    nc = 512 * 512
+    marks = [0, 1, 2, 254, 255, 256, 257, 511, 512, nc - 513, nc - 258, nc - 257, nc - 256, nc - 255, nc - 3, nc - 2, nc - 1]
+    out["many_blocks"] = (b,) + _sp_world(
+        b, 4000, 20, [_sp_in_cells(b, marks[:9], 6, rng), _sp_in_cells(b, marks[9:], 6, rng),
+                      rng.normal([1000.0, -2500.0], 25.0, (500, 2)), rng.normal([-3900.0, 3900.0], 8.0, (200, 2))],
+        big_radii=(200.0, 400.0, 530.0))
+    # bounds that are no multiple of anything: 82 x 50 cells (the last coarse block column and row are 2 cells wide),
+    # 4 100 cells = 16 scan blocks + 4 cells; once with each build
+    b = (-100.3, 1207.9, -65.0, 720.6)
+    assert sp_geometry(b)[2:] == (82, 50)
+    rng = np.random.RandomState(21)
+    out["ragged"] = (b,) + _sp_world(b, 1500, 22, [rng.normal([1150.0, 680.0], 20.0, (300, 2)), rng.normal([400.0, 100.0], 7.0, (200, 2))],
+                                     many=True)
+    out["ragged_small"] = (b,) + _sp_world(b, 700, 23, [rng.normal([1180.0, 300.0], 15.0, (150, 2))])
+    _SPATIAL_CASES = out
+    return out

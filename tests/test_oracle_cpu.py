@@ -73,6 +73,37 @@ def test_spatial_query_restatement_matches_reference():
 
 
 @needs_ref
+@pytest.mark.parametrize("name", list(cases.spatial_cases()))
+def test_spatial_cases_restatement_matches_reference(name):
+    """Every world, radius and cap of cases.spatial_cases() (grid shapes, ragged bounds, entities outside the bounds,
+    exact-distance ties, caps around 64, the radii around the wide threshold, a negative range): counts and the first
+    `count` ids, in order."""
+    from tests import test_spatial_gpu as sp
+    bounds, pos, query, pairs = cases.spatial_cases()[name]
+    for r, cap in pairs:
+        ec, ei = pfref.spatial_query(bounds, pos, query, r, cap)
+        gc, gi = navoracle.spatial_query(1, 1, pos, query, r, cap, bounds=bounds)
+        assert sp.lists_differ(gc, gi, ec, ei) is None, (name, r, cap, sp.lists_differ(gc, gi, ec, ei))
+
+
+@pytest.mark.parametrize("name", list(cases.spatial_cases()))
+def test_spatial_cases_restatement_matches_brute_force(name):
+    """The same lists against the numpy model of tests/test_spatial_gpu.py, which shares no code with either oracle:
+    uncapped lists as SETS against |x_i - q|^2 <= r^2 in x256 fixed point, capped ones and a sample of the others in the
+    model's visiting order."""
+    from tests import test_spatial_gpu as sp
+    bounds, pos, query, pairs = cases.spatial_cases()[name]
+    for r, cap in pairs:
+        gc, gi = navoracle.spatial_query(1, 1, pos, query, r, cap, bounds=bounds)
+        sp.check_against_model(name, r, cap, gc, gi)
+
+
+def test_spatial_case_matrix_reaches_every_path():
+    from tests import test_spatial_gpu as sp
+    sp.assert_covered()
+
+
+@needs_ref
 @pytest.mark.parametrize("seed,max_dyn,max_stat,spread", [(1, 6, 3, 9.0), (2, 32, 32, 9.5),
                                                          (3, 12, 0, 5.0), (4, 0, 12, 5.0), (5, 3, 3, 2.5)])
 def test_clearpath_restatement_matches_reference(seed, max_dyn, max_stat, spread):
