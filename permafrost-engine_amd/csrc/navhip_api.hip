@@ -654,13 +654,14 @@ int navhip_build_fields(navhip_ctx *ctx, const navhip_field_req *reqs, int n,
     int rc = nh_validate_field_reqs(ctx, reqs, n);
     if(rc) return rc;
     hipStream_t s = ctx->stream;
-    rc = nh_ensure(ctx, ctx->d_reqs, (size_t)n * sizeof(navhip_field_req));
-    if(!rc) rc = nh_ensure(ctx, ctx->d_dirs, (size_t)n * NH_CELLS);
-    if(!rc && out_integ) rc = nh_ensure(ctx, ctx->d_integ, (size_t)n * NH_CELLS * sizeof(float));
+    nh_buf &d_reqs = ctx->stage[NH_STAGE_CALL0], &d_dirs_buf = ctx->stage[NH_STAGE_CALL1], &d_integ_buf = ctx->stage[NH_STAGE_CALL2];
+    rc = nh_ensure_buf(ctx, d_reqs, (size_t)n * sizeof(navhip_field_req));
+    if(!rc) rc = nh_ensure_buf(ctx, d_dirs_buf, (size_t)n * NH_CELLS);
+    if(!rc && out_integ) rc = nh_ensure_buf(ctx, d_integ_buf, (size_t)n * NH_CELLS * sizeof(float));
     if(rc) return rc;
-    uint8_t *d_dirs = (uint8_t*)ctx->d_dirs.p;
-    float *d_integ = out_integ ? (float*)ctx->d_integ.p : nullptr;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->d_reqs.p, reqs, (size_t)n * sizeof(navhip_field_req),
+    uint8_t *d_dirs = (uint8_t*)d_dirs_buf.p;
+    float *d_integ = out_integ ? (float*)d_integ_buf.p : nullptr;
+    HIPCHK(ctx, hipMemcpyAsync(d_reqs.p, reqs, (size_t)n * sizeof(navhip_field_req),
                                hipMemcpyHostToDevice, s));
     bool any_inout = false;
     for(int i = 0; i < n; i++)      // skipped (IF_CHANGED) slots must come back unchanged too
@@ -669,7 +670,7 @@ int navhip_build_fields(navhip_ctx *ctx, const navhip_field_req *reqs, int n,
     if(any_inout)
         HIPCHK(ctx, hipMemcpyAsync(d_dirs, inout_dirs, (size_t)n * NH_CELLS,
                                    hipMemcpyHostToDevice, s));
-    rc = navhip_build_fields_dev(ctx, (const navhip_field_req*)ctx->d_reqs.p, n, d_dirs, d_integ, s);
+    rc = navhip_build_fields_dev(ctx, (const navhip_field_req*)d_reqs.p, n, d_dirs, d_integ, s);
     if(rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(inout_dirs, d_dirs, (size_t)n * NH_CELLS,
                                hipMemcpyDeviceToHost, s));

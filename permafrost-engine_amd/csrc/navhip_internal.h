@@ -27,6 +27,9 @@ static_assert(sizeof(navhip_los_req) == 16, "navhip_los_req must stay 16 bytes")
 
 struct nh_buf { void *p = nullptr; size_t cap = 0; };      // device memory, grown on demand (nh_ensure)
 
+// the granule of everything that is packed into a staging slab: every array starts on a multiple of 256 bytes
+static inline size_t nh_up256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
 // ctx->stage[]: the device copies of host buffers, one slot per PURPOSE.  Two purposes share a slot only when they are
 // the same data (the snapshot's positions, whoever stages them).  A slot in front of NH_STAGE_CALL0 may hold something a
 // later call reads in place (nh_async_resident and its reader, navhip_state_pass_resident) or a launch that is still
@@ -47,7 +50,7 @@ enum nh_stage_slot {
     // navhip_build_los_dev: the per-request overlay (the launch may still run when the call returns)
     NH_STAGE_LOS_OVERLAY,
     // call-local scratch of the host-pointer utilities that synchronise before they return and leave nothing behind:
-    // the ClearPath batches, navhip_region_lookup, navhip_spatial_query, navhip_build_los,
+    // the ClearPath batches, navhip_region_lookup, navhip_spatial_query, navhip_build_los, navhip_build_fields,
     // navhip_build_region_fields, navhip_blockers_circles
     NH_STAGE_CALL0, NH_STAGE_CALL1, NH_STAGE_CALL2, NH_STAGE_CALL3, NH_STAGE_CALL4, NH_STAGE_CALL5, NH_STAGE_CALL6,
     NH_STAGE_COUNT
@@ -246,7 +249,6 @@ struct navhip_ctx {
     navhip_layer layers[NAVHIP_NAV_LAYER_MAX];
     int          field_kernel_mode = 0;
     // scratch for the host-buffer entry points
-    nh_buf       d_reqs, d_dirs, d_integ;   // navhip_build_fields: requests, directions, integration values
     nh_buf       d_dirty_list;              // chunks whose derived masks are rebuilt
     nh_buf       gen_list;     // [2 + n] requests the BFS kernel left to k_field_generic: 2 counters, ids
     unsigned     gen_launches = 0; // parity selects the counter of a launch
@@ -261,7 +263,7 @@ struct navhip_ctx {
     std::string  last_error;
     struct nh_handover *ho = nullptr;    // hand-overs between the step's streams through device memory (stream_set.hip) or NULL
     struct nh_pool  *pool = nullptr;     // resident flow-field pool (navhip_pool_*, pool_api.hip) or NULL
-    struct nh_async *async = nullptr;    // state of navhip_agent_step_submit / _poll
+    struct nh_async *async = nullptr;    // state of navhip_agent_step_submit / _poll (submit_api.hip) or NULL
     struct nh_comm  *comm = nullptr;     // RCCL communicator of navhip_comm_* (comm_api.hip) or NULL
 };
 
@@ -280,8 +282,7 @@ static inline void nh_fill_map_view(const navhip_ctx *ctx, nh_map_view *mv)
 // every device buffer of the context that nh_ensure grows, for navhip_ctx_destroy
 template<class F> static inline void nh_ctx_each_buf(navhip_ctx *ctx, F f)
 {
-    nh_buf *one[] = {&ctx->d_reqs, &ctx->d_dirs, &ctx->d_integ, &ctx->d_dirty_list, &ctx->gen_list, &ctx->state_arrived,
-                     &ctx->state_arrived_n};
+    nh_buf *one[] = {&ctx->d_dirty_list, &ctx->gen_list, &ctx->state_arrived, &ctx->state_arrived_n};
     for(nh_buf *b : one) f(*b);
     for(auto &b : ctx->step.buf) f(b);
     for(auto &b : ctx->stage) f(b);
@@ -338,7 +339,7 @@ int32_t  nh_handover_seq(navhip_ctx *ctx, int flag);                            
 void     nh_handover_wait_for(navhip_ctx *ctx, int flag, int32_t want, hipStream_t consumer); // ... of an earlier one (nh_handover_seq then)
 bool     nh_handover_failed(navhip_ctx *ctx);                                   // a wait gave up: ctx->last_error says so
 
-// pool_api.hip, state_kernels.hip, step_api.hip <-> navhip_api.hip
+// pool_api.hip, submit_api.hip, state_kernels.hip, step_api.hip <-> navhip_api.hip
 extern "C" int nh_validate_field_reqs(navhip_ctx *ctx, const navhip_field_req *reqs, int n);   /* (library internal) */
 int  navhip_build_fields_slots_dev(navhip_ctx *ctx, const navhip_field_req *dev_reqs, int n, uint8_t *dev_fields,
                                    const int32_t *dev_slots, hipStream_t s);

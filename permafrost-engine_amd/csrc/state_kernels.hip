@@ -491,7 +491,7 @@ struct sk_plan {
     bool gather = false;                                            // pack(): the blocks lie behind the rows
     char *base = nullptr, *h_in = nullptr, *h_out = nullptr;
 
-    static size_t up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+    static size_t up(size_t bytes) { return nh_up256(bytes); }
     // pad: tail bytes of a row whose array may be empty, so that a kernel is never handed the next row's address as its own
     int in(const void *src, size_t bytes, size_t pad = 0, void **twin = nullptr)
     {

@@ -419,6 +419,29 @@ def test_step_host_code_is_one_unit_with_named_scratch_and_one_state_struct():
         assert not re.search(r"\b%s\b" % name, ctx_body if name == "ev" else rest), name
 
 
+def test_pool_and_submit_are_two_units_with_one_of_each_helper():
+    """csrc/pool_api.hip is the resident field pool and nothing else; the asynchronous host-buffer step, the page-locked
+    memory helpers and the one place that asks the runtime about a pointer are csrc/submit_api.hip, a unit without
+    kernels; navhip_build_fields stages in the call-local slots, so navhip_ctx keeps no scratch of its own for it."""
+    csrc = os.path.join(ROOT, "permafrost-engine_amd", "csrc")
+    submit = open(os.path.join(csrc, "submit_api.hip")).read()
+    pool = open(os.path.join(csrc, "pool_api.hip")).read()
+    for entry in ("int navhip_agent_step_submit", "int navhip_agent_step_poll", "int navhip_agent_step_wait", "void *navhip_host_alloc"):
+        assert re.search(r"^%s\(" % re.escape(entry), submit, re.M), entry
+    assert "__global__" not in submit and "hipLaunchKernelGGL" not in submit
+    for gone in ("nh_async", "hipHostMalloc", "POOL_FAIL", "POOL_HIPCHK", "fresh_slots", "<< 12"):
+        assert gone not in pool, gone
+    asks = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))
+            for _ in re.findall("hipPointerGetAttributes", open(os.path.join(csrc, f)).read())]
+    assert asks == ["submit_api.hip"], asks
+    strip = lambda s: re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", s, flags=re.S))      # noqa: E731
+    internal = strip(open(os.path.join(csrc, "navhip_internal.h")).read())
+    ctx_body = re.search(r"struct navhip_ctx \{(.*?)\n\};", internal, re.S).group(1)
+    each_buf = re.search(r"nh_ctx_each_buf\(navhip_ctx \*ctx, F f\)\s*\{(.*?)\n\}", internal, re.S).group(1)
+    for name in ("d_reqs", "d_dirs", "d_integ"):
+        assert not re.search(r"\b%s\b" % name, ctx_body) and not re.search(r"\b%s\b" % name, each_buf), name
+
+
 def test_state_staging_tables_cover_every_array():
     """csrc/state_kernels.hip stages the input and output structs of the state half of the tick from ONE list per
     struct (sk_gate_rows, sk_state_rows, sk_aux_rows, sk_pass_out_rows, sk_settle_in_rows, sk_settle_out_rows): each

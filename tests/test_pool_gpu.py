@@ -34,7 +34,7 @@ def small(navlib):
     all_ids = np.array([navlib.N_FlowFieldID(reqs[i]) for i in range(len(reqs))], np.uint64)
     _, first = np.unique(all_ids, return_index=True)
     first.sort()
-    yield dict(W=W, K=K, N=N, reqs=reqs, cols=cols, ctx=ctx, arrays=arrays, all_ids=all_ids, uniq=first)
+    yield dict(W=W, K=K, N=N, reqs=reqs, cols=cols, ctx=ctx, arrays=arrays, all_ids=all_ids, uniq=first, grid=grid)
     ctx.close()
 
 
@@ -211,6 +211,189 @@ def test_pool_copy_and_rewrite_of_one_field_in_one_call(navlib, small):
     for _ in range(50):
         ctx.pool_map([0, 0], [int(a["chunk_r"][0]), int(b["chunk_r"][0])], [int(a["chunk_c"][0]), int(b["chunk_c"][0])], [ida, idb])
     assert ctx.pool_contains(ida) and ctx.pool_contains(idb)
+
+
+class _PoolModel:
+    """What the host may rely on: ids ordered by their last build or put (pool_get / pool_contains do not count); free
+    and invalidated slots are taken first; a new id evicts the least recently used id the call in progress has not
+    pinned -- its resident bases from the start, its own ids as they are reached --; eviction and invalidation unmap
+    every (dest, chunk) entry of the id, and building the id again does not bring them back."""
+
+    def __init__(self, n_slots):
+        self.n_slots, self.order, self.mapped = n_slots, [], {}          # order: least recently used first
+
+    def _take(self, fid, pinned):
+        if fid in self.order:
+            self.order.remove(fid)
+        elif len(self.order) == self.n_slots:
+            self.drop(next(i for i in self.order if i not in pinned))
+        self.order.append(fid)
+        pinned.add(fid)
+
+    def build(self, ids, bases=None):
+        pinned = set(b for b in (bases or []) if b and b in self.order)
+        for fid in ids:
+            self._take(int(fid), pinned)
+
+    def put(self, fid):
+        self._take(int(fid), set())
+
+    def drop(self, fid):
+        if fid in self.order:
+            self.order.remove(fid)
+            self.mapped = {e: (None if i == fid else i) for e, i in self.mapped.items()}
+
+    def map(self, entries, ids):
+        for e, fid in zip(entries, ids):
+            self.mapped[e] = int(fid) if int(fid) in self.order else None
+
+
+def test_eviction_and_invalidation_reach_existing_mappings(navlib, small):
+    """The (dest, chunk) table is mapped FIRST, then a scripted dozen of operations evicts, invalidates, rebuilds and
+    re-maps: after every one of them navhip_region_lookup against the resident pool (rows = dest, one point per chunk)
+    answers 0xff for exactly the entries _PoolModel says are unmapped and a direction for the others, and
+    navhip_pool_contains agrees with the model for every id."""
+    synth = cases.synth
+    ctx, reqs, cols, W, K, grid = small["ctx"], small["reqs"], small["cols"], small["W"], small["K"], small["grid"]
+    u = small["uniq"]
+    ids = [int(i) for i in small["all_ids"][u]]
+    n = len(u)
+    assert n >= 12
+    PUT, ABSENT = 0xABCDEF, 12345
+    entries = list(zip(cols["dest"].tolist(), (cols["chunk_r"] * W + cols["chunk_c"]).tolist()))
+    # one query per (dest, chunk): a passable tile of the chunk
+    tile = {}
+    for ch in range(W * W):
+        r, c = np.argwhere(synth.to_chunks(grid)[ch // W, ch % W] != 0xff)[0]
+        tile[ch] = ((ch // W) * 64 + r, (ch % W) * 64 + c)
+    pos = synth.cell_centre(W, W, [tile[ch][0] for _, ch in entries], [tile[ch][1] for _, ch in entries])
+    rows = np.array([d for d, _ in entries], np.int32)
+    M = _PoolModel(n - 4)
+
+    def check(step):
+        got, _ = ctx.region_lookup(pos, rows)
+        want_none = np.array([M.mapped[e] is None for e in entries])
+        assert np.array_equal(got == 0xff, want_none), (step, np.flatnonzero((got == 0xff) != want_none))
+        assert (got[~want_none] < 16).all(), step
+        for fid in ids + [PUT, ABSENT]:
+            assert ctx.pool_contains(fid) == (fid in M.order), (step, fid)
+
+    def build(step, idx, bases=None, inout=()):
+        r = reqs[u[idx]].copy()
+        for k in inout:
+            r["flags"][k] |= navlib.REQ_INOUT
+        ctx.pool_build(r, ff_ids=[ids[i] for i in idx], base_ids=bases, readback=False)
+        M.build([ids[i] for i in idx], bases)
+        check(step)
+
+    ctx.pool_create(n - 4, K)
+    ctx.pool_build(reqs[u[:n - 4]], readback=False)
+    M.build(ids[:n - 4])
+    ctx.pool_map(cols["dest"], cols["chunk_r"], cols["chunk_c"], small["all_ids"])
+    M.map(entries, small["all_ids"])
+    check("mapped")
+    assert sum(v is None for v in M.mapped.values()) > 0 and sum(v is not None for v in M.mapped.values()) > n - 4
+    build("evict two", [n - 4, n - 3])                               # ids[0], ids[1] go
+    assert ctx.pool_get(ids[2]) is not None and ctx.pool_contains(ids[2])     # (reading is not using)
+    build("evict the one just read", [0])                            # ids[2] goes: the read did not move it
+    assert ids[2] not in M.order and ids[0] in M.order
+    # a resident base is pinned (and not touched): ids[3] is the least recently used, ids[4] goes instead
+    build("resident base", [1], bases=[ids[3]], inout=(0,))
+    assert ids[3] in M.order and ids[4] not in M.order
+    ctx.pool_put(PUT, np.full((64, 64), 3, np.uint8))               # a full pool: ids[3] goes now
+    M.put(PUT)
+    check("put")
+    assert ids[3] not in M.order
+    ctx.pool_invalidate(ids[6])
+    M.drop(ids[6])
+    check("invalidate a mapped id")
+    ctx.pool_invalidate(ABSENT)
+    check("invalidate an absent id")
+    # re-map two entries: one to an id that is not resident, one to the field put from the host
+    live = [e for e in entries if M.mapped[e] is not None]
+    e_gone, e_put = live[0], live[1]
+    owner = M.mapped[e_put]
+    ctx.pool_map([e_gone[0], e_put[0]], [e_gone[1] // W, e_put[1] // W], [e_gone[1] % W, e_put[1] % W], [ids[2], PUT])
+    M.map([e_gone, e_put], [ids[2], PUT])
+    check("re-map")
+    assert M.mapped[e_gone] is None and M.mapped[e_put] == PUT
+    build("the freed slot first", [2])                               # nothing is evicted
+    assert len(M.order) == n - 4 and ids[5] in M.order
+    build("evict two more", [3, 4])
+    # an entry that was re-mapped away from a field does not follow that field's eviction
+    while owner in M.order:
+        gone = next(i for i in range(n) if ids[i] not in M.order)
+        build("evict until the old owner goes", [gone])
+    assert M.mapped[e_put] == PUT
+    # the call's own ids are pinned as they are reached: the least recently used id is rebuilt, then two new ones
+    lru = ids.index(next(i for i in M.order if i != PUT))
+    new = [i for i in range(n) if ids[i] not in M.order][:2]
+    build("own ids pinned", [lru] + new)
+    assert ids[lru] in M.order
+    ctx.pool_map(cols["dest"], cols["chunk_r"], cols["chunk_c"], small["all_ids"])
+    M.map(entries, small["all_ids"])
+    check("mapped again")
+
+
+def _backed(navlib, a, pinned, bufs):
+    """a copy of the array `a` in page-locked memory (navhip_host_alloc; kept in bufs) or in pageable memory"""
+    if not pinned:
+        return a.copy()
+    buf = navlib.host_alloc(max(a.nbytes, 1))
+    bufs.append(buf)
+    out = np.frombuffer(buf, np.uint8, a.nbytes).view(a.dtype).reshape(a.shape)
+    out[...] = a
+    return out
+
+
+def test_submit_with_pageable_page_locked_and_mixed_arrays(navlib, small):
+    """navhip_agent_step_submit + _wait on one snapshot whose arrays are all pageable, all page-locked, or alternate by
+    position (the outputs the other way round), for the whole world and for the middle third: the rows of the range
+    are bit-identical to navhip_agent_step, the others keep what the caller had there; the mixed form twice more under
+    one static_epoch.  (Where no pointer reports as page-locked every form takes the pageable path.)"""
+    import ctypes as C
+    ctx, reqs, cols, W, K, N = small["ctx"], small["reqs"], small["cols"], small["W"], small["K"], small["N"]
+    ctx.pool_create(len(reqs), K)
+    ctx.pool_build(reqs[small["uniq"]], readback=False)
+    ctx.pool_map(cols["dest"], cols["chunk_r"], cols["chunk_c"], small["all_ids"])
+    exp = ctx.agent_step(dict(small["arrays"], use_resident_pool=True))
+    names, dtypes = [k for k, _ in navlib._WORLD_ARRAYS], dict(navlib._WORLD_ARRAYS)
+    shapes = {"vel_xz": ((N, 2), np.float32), "new_pos_xz": ((N, 2), np.float32), "vdes_xz": ((N, 2), np.float32),
+              "vpref_xz": ((N, 2), np.float32), "status": ((N,), np.uint8)}
+    L = navlib.lib()
+    bufs = []
+
+    def run(form, work, epoch=0):
+        pin_in = {k: form == "locked" or (form == "mixed" and i % 2 == 0) for i, k in enumerate(names)}
+        a = {k: _backed(navlib, np.ascontiguousarray(v, dtypes[k]), pin_in[k], bufs)
+             for k, v in small["arrays"].items() if v is not None}
+        w, keep = navlib.make_world(W, W, a)
+        w.n_field_slots = navlib.POOL_RESIDENT
+        w.static_epoch = epoch
+        b, e = work if work else (0, N)
+        if work:
+            w.work_begin, w.work_end = work
+        so, outs = navlib.StepOut(), {}
+        for i, (k, (shape, dt)) in enumerate(shapes.items()):
+            pinned = form == "locked" or (form == "mixed" and i % 2 == 1)
+            outs[k] = _backed(navlib, np.full(shape, 0xa5, np.uint8).repeat(np.dtype(dt).itemsize, -1).view(dt), pinned, bufs)
+            setattr(so, k, outs[k].ctypes.data)
+        ctx._chk(L.navhip_agent_step_submit(ctx._h, C.byref(w), C.byref(so)), "navhip_agent_step_submit")
+        ctx._chk(L.navhip_agent_step_wait(ctx._h), "navhip_agent_step_wait")
+        for k, o in outs.items():
+            assert np.array_equal(o[b:e], exp[k][b:e]), (form, work, epoch, k)
+            rest = np.concatenate([o[:b], o[e:]])
+            assert (rest.view(np.uint8) == 0xa5).all(), (form, work, epoch, k)
+
+    try:
+        for form in ("pageable", "locked", "mixed"):
+            for work in (None, (N // 3, 2 * N // 3)):
+                run(form, work)
+        run("mixed", None, epoch=9)
+        run("mixed", (N // 3, 2 * N // 3), epoch=9)
+    finally:
+        for buf in bufs:
+            navlib.host_free(buf)
 
 
 def test_step_joins_a_prefetch_issued_on_another_stream(navlib, small):
