@@ -1,4 +1,4 @@
-// agent_internal.h -- launch interface of agent_kernels.hip (used by step_api.hip, navhip_api.hip, state_kernels.hip).
+// agent_internal.h -- launch interface of agent_kernels.hip (used by step_api.hip, state_kernels.hip).
 #pragma once
 #define NH_SCAN_T 256      /* threads (= cells) per block of the two-pass scans */
 #include "navhip_internal.h"

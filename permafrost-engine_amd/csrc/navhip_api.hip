@@ -1,55 +1,59 @@
-// navhip_api.hip -- the C ABI of libnavhip.so (include/navhip.h): context, map-plane
-// residency in HBM, and the host-/device-buffer entry points that launch the kernels.
-//
-// Data layout in HBM (per nav layer, allocated on first upload; sized for the reference's
-// maximum 64x64-chunk map this is 64 MB cost + 128 MB blockers + 128 MB local islands +
-// 960 MB factions -- a fraction of the 288 GB part, so everything stays resident):
-//   cost          u8  [chunks][64][64]       struct nav_chunk.cost_base      nav_data.h:123
-//   blockers      u16 [chunks][64][64]       struct nav_chunk.blockers       nav_data.h:134
-//   local_islands u16 [chunks][64][64]       struct nav_chunk.local_islands  nav_data.h:157
-//   factions      u8  [chunks][15][64][64]   struct nav_chunk.factions       nav_data.h:141
-//   passmask      u64 [chunks][64]           derived: row bitmasks of field_tile_passable
-//   probemask     u64 [chunks][64][2]        derived: row bitmasks cost_base != 0xff | blockers > 0 (tile probes)
-//   facmask       u64 [chunks][15][64]       derived: row bitmasks factions[f] != 0 (attacking-path fields); with the
-//   facany        u16 [chunks]               derived: factions present in the chunk      factions plane only
-//   unit_cost     u8  [chunks]               derived: BFS kernel eligibility
+// navhip_api.hip -- the map state behind the C ABI of libnavhip.so (include/navhip.h): the context, the planes of every
+// nav layer resident in HBM with the row masks derived from them, the blockers, and the chunk / LOS / region field builds
+// through device or host buffers, with the two field ids.
 #include "navhip_internal.h"
-#include "agent_internal.h"
-#include "agent_thread.h"
 #include <cmath>
 
 #include <cstdio>
 #include <cstdlib>
-#include <algorithm>
 #include <cstring>
-#include <initializer_list>
+#include <iterator>
 #include <new>
 #include <vector>
 
-static size_t plane_elem_bytes(int plane)
+// The planes of a layer (resident from their first upload: for the reference's maximum 64x64-chunk map 64 MB cost + 128 MB
+// blockers + 128 MB local islands + 960 MB factions, a fraction of the 288 GB part), one row per NAVHIP_PLANE_* in the order
+// of their numbers: the member of navhip_layer, bytes per cell, whether an upload leaves the derived masks stale, whether
+// a fresh allocation is zeroed (a cost plane is not: it appears with its first upload) ...
+struct plane_row { size_t off; size_t cell_bytes; bool dirties, zeroed; };
+static const plane_row plane_rows[] = {
+    {offsetof(navhip_layer, cost),          1,                   true,  false},  // u8  [chunks][64][64]     nav_chunk.cost_base     nav_data.h:123
+    {offsetof(navhip_layer, blockers),      2,                   true,  true},   // u16 [chunks][64][64]     nav_chunk.blockers      nav_data.h:134
+    {offsetof(navhip_layer, local_islands), 2,                   false, true},   // u16 [chunks][64][64]     nav_chunk.local_islands nav_data.h:157
+    {offsetof(navhip_layer, factions),      NAVHIP_MAX_FACTIONS, true,  true},   // u8  [chunks][15][64][64] nav_chunk.factions      nav_data.h:141
+    {offsetof(navhip_layer, islands),       2,                   false, true},   // u16 [chunks][64][64]     global island ids
+};
+static_assert(std::size(plane_rows) == NAVHIP_PLANE_COUNT && NAVHIP_PLANE_COST_BASE == 0 && NAVHIP_PLANE_BLOCKERS == 1
+           && NAVHIP_PLANE_LOCAL_ISLANDS == 2 && NAVHIP_PLANE_FACTIONS == 3 && NAVHIP_PLANE_ISLANDS == 4,
+              "plane_rows: one row per NAVHIP_PLANE_*, indexed by it");
+// ... and its derived device arrays (struct navhip_layer says what each holds): bytes per chunk, whether the array exists
+// only beside the factions plane, whether a fresh one is zeroed (the flags the kernels raise; the rows of a factions plane
+// that is all zero until its first upload)
+struct derived_row { size_t off; size_t chunk_bytes; bool with_factions, zeroed; };
+static const derived_row derived_rows[] = {
+    {offsetof(navhip_layer, passmask),    64 * sizeof(uint64_t),                       false, false},
+    {offsetof(navhip_layer, probemask),   128 * sizeof(uint64_t),                      false, false},
+    {offsetof(navhip_layer, unit_cost),   1,                                           false, false},
+    {offsetof(navhip_layer, touched),     1,                                           false, true},
+    {offsetof(navhip_layer, changed),     1,                                           false, true},
+    {offsetof(navhip_layer, facmask),     NAVHIP_MAX_FACTIONS * 64 * sizeof(uint64_t), true,  true},
+    {offsetof(navhip_layer, facany),      sizeof(uint16_t),                            true,  true},
+    {offsetof(navhip_layer, fac_touched), sizeof(uint32_t),                            true,  true},
+};
+
+static void *&plane_slot(navhip_layer &L, int plane) { return nh_member(&L, plane_rows[plane].off); }
+static size_t plane_bytes(const navhip_ctx *ctx, int plane) { return (size_t)ctx->nchunks * NH_CELLS * plane_rows[plane].cell_bytes; }
+static bool check_layer_plane(const navhip_ctx *ctx, int layer, int plane)
 {
-    switch(plane) {
-    case NAVHIP_PLANE_COST_BASE:     return 1;
-    case NAVHIP_PLANE_BLOCKERS:      return 2;
-    case NAVHIP_PLANE_LOCAL_ISLANDS: return 2;
-    case NAVHIP_PLANE_FACTIONS:      return NAVHIP_MAX_FACTIONS;
-    case NAVHIP_PLANE_ISLANDS:       return 2;
-    default: return 0;
-    }
+    return ctx && layer >= 0 && layer < NAVHIP_NAV_LAYER_MAX && plane >= 0 && plane < NAVHIP_PLANE_COUNT;
 }
 
-static void **plane_slot(navhip_layer &L, int plane)
-{
-    switch(plane) {
-    case NAVHIP_PLANE_COST_BASE:     return (void**)&L.cost;
-    case NAVHIP_PLANE_BLOCKERS:      return (void**)&L.blockers;
-    case NAVHIP_PLANE_LOCAL_ISLANDS: return (void**)&L.local_islands;
-    case NAVHIP_PLANE_FACTIONS:      return (void**)&L.factions;
-    case NAVHIP_PLANE_ISLANDS:       return (void**)&L.islands;
-    default: return nullptr;
-    }
-}
-
+// Device buffers grown on demand, and the staging path of every host-buffer entry point of the library (this unit,
+// step_api.hip, submit_api.hip, state_kernels.hip): nh_ensure -- b holds at least `need` bytes, contents are not kept;
+// nh_ensure_buf -- the step's scratch and the staging slots: at least 16 bytes, and a buffer that moved is counted
+// (scratch_moves); nh_stage_reserve -- a staging slot of `bytes`; nh_stage_in -- a host array copied to its slot on s
+// (*dst: the device copy, NULL stays NULL).  What a slot in front of NH_STAGE_CALL0 held may have been the asynchronous
+// step's (its attribute tables, its resident snapshot): writing one tells it so.
 int nh_ensure(navhip_ctx *ctx, nh_buf &b, size_t need)
 {
     if(b.cap >= need) return NAVHIP_OK;
@@ -61,13 +65,31 @@ int nh_ensure(navhip_ctx *ctx, nh_buf &b, size_t need)
     return NAVHIP_OK;
 }
 
-// the step's scratch and the staging slots: at least 16 bytes, and a buffer that moved is counted (scratch_moves)
 int nh_ensure_buf(navhip_ctx *ctx, nh_buf &b, size_t need)
 {
     const void *old = b.p;
     int rc = nh_ensure(ctx, b, need ? need : 16);
     if(b.p != old) ctx->step.scratch_moves++;
     return rc;
+}
+
+int nh_stage_reserve(navhip_ctx *ctx, nh_stage_slot slot, size_t bytes, void **dev)
+{
+    int rc = nh_ensure_buf(ctx, ctx->stage[slot], bytes);
+    if(rc) return rc;
+    *dev = ctx->stage[slot].p;
+    return NAVHIP_OK;
+}
+
+int nh_stage_in(navhip_ctx *ctx, nh_stage_slot slot, const void *host, size_t bytes, const void **dst, hipStream_t s)
+{
+    if(slot < NH_STAGE_CALL0) nh_async_invalidate_static(ctx);
+    *dst = nullptr;
+    if(!host) return NAVHIP_OK;
+    int rc = nh_stage_reserve(ctx, slot, bytes, (void**)dst);
+    if(rc) return rc;
+    if(bytes) HIPCHK(ctx, hipMemcpyAsync((void*)*dst, host, bytes, hipMemcpyHostToDevice, s));
+    return NAVHIP_OK;
 }
 
 // rebuild passmask / probemask / unit_cost / facmask of chunks whose cost, blockers or factions changed (after an upload: the
@@ -101,6 +123,88 @@ int nh_refresh_derived(navhip_ctx *ctx, hipStream_t s)
     }
     if(launched) HIPCHK(ctx, hipStreamSynchronize(s));
     return NAVHIP_OK;
+}
+
+// a device array of a layer that does not exist yet
+static int layer_array(navhip_ctx *ctx, void *&p, size_t bytes, bool zeroed)
+{
+    if(p) return NAVHIP_OK;
+    HIPCHK(ctx, hipMalloc(&p, bytes));
+    if(zeroed) HIPCHK(ctx, hipMemsetAsync(p, 0, bytes, ctx->stream));
+    return NAVHIP_OK;
+}
+
+// The layer is about to hold `plane`: the plane, the host's dirty marks and the derived arrays, each made where it is
+// missing -- a preparation that ran out of memory half way is finished by the next one, and the dirty marks, made first,
+// are there for every upload that gets as far as marking.
+static int layer_prepare(navhip_ctx *ctx, int layer, int plane)
+{
+    navhip_layer &L = ctx->layers[layer];
+    if(!L.dirty && !(L.dirty = (uint8_t*)calloc(ctx->nchunks, 1))) return NAVHIP_ERR_NOMEM;
+    int rc = layer_array(ctx, plane_slot(L, plane), plane_bytes(ctx, plane), plane_rows[plane].zeroed);
+    for(const derived_row &d : derived_rows)
+        if(!rc && (!d.with_factions || L.factions))
+            rc = layer_array(ctx, nh_member(&L, d.off), (size_t)ctx->nchunks * d.chunk_bytes, d.zeroed);
+    return rc;
+}
+
+// Chunks [chunk0, chunk0 + n) of a plane from host memory (who: the entry point, for last_error).  A whole-plane upload
+// (navhip_upload_plane: [0, nchunks)) SETS the layer's nonunit_costs, so it can go back to false; a chunk upload
+// (navhip_upload_chunk: one chunk) can only raise it.
+static int upload_chunks(navhip_ctx *ctx, int layer, int plane, int chunk0, int n, bool whole, const void *host, size_t bytes,
+                         const char *who)
+{
+    const size_t per = NH_CELLS * plane_rows[plane].cell_bytes;
+    if(bytes != (size_t)n * per) {
+        ctx->last_error = std::string(who) + ": size mismatch";
+        return NAVHIP_ERR_INVALID;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = layer_prepare(ctx, layer, plane);
+    if(rc) return rc;
+    navhip_layer &L = ctx->layers[layer];
+    HIPCHK(ctx, hipMemcpyAsync((char*)plane_slot(L, plane) + (size_t)chunk0 * per, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // caller may reuse `host` immediately
+    if(plane_rows[plane].dirties) {
+        memset(L.dirty + chunk0, 1, n);
+        L.any_dirty = true;
+    }
+    if(plane == NAVHIP_PLANE_COST_BASE) {
+        // does the layer hold costs other than 1 / impassable?  (The reference's cost writers produce no
+        // others, nav.c:339-342,416; a host that does sends its requests to the relaxation kernel, whose
+        // launch is then sized for real work instead of for an empty list.)
+        const uint8_t *c = (const uint8_t*)host;
+        bool other = false;
+        for(size_t i = 0; i < bytes && !other; i++) other = c[i] != 1 && c[i] != NAVHIP_COST_IMPASSABLE;
+        L.nonunit_costs = other || (!whole && L.nonunit_costs);
+    }
+    return NAVHIP_OK;
+}
+
+// request i is built into slot dev_slots[i] of dev_inout_dirs when dev_slots is given (navhip_pool_build)
+static int build_fields_on(navhip_ctx *ctx, const navhip_field_req *dev_reqs, int n, uint8_t *dev_inout_dirs,
+                           float *dev_out_integ, const int32_t *dev_slots, hipStream_t s)
+{
+    int rc = nh_refresh_derived(ctx, s);
+    if(rc) return rc;
+    // work list of the generic kernel: the header is zero between launches (the kernel resets it)
+    const void *old_list = ctx->gen_list.p;
+    rc = nh_ensure_buf(ctx, ctx->gen_list, ((size_t)n + 2) * sizeof(int32_t));
+    if(rc) return rc;
+    if(ctx->gen_list.p != old_list) HIPCHK(ctx, hipMemsetAsync(ctx->gen_list.p, 0, 2 * sizeof(int32_t), s));
+    ctx->last_fields.gen_slot = nh_launch_fields(ctx, dev_reqs, n, dev_inout_dirs, dev_out_integ, (int32_t*)ctx->gen_list.p,
+                                                 s, dev_slots);
+    ctx->last_fields.n = n; ctx->last_fields.stream = s;
+    HIPCHK(ctx, hipGetLastError());
+    ctx->counters.field_calls++; ctx->counters.chunk_fields += (uint64_t)n;
+    return NAVHIP_OK;
+}
+
+int navhip_build_fields_slots_dev(navhip_ctx *ctx, const navhip_field_req *dev_reqs, int n, uint8_t *dev_fields,
+                                  const int32_t *dev_slots, hipStream_t s)
+{
+    if(n == 0) return NAVHIP_OK;
+    return build_fields_on(ctx, dev_reqs, n, dev_fields, nullptr, dev_slots, s);
 }
 
 extern "C" {
@@ -138,12 +242,9 @@ void navhip_ctx_destroy(navhip_ctx *ctx)
     if(ctx->step.lists_pinned) hipHostFree(ctx->step.lists_pinned);
     navhip_pool_destroy(ctx);
     nh_async_destroy(ctx);
-    for(int l = 0; l < NAVHIP_NAV_LAYER_MAX; l++) {
-        navhip_layer &L = ctx->layers[l];
-        hipFree(L.cost); hipFree(L.blockers); hipFree(L.local_islands); hipFree(L.factions);
-        hipFree(L.islands);
-        hipFree(L.passmask); hipFree(L.probemask); hipFree(L.unit_cost); hipFree(L.touched); hipFree(L.changed);
-        hipFree(L.facmask); hipFree(L.facany); hipFree(L.fac_touched);
+    for(navhip_layer &L : ctx->layers) {
+        for(const plane_row &p : plane_rows) hipFree(nh_member(&L, p.off));
+        for(const derived_row &d : derived_rows) hipFree(nh_member(&L, d.off));
         free(L.dirty);
     }
     nh_ctx_each_buf(ctx, [](nh_buf &b) { hipFree(b.p); });
@@ -161,41 +262,6 @@ const char *navhip_last_error(const navhip_ctx *ctx) { return ctx ? ctx->last_er
 int   navhip_device(const navhip_ctx *ctx) { return ctx ? ctx->device : -1; }
 void *navhip_stream(const navhip_ctx *ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 
-int navhip_stream_beside(navhip_ctx *ctx, void *main_stream, int cu_begin, int cu_count, void **out_stream)
-{
-    if(!ctx || !out_stream || cu_begin < 0) return NAVHIP_ERR_INVALID;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = nullptr;
-    if(cu_count <= 0) {
-        hipStream_t all[NH_STREAM_FIXED];
-        int rc = nh_streams_for(ctx, (hipStream_t)main_stream, all);
-        if(rc) return rc;
-        st = all[NH_STREAM_FIELDS];
-    }else{
-        st = nh_stream_partial_for(ctx, (hipStream_t)main_stream, cu_begin, cu_count);
-        if(!st) return ctx->last_error.empty() ? NAVHIP_ERR_INVALID : NAVHIP_ERR_DEVICE;
-    }
-    *out_stream = (void*)st;
-    return NAVHIP_OK;
-}
-
-int navhip_stream_main(navhip_ctx *ctx, void **out_stream)
-{
-    if(!ctx || !out_stream) return NAVHIP_ERR_INVALID;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t all[NH_STREAM_FIXED];
-    int rc = nh_streams_for(ctx, nullptr, all);
-    if(rc) return rc;
-    *out_stream = (void*)all[NH_STREAM_MAIN];
-    return NAVHIP_OK;
-}
-
-int navhip_stream_create_partial(navhip_ctx *ctx, int cu_begin, int cu_count, void **out_stream)
-{
-    if(cu_count <= 0) return NAVHIP_ERR_INVALID;
-    return navhip_stream_beside(ctx, ctx ? (void*)ctx->stream : nullptr, cu_begin, cu_count, out_stream);
-}
-
 int navhip_sync(navhip_ctx *ctx)
 {
     if(!ctx) return NAVHIP_ERR_INVALID;
@@ -204,143 +270,43 @@ int navhip_sync(navhip_ctx *ctx)
     return NAVHIP_OK;
 }
 
-int navhip_set_field_kernel(navhip_ctx *ctx, int mode)
-{
-    if(!ctx || mode < 0 || mode > 1) return NAVHIP_ERR_INVALID;
-    ctx->field_kernel_mode = mode;
-    return NAVHIP_OK;
-}
-
-int navhip_last_fields_split(navhip_ctx *ctx, int32_t out[2])
+int navhip_get_counters(navhip_ctx *ctx, navhip_counters *out, int reset)
 {
     if(!ctx || !out) return NAVHIP_ERR_INVALID;
-    if(ctx->last_fields.n < 0) {
-        ctx->last_error = "navhip_last_fields_split: no chunk-field build yet";
-        return NAVHIP_ERR_INVALID;
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int32_t generic = ctx->last_fields.n;           // (forced: no list, k_field_generic built every request)
-    if(ctx->last_fields.gen_slot >= 0)
-        // the counter the two kernels keep anyway: it stays until the launch after the next one zeroes it
-        HIPCHK(ctx, hipMemcpyAsync(&generic, (const int32_t*)ctx->gen_list.p + ctx->last_fields.gen_slot, sizeof(int32_t),
-                                   hipMemcpyDeviceToHost, ctx->last_fields.stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->last_fields.stream));
-    out[0] = ctx->last_fields.n - generic; out[1] = generic;
+    *out = ctx->counters;
+    if(reset) memset(&ctx->counters, 0, sizeof(ctx->counters));
     return NAVHIP_OK;
 }
 
-static int layer_prepare(navhip_ctx *ctx, int layer, int plane)
-{
-    navhip_layer &L = ctx->layers[layer];
-    void **slot = plane_slot(L, plane);
-    if(!*slot) {
-        size_t bytes = (size_t)ctx->nchunks * NH_CELLS * plane_elem_bytes(plane);
-        HIPCHK(ctx, hipMalloc(slot, bytes));
-        if(plane != NAVHIP_PLANE_COST_BASE)
-            HIPCHK(ctx, hipMemsetAsync(*slot, 0, bytes, ctx->stream));
-    }
-    if(!L.passmask) {
-        HIPCHK(ctx, hipMalloc((void**)&L.passmask, (size_t)ctx->nchunks * 64 * sizeof(uint64_t)));
-        HIPCHK(ctx, hipMalloc((void**)&L.probemask, (size_t)ctx->nchunks * 128 * sizeof(uint64_t)));
-        HIPCHK(ctx, hipMalloc((void**)&L.unit_cost, (size_t)ctx->nchunks));
-        HIPCHK(ctx, hipMalloc((void**)&L.touched, (size_t)ctx->nchunks));
-        HIPCHK(ctx, hipMalloc((void**)&L.changed, (size_t)ctx->nchunks));
-        HIPCHK(ctx, hipMemsetAsync(L.touched, 0, (size_t)ctx->nchunks, ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(L.changed, 0, (size_t)ctx->nchunks, ctx->stream));
-        L.dirty = (uint8_t*)calloc(ctx->nchunks, 1);
-        if(!L.dirty) return NAVHIP_ERR_NOMEM;
-    }
-    if(L.factions && !L.facmask) {
-        // the derived rows of the factions plane (all zero, like the plane itself until its first upload)
-        const size_t rows = (size_t)ctx->nchunks * NAVHIP_MAX_FACTIONS * 64 * sizeof(uint64_t);
-        HIPCHK(ctx, hipMalloc((void**)&L.facmask, rows));
-        HIPCHK(ctx, hipMalloc((void**)&L.facany, (size_t)ctx->nchunks * sizeof(uint16_t)));
-        HIPCHK(ctx, hipMalloc((void**)&L.fac_touched, (size_t)ctx->nchunks * sizeof(uint32_t)));
-        HIPCHK(ctx, hipMemsetAsync(L.facmask, 0, rows, ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(L.facany, 0, (size_t)ctx->nchunks * sizeof(uint16_t), ctx->stream));
-        HIPCHK(ctx, hipMemsetAsync(L.fac_touched, 0, (size_t)ctx->nchunks * sizeof(uint32_t), ctx->stream));
-    }
-    return NAVHIP_OK;
-}
-
+// ---------------------------------------------------------------------------------------------
+// planes
+// ---------------------------------------------------------------------------------------------
 int navhip_upload_plane(navhip_ctx *ctx, int layer, int plane, const void *host, size_t bytes)
 {
-    if(!ctx || !host || layer < 0 || layer >= NAVHIP_NAV_LAYER_MAX
-    || plane < 0 || plane >= NAVHIP_PLANE_COUNT)
-        return NAVHIP_ERR_INVALID;
-    size_t want = (size_t)ctx->nchunks * NH_CELLS * plane_elem_bytes(plane);
-    if(bytes != want) {
-        ctx->last_error = "navhip_upload_plane: size mismatch";
-        return NAVHIP_ERR_INVALID;
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int rc = layer_prepare(ctx, layer, plane);
-    if(rc) return rc;
-    navhip_layer &L = ctx->layers[layer];
-    HIPCHK(ctx, hipMemcpyAsync(*plane_slot(L, plane), host, bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // caller may reuse `host` immediately
-    if(plane == NAVHIP_PLANE_COST_BASE || plane == NAVHIP_PLANE_BLOCKERS || plane == NAVHIP_PLANE_FACTIONS) {
-        memset(L.dirty, 1, ctx->nchunks);
-        L.any_dirty = true;
-    }
-    if(plane == NAVHIP_PLANE_COST_BASE) {
-        // does the layer hold costs other than 1 / impassable?  (The reference's cost writers produce no
-        // others, nav.c:339-342,416; a host that does sends its requests to the relaxation kernel, whose
-        // launch is then sized for real work instead of for an empty list.)
-        const uint8_t *c = (const uint8_t*)host;
-        bool other = false;
-        for(size_t i = 0; i < bytes && !other; i++) other = c[i] != 1 && c[i] != NAVHIP_COST_IMPASSABLE;
-        L.nonunit_costs = other;
-    }
-    return NAVHIP_OK;
+    if(!check_layer_plane(ctx, layer, plane) || !host) return NAVHIP_ERR_INVALID;
+    return upload_chunks(ctx, layer, plane, 0, ctx->nchunks, true, host, bytes, "navhip_upload_plane");
 }
 
 int navhip_upload_chunk(navhip_ctx *ctx, int layer, int plane, int chunk_r, int chunk_c,
                         const void *host, size_t bytes)
 {
-    if(!ctx || !host || layer < 0 || layer >= NAVHIP_NAV_LAYER_MAX
-    || plane < 0 || plane >= NAVHIP_PLANE_COUNT
+    if(!check_layer_plane(ctx, layer, plane) || !host
     || chunk_r < 0 || chunk_r >= ctx->h || chunk_c < 0 || chunk_c >= ctx->w)
         return NAVHIP_ERR_INVALID;
-    size_t per = (size_t)NH_CELLS * plane_elem_bytes(plane);
-    if(bytes != per) {
-        ctx->last_error = "navhip_upload_chunk: size mismatch";
-        return NAVHIP_ERR_INVALID;
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int rc = layer_prepare(ctx, layer, plane);
-    if(rc) return rc;
-    navhip_layer &L = ctx->layers[layer];
-    int chunk = chunk_r * ctx->w + chunk_c;
-    if(plane == NAVHIP_PLANE_COST_BASE) {
-        const uint8_t *c = (const uint8_t*)host;
-        for(size_t i = 0; i < per; i++) if(c[i] != 1 && c[i] != NAVHIP_COST_IMPASSABLE) { L.nonunit_costs = true; break; }
-    }
-    HIPCHK(ctx, hipMemcpyAsync((char*)*plane_slot(L, plane) + (size_t)chunk * per, host, per,
-                               hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if(plane == NAVHIP_PLANE_COST_BASE || plane == NAVHIP_PLANE_BLOCKERS || plane == NAVHIP_PLANE_FACTIONS) {
-        L.dirty[chunk] = 1;
-        L.any_dirty = true;
-    }
-    return NAVHIP_OK;
+    return upload_chunks(ctx, layer, plane, chunk_r * ctx->w + chunk_c, 1, false, host, bytes, "navhip_upload_chunk");
 }
 
 void *navhip_plane_dev(navhip_ctx *ctx, int layer, int plane)
 {
-    if(!ctx || layer < 0 || layer >= NAVHIP_NAV_LAYER_MAX || plane < 0 || plane >= NAVHIP_PLANE_COUNT)
-        return nullptr;
-    return *plane_slot(ctx->layers[layer], plane);
+    return check_layer_plane(ctx, layer, plane) ? plane_slot(ctx->layers[layer], plane) : nullptr;
 }
 
 int navhip_download_plane(navhip_ctx *ctx, int layer, int plane, void *host, size_t bytes)
 {
-    if(!ctx || !host || layer < 0 || layer >= NAVHIP_NAV_LAYER_MAX
-    || plane < 0 || plane >= NAVHIP_PLANE_COUNT)
-        return NAVHIP_ERR_INVALID;
-    void *src = *plane_slot(ctx->layers[layer], plane);
+    if(!check_layer_plane(ctx, layer, plane) || !host) return NAVHIP_ERR_INVALID;
+    const void *src = plane_slot(ctx->layers[layer], plane);
     if(!src) return NAVHIP_ERR_NOT_UPLOADED;
-    if(bytes != (size_t)ctx->nchunks * NH_CELLS * plane_elem_bytes(plane)) return NAVHIP_ERR_INVALID;
+    if(bytes != plane_bytes(ctx, plane)) return NAVHIP_ERR_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipMemcpyAsync(host, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -385,13 +351,9 @@ int navhip_blockers_circles(navhip_ctx *ctx, const navhip_circle *circles, int n
     }
     if(n == 0) return NAVHIP_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    nh_buf &d_circles = ctx->stage[NH_STAGE_CALL0];
-    int rc = nh_ensure_buf(ctx, d_circles, (size_t)n * sizeof(navhip_circle));
-    if(rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(d_circles.p, circles, (size_t)n * sizeof(navhip_circle),
-                               hipMemcpyHostToDevice, ctx->stream));
-    rc = navhip_blockers_circles_dev(ctx, (const navhip_circle*)d_circles.p, n, map_pos_x,
-                                     map_pos_z, ctx->stream);
+    const navhip_circle *d_circles;
+    int rc = nh_stage_in(ctx, NH_STAGE_CALL0, circles, (size_t)n * sizeof(navhip_circle), (const void**)&d_circles, ctx->stream);
+    if(!rc) rc = navhip_blockers_circles_dev(ctx, d_circles, n, map_pos_x, map_pos_z, ctx->stream);
     if(rc) return rc;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return NAVHIP_OK;
@@ -484,23 +446,18 @@ int navhip_build_region_fields(navhip_ctx *ctx, const navhip_region_req *reqs, i
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    nh_buf &d_reqs = ctx->stage[NH_STAGE_CALL0], &d_seeds = ctx->stage[NH_STAGE_CALL1];
-    nh_buf &d_overlay = ctx->stage[NH_STAGE_CALL2], &d_out = ctx->stage[NH_STAGE_CALL3];
-    int rc = nh_ensure_buf(ctx, d_reqs, (size_t)n * sizeof(navhip_region_req));
-    if(!rc) rc = nh_ensure_buf(ctx, d_seeds, n_seeds * 4);
-    if(!rc) rc = nh_ensure_buf(ctx, d_overlay, n_overlay * 4);
-    if(!rc) rc = nh_ensure_buf(ctx, d_out, (size_t)n * out_stride);
+    const size_t out_bytes = (size_t)n * out_stride;
+    const navhip_region_req *d_reqs; const int16_t *d_seeds, *d_overlay;
+    uint8_t *d_out = nullptr;
+    int rc = nh_stage_in(ctx, NH_STAGE_CALL0, reqs, (size_t)n * sizeof(navhip_region_req), (const void**)&d_reqs, s);
+    if(!rc) rc = nh_stage_in(ctx, NH_STAGE_CALL1, seeds, n_seeds * 4, (const void**)&d_seeds, s);
+    if(!rc) rc = nh_stage_in(ctx, NH_STAGE_CALL2, overlay, n_overlay * 4, (const void**)&d_overlay, s);
+    // (the slots a window request writes into travel with what they hold; whole-region slots are fully written)
+    if(!rc) rc = any_window ? nh_stage_in(ctx, NH_STAGE_CALL3, inout, out_bytes, (const void**)&d_out, s)
+                            : nh_stage_reserve(ctx, NH_STAGE_CALL3, out_bytes, (void**)&d_out);
+    if(!rc) rc = navhip_build_region_fields_dev(ctx, d_reqs, n, max_dim, d_seeds, d_overlay, d_out, out_stride, s);
     if(rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(d_reqs.p, reqs, (size_t)n * sizeof(navhip_region_req), hipMemcpyHostToDevice, s));
-    if(n_seeds) HIPCHK(ctx, hipMemcpyAsync(d_seeds.p, seeds, n_seeds * 4, hipMemcpyHostToDevice, s));
-    if(n_overlay) HIPCHK(ctx, hipMemcpyAsync(d_overlay.p, overlay, n_overlay * 4, hipMemcpyHostToDevice, s));
-    if(any_window)
-        HIPCHK(ctx, hipMemcpyAsync(d_out.p, inout, (size_t)n * out_stride, hipMemcpyHostToDevice, s));
-    rc = navhip_build_region_fields_dev(ctx, (const navhip_region_req*)d_reqs.p, n, max_dim,
-                                        (const int16_t*)d_seeds.p, (const int16_t*)d_overlay.p,
-                                        (uint8_t*)d_out.p, out_stride, s);
-    if(rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(inout, d_out.p, (size_t)n * out_stride, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(inout, d_out, out_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     return NAVHIP_OK;
 }
@@ -551,22 +508,23 @@ int navhip_build_los(navhip_ctx *ctx, const navhip_los_req *reqs, int n,
     if(any_prev && !prev_fields) return NAVHIP_ERR_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    nh_buf &d_reqs = ctx->stage[NH_STAGE_CALL0], &d_prev = ctx->stage[NH_STAGE_CALL1], &d_out = ctx->stage[NH_STAGE_CALL2];
-    int rc = nh_ensure_buf(ctx, d_reqs, (size_t)n * sizeof(navhip_los_req));
-    if(!rc) rc = nh_ensure_buf(ctx, d_prev, (size_t)n * NH_CELLS);
-    if(!rc) rc = nh_ensure_buf(ctx, d_out, (size_t)n * NH_CELLS);
+    const size_t field_bytes = (size_t)n * NH_CELLS;
+    const navhip_los_req *d_reqs; const uint8_t *d_prev;
+    uint8_t *d_out = nullptr;
+    int rc = nh_stage_in(ctx, NH_STAGE_CALL0, reqs, (size_t)n * sizeof(navhip_los_req), (const void**)&d_reqs, s);
+    // (no request with a predecessor: no copy, and NULL for the kernel, which reads a previous field only for such a request)
+    if(!rc) rc = nh_stage_in(ctx, NH_STAGE_CALL1, any_prev ? prev_fields : nullptr, field_bytes, (const void**)&d_prev, s);
+    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_CALL2, field_bytes, (void**)&d_out);
+    if(!rc) rc = navhip_build_los_dev(ctx, d_reqs, n, d_prev, d_out, map_pos_x, map_pos_z, s);
     if(rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(d_reqs.p, reqs, (size_t)n * sizeof(navhip_los_req), hipMemcpyHostToDevice, s));
-    if(any_prev)
-        HIPCHK(ctx, hipMemcpyAsync(d_prev.p, prev_fields, (size_t)n * NH_CELLS, hipMemcpyHostToDevice, s));
-    rc = navhip_build_los_dev(ctx, (const navhip_los_req*)d_reqs.p, n, (const uint8_t*)d_prev.p, (uint8_t*)d_out.p,
-                              map_pos_x, map_pos_z, s);
-    if(rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(out_fields, d_out.p, (size_t)n * NH_CELLS, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(out_fields, d_out, field_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     return NAVHIP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// chunk fields, field ids
+// ---------------------------------------------------------------------------------------------
 int nh_validate_field_reqs(navhip_ctx *ctx, const navhip_field_req *reqs, int n)
 {
     for(int i = 0; i < n; i++) {
@@ -597,24 +555,6 @@ int nh_validate_field_reqs(navhip_ctx *ctx, const navhip_field_req *reqs, int n)
     return NAVHIP_OK;
 }
 
-static int build_fields_on(navhip_ctx *ctx, const navhip_field_req *dev_reqs, int n, uint8_t *dev_inout_dirs,
-                           float *dev_out_integ, const int32_t *dev_slots, hipStream_t s)
-{
-    int rc = nh_refresh_derived(ctx, s);
-    if(rc) return rc;
-    // work list of the generic kernel: the header is zero between launches (the kernel resets it)
-    const void *old_list = ctx->gen_list.p;
-    rc = nh_ensure_buf(ctx, ctx->gen_list, ((size_t)n + 2) * sizeof(int32_t));
-    if(rc) return rc;
-    if(ctx->gen_list.p != old_list) HIPCHK(ctx, hipMemsetAsync(ctx->gen_list.p, 0, 2 * sizeof(int32_t), s));
-    ctx->last_fields.gen_slot = nh_launch_fields(ctx, dev_reqs, n, dev_inout_dirs, dev_out_integ, (int32_t*)ctx->gen_list.p,
-                                                 s, dev_slots);
-    ctx->last_fields.n = n; ctx->last_fields.stream = s;
-    HIPCHK(ctx, hipGetLastError());
-    ctx->counters.field_calls++; ctx->counters.chunk_fields += (uint64_t)n;
-    return NAVHIP_OK;
-}
-
 int navhip_build_fields_dev(navhip_ctx *ctx, const navhip_field_req *dev_reqs, int n,
                             uint8_t *dev_inout_dirs, float *dev_out_integ, void *stream)
 {
@@ -625,26 +565,6 @@ int navhip_build_fields_dev(navhip_ctx *ctx, const navhip_field_req *dev_reqs, i
                            stream ? (hipStream_t)stream : ctx->stream);
 }
 
-}  // extern "C"
-
-// request i is built into slot dev_slots[i] of dev_fields (navhip_pool_build)
-int navhip_build_fields_slots_dev(navhip_ctx *ctx, const navhip_field_req *dev_reqs, int n, uint8_t *dev_fields,
-                                  const int32_t *dev_slots, hipStream_t s)
-{
-    if(n == 0) return NAVHIP_OK;
-    return build_fields_on(ctx, dev_reqs, n, dev_fields, nullptr, dev_slots, s);
-}
-
-int nh_stage_reserve(navhip_ctx *ctx, nh_stage_slot slot, size_t bytes, void **dev)
-{
-    int rc = nh_ensure_buf(ctx, ctx->stage[slot], bytes);
-    if(rc) return rc;
-    *dev = ctx->stage[slot].p;
-    return NAVHIP_OK;
-}
-
-extern "C" {
-
 int navhip_build_fields(navhip_ctx *ctx, const navhip_field_req *reqs, int n,
                         uint8_t *inout_dirs, float *out_integ)
 {
@@ -654,141 +574,49 @@ int navhip_build_fields(navhip_ctx *ctx, const navhip_field_req *reqs, int n,
     int rc = nh_validate_field_reqs(ctx, reqs, n);
     if(rc) return rc;
     hipStream_t s = ctx->stream;
-    nh_buf &d_reqs = ctx->stage[NH_STAGE_CALL0], &d_dirs_buf = ctx->stage[NH_STAGE_CALL1], &d_integ_buf = ctx->stage[NH_STAGE_CALL2];
-    rc = nh_ensure_buf(ctx, d_reqs, (size_t)n * sizeof(navhip_field_req));
-    if(!rc) rc = nh_ensure_buf(ctx, d_dirs_buf, (size_t)n * NH_CELLS);
-    if(!rc && out_integ) rc = nh_ensure_buf(ctx, d_integ_buf, (size_t)n * NH_CELLS * sizeof(float));
-    if(rc) return rc;
-    uint8_t *d_dirs = (uint8_t*)d_dirs_buf.p;
-    float *d_integ = out_integ ? (float*)d_integ_buf.p : nullptr;
-    HIPCHK(ctx, hipMemcpyAsync(d_reqs.p, reqs, (size_t)n * sizeof(navhip_field_req),
-                               hipMemcpyHostToDevice, s));
     bool any_inout = false;
     for(int i = 0; i < n; i++)      // skipped (IF_CHANGED) slots must come back unchanged too
         any_inout |= (reqs[i].flags & (NAVHIP_REQ_INOUT | NAVHIP_REQ_IF_CHANGED | NAVHIP_REQ_ISLAND_NEAREST)) != 0
                   || reqs[i].type == NAVHIP_TARGET_NEAREST_PATHABLE;
-    if(any_inout)
-        HIPCHK(ctx, hipMemcpyAsync(d_dirs, inout_dirs, (size_t)n * NH_CELLS,
-                                   hipMemcpyHostToDevice, s));
-    rc = navhip_build_fields_dev(ctx, (const navhip_field_req*)d_reqs.p, n, d_dirs, d_integ, s);
+    const size_t dirs_bytes = (size_t)n * NH_CELLS, integ_bytes = dirs_bytes * sizeof(float);
+    const navhip_field_req *d_reqs;
+    uint8_t *d_dirs = nullptr;
+    float *d_integ = nullptr;
+    rc = nh_stage_in(ctx, NH_STAGE_CALL0, reqs, (size_t)n * sizeof(navhip_field_req), (const void**)&d_reqs, s);
+    if(!rc) rc = any_inout ? nh_stage_in(ctx, NH_STAGE_CALL1, inout_dirs, dirs_bytes, (const void**)&d_dirs, s)
+                           : nh_stage_reserve(ctx, NH_STAGE_CALL1, dirs_bytes, (void**)&d_dirs);
+    if(!rc && out_integ) rc = nh_stage_reserve(ctx, NH_STAGE_CALL2, integ_bytes, (void**)&d_integ);
+    if(!rc) rc = navhip_build_fields_dev(ctx, d_reqs, n, d_dirs, d_integ, s);
     if(rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(inout_dirs, d_dirs, (size_t)n * NH_CELLS,
-                               hipMemcpyDeviceToHost, s));
-    if(out_integ)
-        HIPCHK(ctx, hipMemcpyAsync(out_integ, d_integ, (size_t)n * NH_CELLS * sizeof(float),
-                                   hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(inout_dirs, d_dirs, dirs_bytes, hipMemcpyDeviceToHost, s));
+    if(out_integ) HIPCHK(ctx, hipMemcpyAsync(out_integ, d_integ, integ_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     return NAVHIP_OK;
 }
 
-int navhip_get_counters(navhip_ctx *ctx, navhip_counters *out, int reset)
+int navhip_set_field_kernel(navhip_ctx *ctx, int mode)
+{
+    if(!ctx || mode < 0 || mode > 1) return NAVHIP_ERR_INVALID;
+    ctx->field_kernel_mode = mode;
+    return NAVHIP_OK;
+}
+
+int navhip_last_fields_split(navhip_ctx *ctx, int32_t out[2])
 {
     if(!ctx || !out) return NAVHIP_ERR_INVALID;
-    *out = ctx->counters;
-    if(reset) memset(&ctx->counters, 0, sizeof(ctx->counters));
-    return NAVHIP_OK;
-}
-
-int navhip_region_lookup(navhip_ctx *ctx, int nq, const float *pos_xz, const int32_t *rows,
-                         const int32_t *region_field_slot, int n_region_rows, const uint8_t *field_pool,
-                         int n_field_slots, const int32_t *centre_abs, const int32_t *radius,
-                         float map_pos_x, float map_pos_z, uint8_t *out_dir, uint8_t *out_at_slot)
-{
-    if(!ctx || nq < 0 || (nq > 0 && (!pos_xz || !rows || !out_dir))) return NAVHIP_ERR_INVALID;
-    if((out_at_slot != nullptr) && (!centre_abs || !radius)) return NAVHIP_ERR_INVALID;
-    if(nq == 0) return NAVHIP_OK;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    nh_step_params P;
-    memset(&P, 0, sizeof(P));
-    nh_fill_map_view(ctx, &P.map);
-    P.map_x = map_pos_x; P.map_z = map_pos_z;
-    const size_t nchunks = (size_t)ctx->nchunks;
-    const bool resident = !region_field_slot && !field_pool;
-    if(resident) {
-        if(!ctx->pool) { ctx->last_error = "navhip_region_lookup: no table given and no resident pool"; return NAVHIP_ERR_INVALID; }
-        P.region_field_slot = nh_pool_map(ctx); P.field_pool = nh_pool_fields(ctx);
-        n_region_rows = nh_pool_dests(ctx);
-    }else{
-        if(!region_field_slot || !field_pool || n_region_rows < 1 || n_field_slots < 1) return NAVHIP_ERR_INVALID;
-        // (the slots of the world's own tables: the same data)
-        int rc = nh_stage_in(ctx, NH_STAGE_REGION_FIELD_SLOT, region_field_slot, (size_t)n_region_rows * nchunks * 4, (const void**)&P.region_field_slot, s);
-        if(!rc) rc = nh_stage_in(ctx, NH_STAGE_FIELD_POOL, field_pool, (size_t)n_field_slots * NH_CELLS, (const void**)&P.field_pool, s);
-        if(rc) return rc;
-        nh_async_invalidate_static(ctx);
-    }
-    for(int q = 0; q < nq; q++)
-        if(rows[q] < -1 || rows[q] >= n_region_rows) return NAVHIP_ERR_INVALID;
-    const float *d_pos; const int32_t *d_rows, *d_cen = nullptr, *d_rad = nullptr;
-    uint8_t *d_out = nullptr;
-    int rc = nh_stage_in(ctx, NH_STAGE_CALL0, pos_xz, (size_t)nq * 8, (const void**)&d_pos, s);
-    if(!rc) rc = nh_stage_in(ctx, NH_STAGE_CALL1, rows, (size_t)nq * 4, (const void**)&d_rows, s);
-    if(!rc && out_at_slot) rc = nh_stage_in(ctx, NH_STAGE_CALL2, centre_abs, (size_t)nq * 8, (const void**)&d_cen, s);
-    if(!rc && out_at_slot) rc = nh_stage_in(ctx, NH_STAGE_CALL3, radius, (size_t)nq * 4, (const void**)&d_rad, s);
-    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_CALL4, (size_t)nq * 2, (void**)&d_out);
-    if(rc) return rc;
-    nh_launch_region_lookup(P, nq, d_pos, d_rows, d_cen, d_rad, d_out, d_out + nq, s);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out_dir, d_out, (size_t)nq, hipMemcpyDeviceToHost, s));
-    if(out_at_slot) HIPCHK(ctx, hipMemcpyAsync(out_at_slot, d_out + nq, (size_t)nq, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return NAVHIP_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// ClearPath batches, field ids
-// ---------------------------------------------------------------------------------------------
-static int clearpath_batch(navhip_ctx *ctx, int nq, const float *ent, const float *des_v,
-                           const float *dyn, const int32_t *n_dyn, const float *stat,
-                           const int32_t *n_stat, float *out, int rows)
-{
-    if(!ctx || nq < 0 || !ent || !des_v || !dyn || !n_dyn || !stat || !n_stat || !out)
+    if(ctx->last_fields.n < 0) {
+        ctx->last_error = "navhip_last_fields_split: no chunk-field build yet";
         return NAVHIP_ERR_INVALID;
-    if(nq == 0) return NAVHIP_OK;
-    for(int i = 0; i < nq; i++) {
-        if(n_dyn[i] < 0 || n_dyn[i] > 32 || n_stat[i] < 0 || n_stat[i] > 32) return NAVHIP_ERR_INVALID;
-        if(rows == 1 && n_dyn[i] + n_stat[i] > NH_ROW_MAX) return NAVHIP_ERR_INVALID;
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const void *d[6];
-    const struct { const void *host; size_t bytes; nh_stage_slot slot; } in[6] = {
-        {ent, (size_t)nq * 20, NH_STAGE_CALL0},   {des_v, (size_t)nq * 8, NH_STAGE_CALL1},  {dyn, (size_t)nq * 640, NH_STAGE_CALL2},
-        {n_dyn, (size_t)nq * 4, NH_STAGE_CALL3},  {stat, (size_t)nq * 640, NH_STAGE_CALL4}, {n_stat, (size_t)nq * 4, NH_STAGE_CALL5}};
-    for(int i = 0; i < 6; i++) {
-        int rc = nh_stage_in(ctx, in[i].slot, in[i].host, in[i].bytes, &d[i], s);
-        if(rc) return rc;
-    }
-    float *d_out = nullptr;
-    int rc = nh_stage_reserve(ctx, NH_STAGE_CALL6, (size_t)nq * 8, (void**)&d_out);
-    if(rc) return rc;
-    nh_launch_clearpath(nq, (const float*)d[0], (const float*)d[1], (const float*)d[2],
-                        (const int32_t*)d[3], (const float*)d[4], (const int32_t*)d[5], d_out, rows, s);
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(out, d_out, (size_t)nq * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
+    int32_t generic = ctx->last_fields.n;           // (forced: no list, k_field_generic built every request)
+    if(ctx->last_fields.gen_slot >= 0)
+        // the counter the two kernels keep anyway: it stays until the launch after the next one zeroes it
+        HIPCHK(ctx, hipMemcpyAsync(&generic, (const int32_t*)ctx->gen_list.p + ctx->last_fields.gen_slot, sizeof(int32_t),
+                                   hipMemcpyDeviceToHost, ctx->last_fields.stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->last_fields.stream));
+    out[0] = ctx->last_fields.n - generic; out[1] = generic;
     return NAVHIP_OK;
-}
-
-int navhip_clearpath(navhip_ctx *ctx, int nq, const float *ent, const float *des_v,
-                     const float *dyn, const int32_t *n_dyn, const float *stat,
-                     const int32_t *n_stat, float *out)
-{
-    return clearpath_batch(ctx, nq, ent, des_v, dyn, n_dyn, stat, n_stat, out, 0);
-}
-
-int navhip_clearpath_rows(navhip_ctx *ctx, int nq, const float *ent, const float *des_v,
-                          const float *dyn, const int32_t *n_dyn, const float *stat,
-                          const int32_t *n_stat, float *out)
-{
-    return clearpath_batch(ctx, nq, ent, des_v, dyn, n_dyn, stat, n_stat, out, 1);
-}
-
-int navhip_clearpath_team(navhip_ctx *ctx, int nq, const float *ent, const float *des_v,
-                          const float *dyn, const int32_t *n_dyn, const float *stat,
-                          const int32_t *n_stat, float *out)
-{
-    return clearpath_batch(ctx, nq, ent, des_v, dyn, n_dyn, stat, n_stat, out, 2);
 }
 
 uint64_t navhip_flow_field_id(const navhip_field_req *r)

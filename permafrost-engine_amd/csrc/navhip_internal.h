@@ -289,7 +289,7 @@ template<class F> static inline void nh_ctx_each_buf(navhip_ctx *ctx, F f)
 }
 
 // The library's streams: one set per process and device, each with a hardware queue of its own, chosen per caller stream
-// so that streams which hand over to each other sit on different pipes of the command processor (navhip_api.hip has the
+// so that streams which hand over to each other sit on different pipes of the command processor (stream_set.hip has the
 // measurements behind this).  Borrowed by contexts and ticks; never destroyed.
 enum { NH_STREAM_SIDE0 = 0,     // the ClearPath side chain of the agent step
        NH_STREAM_SIDE1,         // the cohesion term
@@ -343,13 +343,13 @@ bool     nh_handover_failed(navhip_ctx *ctx);                                   
 extern "C" int nh_validate_field_reqs(navhip_ctx *ctx, const navhip_field_req *reqs, int n);   /* (library internal) */
 int  navhip_build_fields_slots_dev(navhip_ctx *ctx, const navhip_field_req *dev_reqs, int n, uint8_t *dev_fields,
                                    const int32_t *dev_slots, hipStream_t s);
-int  nh_ensure(navhip_ctx *ctx, nh_buf &b, size_t need);          // b holds at least `need` bytes (contents are not kept)
-int  nh_ensure_buf(navhip_ctx *ctx, nh_buf &b, size_t need);      // the step's scratch and the staging slots: at least 16 bytes, a buffer that moved is counted
-// step_api.hip: a host array copied to its staging slot (*dst: the device copy, NULL stays NULL); the world's arrays, row
-// by row of nh_world_rows, `only`: just these members (their offsets)
-int  nh_stage_in(navhip_ctx *ctx, nh_stage_slot slot, const void *host, size_t bytes, const void **dst, hipStream_t s);
-int  nh_stage_world(navhip_ctx *ctx, const navhip_world *w, navhip_world *d, hipStream_t s, std::initializer_list<size_t> only = {});
+// navhip_api.hip: device buffers grown on demand and the staging path of the host-buffer entry points (described there)
+int  nh_ensure(navhip_ctx *ctx, nh_buf &b, size_t need);
+int  nh_ensure_buf(navhip_ctx *ctx, nh_buf &b, size_t need);
 int  nh_stage_reserve(navhip_ctx *ctx, nh_stage_slot slot, size_t bytes, void **dev);
+int  nh_stage_in(navhip_ctx *ctx, nh_stage_slot slot, const void *host, size_t bytes, const void **dst, hipStream_t s);
+// step_api.hip: the world's arrays, row by row of nh_world_rows, `only`: just these members (their offsets)
+int  nh_stage_world(navhip_ctx *ctx, const navhip_world *w, navhip_world *d, hipStream_t s, std::initializer_list<size_t> only = {});
 void nh_async_destroy(navhip_ctx *ctx);
 void nh_async_invalidate_static(navhip_ctx *ctx);   // the staging buffers were used by someone else
 bool nh_async_resident(navhip_ctx *ctx, navhip_world *w, navhip_step_out *o);   // snapshot + outputs the last completed submit left on the device

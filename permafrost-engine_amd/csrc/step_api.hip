@@ -1,6 +1,7 @@
 // step_api.hip -- the host side of the agent step (no kernel lives here): its scratch, the schedule of a tick's launches
 // over the caller's stream and the two side streams, the prefetch that starts the snapshot-only
-// part early, and the host-buffer entry points that stage a world and run a step or a spatial query on it.
+// part early, and the host-buffer entry points that stage a world and run a step on it -- or a spatial query, a region
+// lookup, a batch of ClearPath problems: the test utilities over the agent kernels.
 #include "navhip_internal.h"
 #include "agent_internal.h"
 #include "agent_thread.h"
@@ -286,21 +287,8 @@ static bool coh_regroup_due(navhip_ctx *ctx, const nh_step_params &P)
 }
 
 // ---------------------------------------------------------------------------------------------
-// staging of host buffers (shared with navhip_api.hip and state_kernels.hip)
+// staging of a world (array by array through nh_stage_in, navhip_api.hip)
 // ---------------------------------------------------------------------------------------------
-// copy a host array to a staging buffer; returns device pointer through *dst (NULL stays NULL)
-int nh_stage_in(navhip_ctx *ctx, nh_stage_slot slot, const void *host, size_t bytes, const void **dst, hipStream_t s)
-{
-    nh_async_invalidate_static(ctx);
-    *dst = nullptr;
-    if(!host) return NAVHIP_OK;
-    int rc = nh_ensure_buf(ctx, ctx->stage[slot], bytes);
-    if(rc) return rc;
-    if(bytes) HIPCHK(ctx, hipMemcpyAsync(ctx->stage[slot].p, host, bytes, hipMemcpyHostToDevice, s));
-    *dst = ctx->stage[slot].p;
-    return NAVHIP_OK;
-}
-
 // the world's arrays, staged row by row of nh_world_rows; `only`: just these members (their offsets)
 int nh_stage_world(navhip_ctx *ctx, const navhip_world *w, navhip_world *d, hipStream_t s, std::initializer_list<size_t> only)
 {
@@ -671,6 +659,106 @@ int navhip_spatial_query(navhip_ctx *ctx, const navhip_world *w, const float *qu
                                hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     return NAVHIP_OK;
+}
+
+int navhip_region_lookup(navhip_ctx *ctx, int nq, const float *pos_xz, const int32_t *rows,
+                         const int32_t *region_field_slot, int n_region_rows, const uint8_t *field_pool,
+                         int n_field_slots, const int32_t *centre_abs, const int32_t *radius,
+                         float map_pos_x, float map_pos_z, uint8_t *out_dir, uint8_t *out_at_slot)
+{
+    if(!ctx || nq < 0 || (nq > 0 && (!pos_xz || !rows || !out_dir))) return NAVHIP_ERR_INVALID;
+    if((out_at_slot != nullptr) && (!centre_abs || !radius)) return NAVHIP_ERR_INVALID;
+    if(nq == 0) return NAVHIP_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    nh_step_params P;
+    memset(&P, 0, sizeof(P));
+    nh_fill_map_view(ctx, &P.map);
+    P.map_x = map_pos_x; P.map_z = map_pos_z;
+    const size_t nchunks = (size_t)ctx->nchunks;
+    const bool resident = !region_field_slot && !field_pool;
+    if(resident) {
+        if(!ctx->pool) { ctx->last_error = "navhip_region_lookup: no table given and no resident pool"; return NAVHIP_ERR_INVALID; }
+        P.region_field_slot = nh_pool_map(ctx); P.field_pool = nh_pool_fields(ctx);
+        n_region_rows = nh_pool_dests(ctx);
+    }else{
+        if(!region_field_slot || !field_pool || n_region_rows < 1 || n_field_slots < 1) return NAVHIP_ERR_INVALID;
+        // (the slots of the world's own tables: the same data)
+        int rc = nh_stage_in(ctx, NH_STAGE_REGION_FIELD_SLOT, region_field_slot, (size_t)n_region_rows * nchunks * 4, (const void**)&P.region_field_slot, s);
+        if(!rc) rc = nh_stage_in(ctx, NH_STAGE_FIELD_POOL, field_pool, (size_t)n_field_slots * NH_CELLS, (const void**)&P.field_pool, s);
+        if(rc) return rc;
+        nh_async_invalidate_static(ctx);
+    }
+    for(int q = 0; q < nq; q++)
+        if(rows[q] < -1 || rows[q] >= n_region_rows) return NAVHIP_ERR_INVALID;
+    const float *d_pos; const int32_t *d_rows, *d_cen = nullptr, *d_rad = nullptr;
+    uint8_t *d_out = nullptr;
+    int rc = nh_stage_in(ctx, NH_STAGE_CALL0, pos_xz, (size_t)nq * 8, (const void**)&d_pos, s);
+    if(!rc) rc = nh_stage_in(ctx, NH_STAGE_CALL1, rows, (size_t)nq * 4, (const void**)&d_rows, s);
+    if(!rc && out_at_slot) rc = nh_stage_in(ctx, NH_STAGE_CALL2, centre_abs, (size_t)nq * 8, (const void**)&d_cen, s);
+    if(!rc && out_at_slot) rc = nh_stage_in(ctx, NH_STAGE_CALL3, radius, (size_t)nq * 4, (const void**)&d_rad, s);
+    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_CALL4, (size_t)nq * 2, (void**)&d_out);
+    if(rc) return rc;
+    nh_launch_region_lookup(P, nq, d_pos, d_rows, d_cen, d_rad, d_out, d_out + nq, s);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(out_dir, d_out, (size_t)nq, hipMemcpyDeviceToHost, s));
+    if(out_at_slot) HIPCHK(ctx, hipMemcpyAsync(out_at_slot, d_out + nq, (size_t)nq, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return NAVHIP_OK;
+}
+
+// the ClearPath kernels on nq problems in host arrays; rows: nh_launch_clearpath
+static int clearpath_batch(navhip_ctx *ctx, int nq, const float *ent, const float *des_v,
+                           const float *dyn, const int32_t *n_dyn, const float *stat,
+                           const int32_t *n_stat, float *out, int rows)
+{
+    if(!ctx || nq < 0 || !ent || !des_v || !dyn || !n_dyn || !stat || !n_stat || !out)
+        return NAVHIP_ERR_INVALID;
+    if(nq == 0) return NAVHIP_OK;
+    for(int i = 0; i < nq; i++) {
+        if(n_dyn[i] < 0 || n_dyn[i] > 32 || n_stat[i] < 0 || n_stat[i] > 32) return NAVHIP_ERR_INVALID;
+        if(rows == 1 && n_dyn[i] + n_stat[i] > NH_ROW_MAX) return NAVHIP_ERR_INVALID;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const void *d[6];
+    const struct { const void *host; size_t bytes; nh_stage_slot slot; } in[6] = {
+        {ent, (size_t)nq * 20, NH_STAGE_CALL0},   {des_v, (size_t)nq * 8, NH_STAGE_CALL1},  {dyn, (size_t)nq * 640, NH_STAGE_CALL2},
+        {n_dyn, (size_t)nq * 4, NH_STAGE_CALL3},  {stat, (size_t)nq * 640, NH_STAGE_CALL4}, {n_stat, (size_t)nq * 4, NH_STAGE_CALL5}};
+    for(int i = 0; i < 6; i++) {
+        int rc = nh_stage_in(ctx, in[i].slot, in[i].host, in[i].bytes, &d[i], s);
+        if(rc) return rc;
+    }
+    float *d_out = nullptr;
+    int rc = nh_stage_reserve(ctx, NH_STAGE_CALL6, (size_t)nq * 8, (void**)&d_out);
+    if(rc) return rc;
+    nh_launch_clearpath(nq, (const float*)d[0], (const float*)d[1], (const float*)d[2],
+                        (const int32_t*)d[3], (const float*)d[4], (const int32_t*)d[5], d_out, rows, s);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(out, d_out, (size_t)nq * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return NAVHIP_OK;
+}
+
+int navhip_clearpath(navhip_ctx *ctx, int nq, const float *ent, const float *des_v,
+                     const float *dyn, const int32_t *n_dyn, const float *stat,
+                     const int32_t *n_stat, float *out)
+{
+    return clearpath_batch(ctx, nq, ent, des_v, dyn, n_dyn, stat, n_stat, out, 0);
+}
+
+int navhip_clearpath_rows(navhip_ctx *ctx, int nq, const float *ent, const float *des_v,
+                          const float *dyn, const int32_t *n_dyn, const float *stat,
+                          const int32_t *n_stat, float *out)
+{
+    return clearpath_batch(ctx, nq, ent, des_v, dyn, n_dyn, stat, n_stat, out, 1);
+}
+
+int navhip_clearpath_team(navhip_ctx *ctx, int nq, const float *ent, const float *des_v,
+                          const float *dyn, const int32_t *n_dyn, const float *stat,
+                          const int32_t *n_stat, float *out)
+{
+    return clearpath_batch(ctx, nq, ent, des_v, dyn, n_dyn, stat, n_stat, out, 2);
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-// stream_set.hip -- the streams the library runs its side chains on (nh_streams_for, nh_stream_partial_for).
+// stream_set.hip -- the streams the library runs its side chains on (nh_streams_for, nh_stream_partial_for), the words they
+// hand over through, and the entry points that lend a stream of the set to the caller (navhip_stream_*).
 #include "navhip_internal.h"
 #include <array>
 #include <chrono>
@@ -422,3 +423,42 @@ hipStream_t nh_stream_partial_for(navhip_ctx *ctx, hipStream_t main, int cu_begi
     for(hipStream_t r : surplus) hipStreamDestroy(r);
     return P[want];
 }
+
+extern "C" {
+
+int navhip_stream_beside(navhip_ctx *ctx, void *main_stream, int cu_begin, int cu_count, void **out_stream)
+{
+    if(!ctx || !out_stream || cu_begin < 0) return NAVHIP_ERR_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = nullptr;
+    if(cu_count <= 0) {
+        hipStream_t all[NH_STREAM_FIXED];
+        int rc = nh_streams_for(ctx, (hipStream_t)main_stream, all);
+        if(rc) return rc;
+        st = all[NH_STREAM_FIELDS];
+    }else{
+        st = nh_stream_partial_for(ctx, (hipStream_t)main_stream, cu_begin, cu_count);
+        if(!st) return ctx->last_error.empty() ? NAVHIP_ERR_INVALID : NAVHIP_ERR_DEVICE;
+    }
+    *out_stream = (void*)st;
+    return NAVHIP_OK;
+}
+
+int navhip_stream_main(navhip_ctx *ctx, void **out_stream)
+{
+    if(!ctx || !out_stream) return NAVHIP_ERR_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t all[NH_STREAM_FIXED];
+    int rc = nh_streams_for(ctx, nullptr, all);
+    if(rc) return rc;
+    *out_stream = (void*)all[NH_STREAM_MAIN];
+    return NAVHIP_OK;
+}
+
+int navhip_stream_create_partial(navhip_ctx *ctx, int cu_begin, int cu_count, void **out_stream)
+{
+    if(cu_count <= 0) return NAVHIP_ERR_INVALID;
+    return navhip_stream_beside(ctx, ctx ? (void*)ctx->stream : nullptr, cu_begin, cu_count, out_stream);
+}
+
+}  // extern "C"

@@ -442,6 +442,33 @@ def test_pool_and_submit_are_two_units_with_one_of_each_helper():
         assert not re.search(r"\b%s\b" % name, ctx_body) and not re.search(r"\b%s\b" % name, each_buf), name
 
 
+def test_map_unit_holds_map_state_only_with_one_plane_table_and_one_staging_path():
+    """csrc/navhip_api.hip is the context, the planes with their derived masks, the blockers and the field builds: the
+    stream fronts live in stream_set.hip, the host-pointer utilities over the agent kernels in step_api.hip, and the unit
+    includes no agent header and opens extern "C" once; the planes are described by a table (no switch over the plane
+    number), guarded by a static_assert on NAVHIP_PLANE_COUNT; the four staging helpers are defined side by side."""
+    csrc = os.path.join(ROOT, "permafrost-engine_amd", "csrc")
+    units = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(".hip")}
+    api = units["navhip_api.hip"]
+    assert "agent_internal.h" not in api and "agent_thread.h" not in api
+    assert len(re.findall(r'extern\s+"C"\s*\{', api)) == 1
+    assert not re.search(r"switch\s*\(\s*plane\s*\)", api)
+    assert re.search(r"static_assert\([^;]*plane_rows[^;]*NAVHIP_PLANE_COUNT", api, re.S)
+    moved = {"navhip_stream_beside": "stream_set.hip", "navhip_stream_main": "stream_set.hip",
+             "navhip_stream_create_partial": "stream_set.hip", "navhip_region_lookup": "step_api.hip",
+             "navhip_clearpath": "step_api.hip", "navhip_clearpath_rows": "step_api.hip", "navhip_clearpath_team": "step_api.hip",
+             "clearpath_batch": "step_api.hip"}
+    for name, unit in moved.items():
+        homes = [f for f, src in units.items() if re.search(r"^(?:static )?int %s\(" % name, src, re.M)]
+        assert homes == [unit], (name, homes)
+    helpers = ("nh_ensure", "nh_ensure_buf", "nh_stage_reserve", "nh_stage_in")
+    homes = {h: [f for f, src in units.items() if re.search(r"^int %s\(" % h, src, re.M)] for h in helpers}
+    assert all(len(v) == 1 for v in homes.values()) and len(set(v[0] for v in homes.values())) == 1, homes
+    for entry in ("navhip_upload_plane", "navhip_upload_chunk", "navhip_download_plane", "navhip_build_fields",
+                  "navhip_build_los", "navhip_build_region_fields", "navhip_blockers_circles"):
+        assert re.search(r"^int %s\(" % entry, api, re.M), entry
+
+
 def test_state_staging_tables_cover_every_array():
     """csrc/state_kernels.hip stages the input and output structs of the state half of the tick from ONE list per
     struct (sk_gate_rows, sk_state_rows, sk_aux_rows, sk_pass_out_rows, sk_settle_in_rows, sk_settle_out_rows): each
