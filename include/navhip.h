@@ -274,6 +274,45 @@ int  navhip_build_los_dev(navhip_ctx *ctx, const navhip_los_req *dev_reqs, int n
                           const uint8_t *dev_prev_fields, uint8_t *dev_out_fields,
                           float map_pos_x, float map_pos_z, void *stream);
 
+/* A resident LOS chain: the LOS fields of a fixed set of (destination, chunk) slots, kept current while blockers move.
+ * The reference drops the LOS fields of a dirty chunk together with its flow fields (fieldcache.c:213-227, 526-535) and
+ * rebuilds a missing one from the cached field of the chunk before it on the path (nav.c:2026-2039, 4042-4047); a chain
+ * does both on the device, behind navhip_blockers_circles[_dev] and from the changed-chunk flags those leave.
+ *   reqs, prev_slot  HOST arrays of n entries (copied).  Slot i is field i of dev_pool; prev_slot[i] is the slot of the
+ *                    field request i continues (its prev_los), -1 for the destination chunk's own field.  Slots are
+ *                    in LEVEL order (level = 0 without a predecessor, else the predecessor's + 1, non-decreasing).
+ *   dev_pool         DEVICE, n * 4096 bytes, the caller's: what navhip_world.los_pool points at.  Slots never move.
+ * NAVHIP_ERR_INVALID, with the reason in navhip_last_error, unless for every slot: prev_slot[i] == -1 exactly where
+ * prev_dr == prev_dc == 0, otherwise 0 <= prev_slot[i] < i; the predecessor's chunk is chunk + (prev_dr, prev_dc) and its
+ * layer and target are this slot's; levels do not decrease; the layer is resident -- and faction_id is
+ * NAVHIP_FACTION_ID_NONE: the changed-chunk flags say "passability WITHOUT a faction changed" and do not cover the
+ * field of an attacking path, which a chain could therefore not keep current. */
+typedef struct navhip_los_chain navhip_los_chain;
+enum { NAVHIP_LOS_REFRESH_DOWNSTREAM = 1u };
+typedef struct navhip_los_chain_stats {
+    int32_t slots, levels;
+    int32_t stale;      /* slots whose own chunk was flagged changed, summed over every refresh so far        */
+    int32_t rebuilt;    /* fields the refreshes rebuilt: the same number, plus -- with NAVHIP_LOS_REFRESH_DOWNSTREAM --
+                           the fields built from a stale one                                                  */
+    int32_t redone;     /* fields a build left to its second launch (more than 1 022 tiles in the frontier)    */
+} navhip_los_chain_stats;
+int  navhip_los_chain_create(navhip_ctx *ctx, const navhip_los_req *reqs, const int32_t *prev_slot, int n,
+                             uint8_t *dev_pool, float map_pos_x, float map_pos_z, navhip_los_chain **out);
+/* Every slot, level by level: one pair of launches per level, each field from its predecessor IN the pool (which need
+ * not hold anything before).  The bytes navhip_build_los_dev gives level by level.  Asynchronous on `stream`. */
+int  navhip_los_chain_build(navhip_los_chain *chain, void *stream);
+/* Only what the changed chunks make stale; asynchronous on `stream`, no host round trip, no allocation.
+ *   flags 0                              the reference: the fields ON changed chunks are dropped, and each is rebuilt --
+ *                                        in level order -- from whatever its predecessor holds then
+ *   NAVHIP_LOS_REFRESH_DOWNSTREAM        ... and every field built from a rebuilt one: the pool equals a
+ *                                        navhip_los_chain_build on the current planes
+ * Reads the changed-chunk flags and clears nothing: that stays navhip_clear_changed. */
+int  navhip_los_chain_refresh(navhip_los_chain *chain, uint32_t flags, void *stream);
+/* Waits for the last build / refresh. */
+int  navhip_los_chain_get_stats(navhip_los_chain *chain, navhip_los_chain_stats *out);
+/* (before the context) */
+void navhip_los_chain_destroy(navhip_los_chain *chain);
+
 /* N_FlowFieldID (field.c:1952) for TILE / PORTAL targets: the 64-bit cache key the reference's
  * fieldcache uses; pure bit packing, host side. */
 uint64_t navhip_flow_field_id(const navhip_field_req *req);
@@ -659,6 +698,10 @@ int  navhip_tick_run(navhip_tick *tick, int n);
  * compute = everything up to the exchange of ONE tick, advance = the ping-pong behind the host's exchange. */
 int  navhip_tick_compute(navhip_tick *tick);
 int  navhip_tick_advance(navhip_tick *tick);
+/* A LOS chain for the tick to keep current (NULL: none, the default): every tick that applies a batch of dev_moves
+ * enqueues navhip_los_chain_refresh(chain, flags, the tick's stream) behind the batch and in front of the
+ * navhip_clear_changed that ends it -- in front of the step that samples the pool.  The chain stays the caller's. */
+int  navhip_tick_set_los_chain(navhip_tick *tick, navhip_los_chain *chain, uint32_t flags);
 int  navhip_tick_sync(navhip_tick *tick);
 int  navhip_tick_get_info(const navhip_tick *tick, navhip_tick_info *out);
 void navhip_tick_destroy(navhip_tick *tick);

@@ -97,19 +97,41 @@ __device__ __forceinline__ bool los_corner(const uint8_t *fl, int r, int c)
     return false;
 }
 
+// What a resident LOS chain (los_chain_api.hip) adds to a launch: requests, overflow flags and fields are indexed by
+// the SLOT -- block b builds slot slot0 + b, or list[b] when there is a list (then *count, in device memory, says how
+// many blocks have one) -- and the predecessor is field prev_slot[slot] of the same pool the slot is written into.
+struct nh_los_chain_args {
+    const int32_t *prev_slot;   // NULL: not a chain (request b, prev_fields + b * 4096, out_fields + b * 4096)
+    const int32_t *list, *count;
+    int32_t       *redone;      // REDO: fields rebuilt with room for every tile, counted
+    int            slot0;
+};
+
 // CAP: heap nodes.  overflow[ri]: set by the CAP = 1022 launch for a field it gave up on; the CAP = 4096
-// launch (REDO) only builds those.
-template <int CAP, bool REDO>
+// launch (REDO) only builds those.  CHAIN: nh_los_chain_args; a CHAIN launch with CAP = 4096 that is no REDO holds every
+// tile, cannot give up and has no overflow flags.
+template <int CAP, bool REDO, bool CHAIN>
 __global__ __launch_bounds__(64) void k_los_field(nh_map_view map, const navhip_los_req *reqs, int n,
                                                   const uint8_t *prev_fields, uint8_t *out_fields,
-                                                  float map_x, float map_z, uint8_t *overflow)
+                                                  float map_x, float map_z, uint8_t *overflow, nh_los_chain_args ch)
 {
     __shared__ __attribute__((aligned(4))) uint16_t h_node[CAP + 2];
     __shared__ __attribute__((aligned(16))) uint8_t fl[NH_CELLS];
     __shared__ int s_over;
-    const int ri = blockIdx.x, lane = threadIdx.x;
+    constexpr bool FLAGS = REDO || !(CHAIN && CAP == 4096);      // the launch reads or writes overflow[]
+    const int lane = threadIdx.x;
+    int ri = blockIdx.x;
     if(ri >= n) return;
+    if(CHAIN) {
+        if(ch.list) {
+            if(ri >= *ch.count) return;
+            ri = ch.list[ri];
+        }else{
+            ri += ch.slot0;
+        }
+    }
     if(REDO && !overflow[ri]) return;
+    if(REDO && CHAIN && ch.redone && lane == 0) atomicAdd(ch.redone, 1);
     if(lane == 0) s_over = 0;
     const navhip_los_req rq = reqs[ri];
     const nh_layer_view &L = map.layers[rq.layer];
@@ -154,7 +176,7 @@ __global__ __launch_bounds__(64) void k_los_field(nh_map_view map, const navhip_
             fl[t] |= LF_ASSIGNED | LF_INHEAP;
         }else{
             // case 2, field.c:2122-2193: carry the shared edge over from the previous chunk's field
-            const uint8_t *prev = prev_fields + ((size_t)ri << 12);
+            const uint8_t *prev = prev_fields + ((size_t)(CHAIN ? ch.prev_slot[ri] : ri) << 12);
             const bool horizontal = rq.prev_dr == 0;
             int curr_edge, prev_edge;
             if(!horizontal) { curr_edge = rq.prev_dr < 0 ? 0 : 63; prev_edge = rq.prev_dr < 0 ? 63 : 0; }
@@ -237,7 +259,7 @@ __global__ __launch_bounds__(64) void k_los_field(nh_map_view map, const navhip_
             }
         }
         s_over = over ? 1 : 0;
-        if(!REDO) overflow[ri] = over ? 1 : 0;
+        if(!REDO && FLAGS) overflow[ri] = over ? 1 : 0;
     }
     __syncthreads();
     if(s_over) return;                     // (left to the launch with room for every tile)
@@ -266,10 +288,117 @@ void nh_launch_los(navhip_ctx *ctx, const navhip_los_req *d_reqs, int n, const u
 {
     nh_map_view mv;
     nh_fill_map_view(ctx, &mv);
+    const nh_los_chain_args none = {};
     if(n > 0) {
-        hipLaunchKernelGGL((k_los_field<1022, false>), dim3(n), dim3(64), 0, s, mv, d_reqs, n, d_prev, d_out, map_x,
-                           map_z, d_over);
-        hipLaunchKernelGGL((k_los_field<4096, true>), dim3(n), dim3(64), 0, s, mv, d_reqs, n, d_prev, d_out, map_x,
-                           map_z, d_over);
+        hipLaunchKernelGGL((k_los_field<1022, false, false>), dim3(n), dim3(64), 0, s, mv, d_reqs, n, d_prev, d_out, map_x,
+                           map_z, d_over, none);
+        hipLaunchKernelGGL((k_los_field<4096, true, false>), dim3(n), dim3(64), 0, s, mv, d_reqs, n, d_prev, d_out, map_x,
+                           map_z, d_over, none);
     }
+}
+
+// ---- resident LOS chains (los_chain_api.hip) -------------------------------------------------------------------------
+// One level of a chain, every slot [slot0, slot0 + n) of it, each from its predecessor in the pool: the pair of launches of
+// nh_launch_los, without a gathered copy of the predecessors.
+void nh_launch_los_chain_level(navhip_ctx *ctx, const nh_los_chain_view &c, int slot0, int n, hipStream_t s)
+{
+    nh_map_view mv;
+    nh_fill_map_view(ctx, &mv);
+    const nh_los_chain_args ch = {c.prev_slot, nullptr, nullptr, c.stats + NH_LCS_REDONE, slot0};
+    if(n > 0) {
+        hipLaunchKernelGGL((k_los_field<1022, false, true>), dim3(n), dim3(64), 0, s, mv, c.reqs, n, c.pool, c.pool, c.map_x,
+                           c.map_z, c.overflow, ch);
+        hipLaunchKernelGGL((k_los_field<4096, true, true>), dim3(n), dim3(64), 0, s, mv, c.reqs, n, c.pool, c.pool, c.map_x,
+                           c.map_z, c.overflow, ch);
+    }
+}
+
+// ... and the stale slots of one level (the level's part of c.list, c.count[level] of them): ONE launch with room for
+// every tile -- stale sets are small, half the launches.  The grid is the level's size; a block without a list entry ends
+// at once.
+void nh_launch_los_chain_stale(navhip_ctx *ctx, const nh_los_chain_view &c, int level, int slot0, int n, hipStream_t s)
+{
+    nh_map_view mv;
+    nh_fill_map_view(ctx, &mv);
+    const nh_los_chain_args ch = {c.prev_slot, c.list + slot0, c.count + level, nullptr, 0};
+    if(n > 0)
+        hipLaunchKernelGGL((k_los_field<4096, false, true>), dim3(n), dim3(64), 0, s, mv, c.reqs, n, c.pool, c.pool, c.map_x,
+                           c.map_z, (uint8_t*)nullptr, ch);
+}
+
+// Which slots of a chain the changed chunks make stale: stale[i] = changed[layer][chunk] of slot i, with `downstream`
+// also stale[prev_slot[i]] -- slots are in level order and a predecessor sits on the level before, so one pass over the
+// levels does it: ONE workgroup walks them, a barrier between two levels.  Per level the stale slots leave as a
+// compacted list in ascending slot order (list[level_begin[L] ...], count[L]): positions come from ballots and a prefix
+// over the waves' counts, never from an atomic append, so the list -- and with it the order of the rebuild's blocks --
+// is the same in every run.  cell[i] = layer << 24 | chunk index.
+#define LM_THREADS 256
+#define LM_ITEMS   4          /* slots per thread and step: LM_ITEMS independent loads in flight */
+#define LM_WAVES   (LM_THREADS / 64)
+__global__ __launch_bounds__(LM_THREADS) void k_los_mark(nh_map_view map, nh_los_chain_view c, int downstream)
+{
+    // [parity of the step][stale | changed itself][item][wave]: a step's counts are read behind ITS barrier only, and the
+    // step after the next cannot overwrite them before every wave has passed the next step's barrier
+    __shared__ int s_cnt[2][2][LM_ITEMS * LM_WAVES];
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int own_total = 0, stale_total = 0, parity = 0;
+    for(int L = 0; L < c.levels; L++) {
+        const int b = c.level_begin[L], e = c.level_begin[L + 1];
+        int n_out = 0;                                     // stale slots of this level so far
+        for(int s0 = b; s0 < e; s0 += LM_THREADS * LM_ITEMS, parity ^= 1) {
+            bool st[LM_ITEMS];
+            unsigned long long bal[LM_ITEMS];
+#pragma unroll
+            for(int k = 0; k < LM_ITEMS; k++) {
+                const int i = s0 + k * LM_THREADS + t;
+                bool own = false, inherited = false;
+                if(i < e) {
+                    const uint32_t cell = c.cell[i];
+                    const uint8_t *chg = map.layers[cell >> 24].changed;
+                    own = chg && chg[cell & 0xffffffu] != 0;
+                    // (the predecessor's flag was stored in front of the barrier that ended its level)
+                    if(downstream && L > 0) inherited = c.stale[c.prev_slot[i]] != 0;
+                    c.stale[i] = (own || inherited) ? 1 : 0;
+                }
+                st[k] = own || inherited;
+                bal[k] = __ballot(st[k]);
+                const unsigned long long bal_own = __ballot(own);
+                if(lane == 0) {
+                    s_cnt[parity][0][k * LM_WAVES + wave] = __popcll(bal[k]);
+                    s_cnt[parity][1][k * LM_WAVES + wave] = __popcll(bal_own);
+                }
+            }
+            __syncthreads();
+            // ascending slot order: item by item, wave by wave, lane by lane
+            int off = n_out;
+#pragma unroll
+            for(int k = 0; k < LM_ITEMS; k++) {
+                int mine = off;
+#pragma unroll
+                for(int w = 0; w < LM_WAVES; w++) {
+                    const int v = s_cnt[parity][0][k * LM_WAVES + w];
+                    if(w < wave) mine += v;
+                    off += v;
+                    own_total += s_cnt[parity][1][k * LM_WAVES + w];
+                }
+                if(st[k]) c.list[b + mine + __popcll(bal[k] & below)] = s0 + k * LM_THREADS + t;
+            }
+            n_out = off;
+        }
+        if(t == 0) c.count[L] = n_out;
+        stale_total += n_out;
+        __syncthreads();                                   // the level's flags are stored: the next level may read them
+    }
+    if(t == 0) {
+        c.stats[NH_LCS_STALE] += own_total;
+        c.stats[NH_LCS_REBUILT] += stale_total;
+    }
+}
+
+void nh_launch_los_chain_mark(navhip_ctx *ctx, const nh_los_chain_view &c, bool downstream, hipStream_t s)
+{
+    nh_map_view mv;
+    nh_fill_map_view(ctx, &mv);
+    hipLaunchKernelGGL(k_los_mark, dim3(1), dim3(LM_THREADS), 0, s, mv, c, downstream ? 1 : 0);
 }

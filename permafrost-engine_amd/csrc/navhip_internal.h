@@ -380,3 +380,24 @@ void nh_launch_region_fields(navhip_ctx *ctx, const navhip_region_req *d_reqs, i
 void nh_launch_los(navhip_ctx *ctx, const navhip_los_req *d_reqs, int n, const uint8_t *d_prev,
                    uint8_t *d_out, uint8_t *d_overlay, float map_x, float map_z, hipStream_t s);
 
+// A resident LOS chain as its kernels take it (los_chain_api.hip owns the memory, los_kernels.hip the launches).  Slots
+// are in level order: level L is the slots [level_begin[L], level_begin[L + 1]).
+enum { NH_LCS_STALE = 0, NH_LCS_REBUILT, NH_LCS_REDONE, NH_LCS_COUNT };
+struct nh_los_chain_view {
+    const navhip_los_req *reqs;         // [slots]
+    const int32_t  *prev_slot;          // [slots]      -1: the destination chunk's own field
+    const uint32_t *cell;               // [slots]      layer << 24 | chunk_r * w + chunk_c
+    const int32_t  *level_begin;        // [levels + 1]
+    uint8_t        *pool;               // [slots][4096] the caller's
+    uint8_t        *stale;              // [slots]      of the last refresh
+    uint8_t        *overflow;           // [slots]      of the last build: the field did not fit the small heap
+    int32_t        *list;               // [slots]      the stale slots of level L, compacted, from level_begin[L] on
+    int32_t        *count;              // [levels]     ... and how many
+    int32_t        *stats;              // [NH_LCS_COUNT] accumulated
+    int             slots, levels;
+    float           map_x, map_z;
+};
+void nh_launch_los_chain_level(navhip_ctx *ctx, const nh_los_chain_view &c, int slot0, int n, hipStream_t s);
+void nh_launch_los_chain_mark(navhip_ctx *ctx, const nh_los_chain_view &c, bool downstream, hipStream_t s);
+void nh_launch_los_chain_stale(navhip_ctx *ctx, const nh_los_chain_view &c, int level, int slot0, int n, hipStream_t s);
+

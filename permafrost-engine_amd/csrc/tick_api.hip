@@ -42,6 +42,8 @@ struct navhip_tick {
     bool             ft_used[8];
     int              ft_next;
     double           fields_ms_sum; int fields_samples;
+    navhip_los_chain *los_chain;      // navhip_tick_set_los_chain: refreshed behind every blocker batch, or NULL
+    uint32_t         los_flags;
 };
 
 static double now_ms()
@@ -105,6 +107,7 @@ static int compute_plain(navhip_tick *T)
         if(T->d.dev_moves) {
             const navhip_circle *mv = T->d.dev_moves + (size_t)((T->d.move_tick0 + T->ticks) % T->d.n_move_ticks) * T->d.n_moves;
             RCCHK(navhip_blockers_circles_dev(ctx, mv, T->d.n_moves, w->map_pos_x, w->map_pos_z, (void*)T->s));
+            if(T->los_chain) RCCHK(navhip_los_chain_refresh(T->los_chain, T->los_flags, (void*)T->s));
         }
         RCCHK(build_fields(T, T->pool[0], T->s));
         if(T->d.dev_moves) RCCHK(navhip_clear_changed(ctx, (void*)T->s));
@@ -148,6 +151,7 @@ static int compute_plain(navhip_tick *T)
         if(T->d.dev_moves) {
             const navhip_circle *mv = T->d.dev_moves + (size_t)((T->d.move_tick0 + T->ticks) % T->d.n_move_ticks) * T->d.n_moves;
             RCCHK(navhip_blockers_circles_dev(ctx, mv, T->d.n_moves, w->map_pos_x, w->map_pos_z, (void*)T->s));
+            if(T->los_chain) RCCHK(navhip_los_chain_refresh(T->los_chain, T->los_flags, (void*)T->s));
         }
         RCCHK(build_fields(T, T->pool[0], T->s));
         if(T->d.dev_moves) RCCHK(navhip_clear_changed(ctx, (void*)T->s));
@@ -287,6 +291,14 @@ int navhip_tick_run(navhip_tick *T, int n)
     T->follows = false;
     T->enqueue_ms += now_ms() - t0;
     return rc;
+}
+
+int navhip_tick_set_los_chain(navhip_tick *T, navhip_los_chain *chain, uint32_t flags)
+{
+    if(!T) return NAVHIP_ERR_INVALID;
+    if(flags & ~(uint32_t)NAVHIP_LOS_REFRESH_DOWNSTREAM) { T->ctx->last_error = "navhip_tick_set_los_chain: unknown flag"; return NAVHIP_ERR_INVALID; }
+    T->los_chain = chain; T->los_flags = flags;
+    return NAVHIP_OK;
 }
 
 int navhip_tick_sync(navhip_tick *T)

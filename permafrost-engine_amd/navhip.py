@@ -533,6 +533,76 @@ def _ctx_build_los_dev(self, d_reqs, n, d_prev, d_out, stream=None):
 NavContext.build_los_dev = _ctx_build_los_dev
 
 
+# ---------------------------------------------------------------------------------------------
+# resident LOS chains (navhip_los_chain_*, csrc/los_chain_api.hip)
+# ---------------------------------------------------------------------------------------------
+LOS_REFRESH_DOWNSTREAM = 1
+
+
+class LosChainStats(C.Structure):
+    """navhip_los_chain_stats, include/navhip.h"""
+    _fields_ = [("slots", C.c_int32), ("levels", C.c_int32), ("stale", C.c_int32), ("rebuilt", C.c_int32),
+                ("redone", C.c_int32)]
+
+
+_SIGS.update({
+    "navhip_los_chain_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float,
+                                          C.POINTER(C.c_void_p)]),
+    "navhip_los_chain_build": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "navhip_los_chain_refresh": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "navhip_los_chain_get_stats": (C.c_int, [C.c_void_p, C.POINTER(LosChainStats)]),
+    "navhip_los_chain_destroy": (None, [C.c_void_p]),
+})
+
+
+class LosChain:
+    """One navhip_los_chain over `d_pool` (a [n][4096] u8 device tensor, the caller's: navhip_world.los_pool).  reqs:
+    LOS_REQ_DTYPE in level order, prev_slot: the slot of every request's predecessor, -1 for a destination chunk."""
+
+    def __init__(self, ctx, reqs, prev_slot, d_pool):
+        reqs = np.ascontiguousarray(reqs, dtype=LOS_REQ_DTYPE)
+        prev_slot = np.ascontiguousarray(prev_slot, dtype=np.int32)
+        assert len(prev_slot) == len(reqs) and int(d_pool.shape[0]) >= len(reqs)
+        self.ctx, self._keep = ctx, d_pool
+        self._h = C.c_void_p()
+        mx, mz = ctx.map_pos()
+        ctx._chk(lib().navhip_los_chain_create(ctx._h, _hp(reqs), _hp(prev_slot), len(reqs), dev_ptr(d_pool), mx, mz,
+                                               C.byref(self._h)), "navhip_los_chain_create")
+
+    def build(self, stream=None):
+        self.ctx._chk(lib().navhip_los_chain_build(self._h, C.c_void_p(stream) if stream else None), "navhip_los_chain_build")
+
+    def refresh(self, flags=0, stream=None):
+        self.ctx._chk(lib().navhip_los_chain_refresh(self._h, flags, C.c_void_p(stream) if stream else None),
+                      "navhip_los_chain_refresh")
+
+    def stats(self):
+        out = LosChainStats()
+        self.ctx._chk(lib().navhip_los_chain_get_stats(self._h, C.byref(out)), "navhip_los_chain_get_stats")
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().navhip_los_chain_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _ctx_los_chain_create(self, reqs, prev_slot, d_pool):
+    return LosChain(self, reqs, prev_slot, d_pool)
+
+
+NavContext.los_chain_create = _ctx_los_chain_create
+NavContext.los_chain_build = lambda self, chain, stream=None: chain.build(stream)
+NavContext.los_chain_refresh = lambda self, chain, flags=0, stream=None: chain.refresh(flags, stream)
+NavContext.los_chain_stats = lambda self, chain: chain.stats()
+
+
 def grid_bounds(chunk_w, chunk_h):
     """bg_ent_init bounds the engine uses (position.c:276-283): the map, centred on the origin."""
     hx, hz = chunk_w * 128.0, chunk_h * 128.0
@@ -1135,6 +1205,7 @@ _SIGS.update({
     "navhip_tick_run": (C.c_int, [C.c_void_p, C.c_int]),
     "navhip_tick_compute": (C.c_int, [C.c_void_p]),
     "navhip_tick_advance": (C.c_int, [C.c_void_p]),
+    "navhip_tick_set_los_chain": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "navhip_tick_sync": (C.c_int, [C.c_void_p]),
     "navhip_tick_get_info": (C.c_int, [C.c_void_p, C.POINTER(TickInfo)]),
     "navhip_tick_destroy": (None, [C.c_void_p]),
@@ -1161,6 +1232,12 @@ class Tick:
 
     def advance(self):
         self.ctx._chk(lib().navhip_tick_advance(self._h), "navhip_tick_advance")
+
+    def set_los_chain(self, chain, flags=0):
+        """The LosChain every tick with a blocker batch refreshes behind it (None: none)."""
+        self._chain = chain
+        self.ctx._chk(lib().navhip_tick_set_los_chain(self._h, chain._h if chain is not None else None, flags),
+                      "navhip_tick_set_los_chain")
 
     def sync(self):
         self.ctx._chk(lib().navhip_tick_sync(self._h), "navhip_tick_sync")

@@ -106,7 +106,7 @@ class NavTick:
                  obstacle_ticks=128, tile_exchange="auto", solo=False, shared_map=False, crowd_cells=0,
                  debug_outputs=False, pipeline_fields=False, exchange="torch", planner_requests=True,
                  straddle=0.0, los=False, flow_velocities=False, share_fields=False, driver="c", serial=None,
-                 time_fields=False):
+                 time_fields=False, los_repair=None):
         self.rank, self.world, self.device_index = rank, world, device
         self.dev = torch.device("cpu") if EMULATED else torch.device("cuda", device)
         tcuda.set_device(self.dev)
@@ -326,6 +326,15 @@ class NavTick:
         # N_LOSFieldCreate chain, from the fixture -- are built on the device (navhip_build_los_dev, level by level
         # along the chain) and every agent's has_dest_los is answered per tick from them (NAVHIP_LOS_LOOKUP:
         # N_HasDestLOS, nav.c:4026).  Built once at start-up like the reference's LOS cache (a static map).
+        # los_repair: what happens to those fields when blockers move.  None = nothing (the fields of the start-up planes
+        # answer for ever); "reference" = behind every blocker batch the fields of the changed chunks are rebuilt, each from
+        # whatever its predecessor holds (the reference's cache: fieldcache.c:526-535, nav.c:2026-2039); "downstream" = and
+        # every field built from a rebuilt one, so that the pool is the one a fresh build on the current planes gives
+        # (navhip_los_chain_*, csrc/los_chain_api.hip)
+        if los_repair not in (None, "reference", "downstream"):
+            raise ValueError("los_repair: None, 'reference' or 'downstream'")
+        self.los_repair = los_repair
+        self.los_chain = None
         self.los_source = "has_dest_los = 0 for every agent (no LOS fields)"
         self.n_los = 0
         if los:
@@ -471,15 +480,8 @@ class NavTick:
         self.los_pool = torch.zeros((n, 4096), dtype=torch.uint8, device=self.dev)
         lv = level[order]
         bounds = np.searchsorted(lv, np.arange(lv.max() + 2))
-        tcuda.synchronize(self.dev)
-        for L in range(len(bounds) - 1):
-            b, e = int(bounds[L]), int(bounds[L + 1])
-            if e == b:
-                continue
-            d_prev = self.los_pool.index_select(0, d_prev_slot[b:e]) if L > 0 else None
-            tcuda.synchronize(self.dev)     # (torch's stream -> the library's: start-up, untimed)
-            self.ctx.build_los_dev(d_reqs[b:e], e - b, d_prev, self.los_pool[b:e])
-            self.ctx.sync()
+        self._los_build_args = (d_reqs, d_prev_slot, bounds)
+        self._build_los_pool(self.los_pool)
         tbl = -np.ones((self.K, self.nchunks), np.int32)
         tbl[lc["dest"], lc["chunk_r"] * Wt + lc["chunk_c"]] = slot_of
         self.t["los_pool"] = self.los_pool
@@ -490,6 +492,33 @@ class NavTick:
         self.n_los = n
         self.los_source = ("device lookup (NAVHIP_LOS_LOOKUP) in %d LOS fields built by navhip_build_los from the "
                            "reference planner's N_LOSFieldCreate chain (fixture), %d levels" % (n, len(bounds) - 1))
+        if self.los_repair is not None:
+            chain_prev = np.where(prev_i[order] >= 0, prev_slot, -1).astype(np.int32)
+            self.los_chain = self.ctx.los_chain_create(reqs, chain_prev, self.los_pool)
+            self.los_flags = navhip.LOS_REFRESH_DOWNSTREAM if self.los_repair == "downstream" else 0
+            self.los_source += ("; kept current behind every blocker batch by navhip_los_chain_refresh (%s)"
+                                % ("the changed chunks' fields and every field built from them" if self.los_flags else
+                                   "the changed chunks' fields only, as the reference's cache"))
+        else:
+            self.los_source += "; never rebuilt (los_repair=None)"
+
+    def _build_los_pool(self, pool):
+        """Every LOS field of the chain into `pool` from the planes as they are now: one navhip_build_los_dev per level,
+        the predecessors gathered from the level before."""
+        d_reqs, d_prev_slot, bounds = self._los_build_args
+        tcuda.synchronize(self.dev)
+        for L in range(len(bounds) - 1):
+            b, e = int(bounds[L]), int(bounds[L + 1])
+            if e == b:
+                continue
+            d_prev = pool.index_select(0, d_prev_slot[b:e]) if L > 0 else None
+            tcuda.synchronize(self.dev)     # (torch's stream -> the library's: start-up, untimed)
+            self.ctx.build_los_dev(d_reqs[b:e], e - b, d_prev, pool[b:e])
+            self.ctx.sync()
+
+    def _los_refresh(self, stream):
+        # (one place for the Python schedule's refresh: tests put a full build here to hold the refresh against)
+        self.los_chain.refresh(self.los_flags, stream=stream)
 
     def _flow_aligned_velocities(self):
         """initial velocity = 0.5 max along the sampled flow direction + N(0, 0.1).  The
@@ -577,6 +606,8 @@ class NavTick:
         d.flags = ((navhip.TICK_SERIAL if self.serial else 0) | (navhip.TICK_TIME_FIELDS if self.time_fields else 0)
                    | navhip.TICK_OWNS_SNAPSHOT)
         self._ctick = navhip.Tick(self.ctx, d, keep)
+        if self.los_chain is not None:
+            self._ctick.set_los_chain(self.los_chain, self.los_flags)
         self._ctick_tick0 = self.tick_no
         self.tick_driver = "c (navhip_tick_run%s)" % (", one stream" if self.serial else "")
         return self._ctick
@@ -657,6 +688,8 @@ class NavTick:
                 marks.append(self._mark("blockers"))
                 t = self.tick_no % self.d_moves.shape[0]
                 self.ctx.blockers_circles_dev(self.d_moves[t], self.n_moves, stream=s.cuda_stream)
+                if self.los_chain is not None:
+                    self._los_refresh(s.cuda_stream)
             marks.append(self._mark("fields"))
             if self.n_req_local:
                 self.ctx.build_fields_dev(self.d_reqs[self.req_begin:self.req_end], self.n_req_local,
@@ -803,4 +836,7 @@ class NavTick:
             self.c_tick_info = self._ctick.info()
             self._ctick.close()
             self._ctick = None
+        if self.los_chain is not None:
+            self.los_chain.close()
+            self.los_chain = None
         self.ctx.close()
