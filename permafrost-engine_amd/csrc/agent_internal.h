@@ -1,4 +1,5 @@
-// agent_internal.h -- launch interface of agent_kernels.hip (used by step_api.hip, state_kernels.hip).
+// agent_internal.h -- launch interface of the agent step's kernel units: spatial_kernels.hip, cohesion_kernels.hip,
+// agent_kernels.hip (used by step_api.hip and, for the types, state_kernels.hip).
 #pragma once
 #define NH_SCAN_T 256      /* threads (= cells) per block of the two-pass scans */
 #include "navhip_internal.h"
@@ -18,24 +19,31 @@ struct nh_spatial_scratch {
     nh_pack_src src;
 };
 
+// ---- spatial_kernels.hip: the build side of the spatial hash
 // fills G.cell_start / recA / recV / pool_of from S
 void nh_launch_spatial_build(nh_grid &G, const float *d_pos_xz, nh_spatial_scratch &S,
                              int slab_begin, int slab_end, hipStream_t s);
-void nh_launch_agent_nbr(const nh_step_params &P, const nh_nbr &NB, hipStream_t s);
+// exclusive scan count[0..n) -> start[0..n], two launches over blocks of NH_SCAN_T (block_sum: one entry per block);
+// box (or null): the slab filter over G's rows of cells; zero_counts (or null): cleared once consumed
+void nh_launch_scan(const int32_t *count, int32_t *start, int32_t *block_sum, int n, int32_t *zero_counts,
+                    const nh_grid &G, const int32_t *box, hipStream_t s);
+
+// ---- cohesion_kernels.hip: the cohesion term
 size_t nh_cohesion_scratch_bytes(int n_flocks, int n_members);
 hipError_t nh_cohesion_scratch_reset(int32_t *scratch, int n_flocks, int n_members, hipStream_t s);
 // returns true when the lane regrouping for the next tick is still to be launched
 // (nh_launch_cohesion_regroup, after the caller's "cohesion done" event)
 bool nh_launch_cohesion(const nh_step_params &P, int32_t *scratch, float *d_coh, int *parity, hipStream_t s);
 void nh_launch_cohesion_regroup(const nh_step_params &P, int32_t *scratch, int *parity, hipStream_t s);
-// k_agent_mid -> k_cp_rows -> k_agent_full | k_cp_small -> retry -> k_cp_heavy; WL.count holds 2 * NH_WL_COUNTERS counters.
-// side / ev (or null): a second stream for the second chain, two events
+
+// ---- agent_kernels.hip: the step proper and the test utilities
+void nh_launch_agent_nbr(const nh_step_params &P, const nh_nbr &NB, hipStream_t s);
 int nh_worklist_cap(int n_work);
+// k_agent_mid -> k_cp_rows -> k_agent_full | k_cp_small -> retry -> k_cp_heavy; WL.count holds 2 * NH_WL_COUNTERS counters.
+// side (or null): a second stream for the second chain, handed over through ctx's device-side signals; *forked: it was used
 bool nh_launch_agent_finish(const nh_step_params &P, const nh_nbr &NB, float *d_coh, nh_mid_rec *d_mid,
                             nh_worklists WL, int parity, const nh_step_outs &O, hipStream_t s,
                             hipStream_t side, navhip_ctx *ctx, bool *forked);
-void nh_launch_state_update(const nh_step_params &P, const navhip_state_in &in, float4 *d_arrived, int32_t *d_arrived_n, uint8_t *d_state, uint8_t *d_flags,
-                            hipStream_t s);
 void nh_launch_region_lookup(const nh_step_params &P, int nq, const float *d_pos, const int32_t *d_rows,
                              const int32_t *d_centre_abs, const int32_t *d_radius, uint8_t *d_dir, uint8_t *d_at_slot,
                              hipStream_t s);

@@ -14,16 +14,11 @@
 // Arithmetic mirrors the reference's C expression by expression (agent_math.h); all
 // order-dependent float sums are evaluated in the reference's own order.
 //
-// Kernels of one tick (step_api.hip wires the streams):
-//   k_sp_count .. k_sp_place   device spatial hash: fixed-point cell binning, scan, and the POOL -- one
-//                 16-byte record {pos, radius, flag bits | uid} + one velocity per inserted entity, in
-//                 the cell order and per-cell order bg_ent_cleanup produces after inserting uids
-//                 0..n-1, so that a query's candidates are contiguous runs and a hit needs no
-//                 second gather.
+// Kernels of one tick (step_api.hip wires the streams; the spatial hash is built by spatial_kernels.hip, the
+// cohesion term comes from cohesion_kernels.hip):
 //   k_agent_nbr   one ROW of 16 lanes per entity, pool order: separation force + ClearPath neighbour
 //                 lists in one walk (agent_group.h).  Needs only the snapshot: runs beside the field
 //                 builds.
-//   k_cohesion    the O(N*F) exp-weighted flock centroid, four lanes per member.
 //   k_agent_mid   one THREAD per entity: the scalar chain -- flow sampling, arrive force, priority
 //                 ladder -> preferred velocity.  Agents without ClearPath neighbours are truncated +
 //                 position-tested here; the rest go to device-side work lists by neighbour count.
@@ -37,221 +32,16 @@
 //                 caller's stream, the rest beside them on a side stream.
 //   k_agent_full  one WAVE per listed agent, the whole step (irregular gathers: garrisoned
 //                 neighbours, wide queries).
+// Test utilities: k_spatial_query (the wave query on its own), k_region_lookup (sample_region in batches),
+// k_clearpath<> / k_clearpath_team (the search on given neighbour lists), navhip_debug_cp_attempts.
+//
+// The ONE unit of the library that includes agent_group.h (it defines the device variable nh_cp_attempts).
 #include "navhip_internal.h"
 #include "agent_internal.h"
 #include "agent_group.h"
 
-__constant__ double c_exp2_64[64] = { NH_EXP2_64_TABLE };
-
-// ---------------------------------------------------------------------------------------------
-// spatial hash (bitmap_grid.h): build
-// ---------------------------------------------------------------------------------------------
-#define SP_MAX_QUERY_R 30   /* largest query radius of the movement tick (separation, movement.c:1695) */
-// Optional slab filter: when a rank steps only the entities [work_begin, work_end), nothing farther
-// than the largest query radius of the tick (r = 30) from the bounding box of THOSE entities can be
-// returned by any of its queries, and leaving such entities out changes neither the order nor the
-// caps of what is returned.  box = {max(-ix), max(ix), max(-iy), max(iy)} over the slab in the
-// x256 fixed point the queries compare in; INT_MIN-initialised.
-// (Four-wave workgroups: a 1024-thread block waits for sixteen free wave slots on one CU -- 26 us beside the
-// field builds, in front of the whole spatial hash.  Two boxes alternate between builds: the build that
-// consumes box[p] (k_sp_count) re-initialises box[p ^ 1] for its successor, so there is no memset.)
-__global__ __launch_bounds__(256) void k_sp_bbox(const float *pos_xz, int begin, int end, int32_t *box)
-{
-    __shared__ int32_t part[4][4];
-    int32_t v[4] = {INT32_MIN, INT32_MIN, INT32_MIN, INT32_MIN};
-    for(int i = begin + blockIdx.x * 256 + threadIdx.x; i < end; i += gridDim.x * 256) {
-        const int32_t ix = bg_scale(pos_xz[2 * i]), iy = bg_scale(pos_xz[2 * i + 1]);
-        v[0] = max(v[0], -ix); v[1] = max(v[1], ix); v[2] = max(v[2], -iy); v[3] = max(v[3], iy);
-    }
-#pragma unroll
-    for(int q = 0; q < 4; q++) {
-#pragma unroll
-        for(int d = 32; d >= 1; d >>= 1) v[q] = max(v[q], __shfl_xor(v[q], d));
-        if((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][q] = v[q];
-    }
-    __syncthreads();
-    if(threadIdx.x < 4) {
-        int32_t m = INT32_MIN;
-        for(int w = 0; w < 4; w++) m = max(m, part[w][threadIdx.x]);
-        if(m != INT32_MIN) atomicMax(&box[threadIdx.x], m);
-    }
-}
-
-__device__ __forceinline__ bool sp_in_box(const int32_t *box, int32_t ix, int32_t iy)
-{
-    if(!box) return true;
-    const int32_t m = SP_MAX_QUERY_R * 256 + 256;     // BG_SCALE_F(largest radius) + 1 wu of slack
-    // (int64: the INT_MIN box of an empty slab must reject everything without overflowing)
-    return (int64_t)ix >= -(int64_t)box[0] - m && (int64_t)ix <= (int64_t)box[1] + m
-        && (int64_t)iy >= -(int64_t)box[2] - m && (int64_t)iy <= (int64_t)box[3] + m;
-}
-// Pass 1: cell of every entity + its arrival rank in the cell (the counters are zero on entry:
-// cleared at allocation, then by k_sp_scan_add of the previous build).
-__global__ __launch_bounds__(256) void k_sp_count(nh_grid G, const float *pos_xz, int n,
-                                                  int32_t *ent_cell, int32_t *ent_rank,
-                                                  int32_t *cell_count, const int32_t *box, int32_t *box_next,
-                                                  int32_t *n_active)
-{
-    int i = blockIdx.x * 256 + threadIdx.x;
-    if(box_next && i < 4) box_next[i] = INT32_MIN;           // (the box of the NEXT build)
-    if(n_active && i == 0) *n_active = 0;                    // (the list k_sp_place fills: its reader, the last walk, is through)
-    if(i >= n) return;
-    const int32_t ix = bg_scale(pos_xz[2 * i]), iy = bg_scale(pos_xz[2 * i + 1]);
-    if(!sp_in_box(box, ix, iy)) { ent_cell[i] = -1; return; }
-    const int c = sp_cell_of(G, ix, iy);
-    ent_cell[i] = c;
-    ent_rank[i] = atomicAdd(&cell_count[c], 1);
-}
-
-// A rank that steps a slab only fills the cells its box (+ the query reach) covers; every other cell is
-// empty and is never looked at by a query of the slab either.  The scans skip the blocks of cells that lie
-// entirely in grid rows outside the box: their block sum is 0 and their cell_start entries stay unwritten.
-// (rows [r0, r1] of the box in cells; a block is a run of NH_SCAN_T consecutive cells, row-major)
-__device__ __forceinline__ bool sp_block_outside_box(const nh_grid &G, const int32_t *box, int first_cell, int ncells)
-{
-    if(!box) return false;
-    const int32_t m = SP_MAX_QUERY_R * 256 + 256;
-    const int64_t y0 = -(int64_t)box[2] - m, y1 = (int64_t)box[3] + m;          // fixed-point rows of the box
-    if(y1 < y0) return true;                                                     // empty slab: nothing is inserted
-    // cell rows (clamped like sp_cell_of clamps an element into the grid)
-    const int64_t r0 = min(max((y0 - G.origin_y) >> 12, (int64_t)0), (int64_t)G.grid_h - 1);
-    const int64_t r1 = min(max((y1 - G.origin_y) >> 12, (int64_t)0), (int64_t)G.grid_h - 1);
-    const int last_cell = min(first_cell + NH_SCAN_T, ncells) - 1;
-    // (one row more at the end: a query reads cell_start one past its last cell -- the first cell of the
-    // row after r1)
-    return last_cell < r0 * G.grid_w || first_cell >= (r1 + 2) * G.grid_w;
-}
-
-// exclusive scan of cell_count[0..ncells) -> cell_start[0..ncells], two passes over NH_SCAN_T-cell
-// blocks: (1) block-local exclusive scan + block totals, (2) add the sum of the preceding totals.
-// (Blocks of four waves: a 1024-thread block needs sixteen free wave slots on ONE compute unit at the
-// same moment, and beside the cohesion kernel's stream of one-wave blocks it waited for them for
-// 50 us -- on the critical path of the tick.)
-__global__ __launch_bounds__(NH_SCAN_T) void k_sp_scan_local(const int32_t *cell_count, int32_t *cell_start,
-                                                             int32_t *block_sum, int ncells,
-                                                             nh_grid G, const int32_t *box)
-{
-    __shared__ int32_t wsum[NH_SCAN_T / 64];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    if(sp_block_outside_box(G, box, blockIdx.x * NH_SCAN_T, ncells)) {
-        if(t == 0) block_sum[blockIdx.x] = 0;
-        return;
-    }
-    const int i = blockIdx.x * NH_SCAN_T + t;
-    int32_t v = (i < ncells) ? cell_count[i] : 0;
-    int32_t incl = v;
-#pragma unroll
-    for(int d = 1; d < 64; d <<= 1) {
-        int32_t o = __shfl_up(incl, d);
-        if(lane >= d) incl += o;
-    }
-    if(lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int32_t woff = 0, tot = 0;
-#pragma unroll
-    for(int k = 0; k < NH_SCAN_T / 64; k++) {
-        int32_t x = wsum[k];
-        if(k < w) woff += x;
-        tot += x;
-    }
-    if(i < ncells) cell_start[i] = woff + incl - v;
-    if(t == 0) block_sum[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(NH_SCAN_T) void k_sp_scan_add(int32_t *cell_start, const int32_t *block_sum,
-                                                           int ncells, int nblocks, int32_t *zero_counts,
-                                                           nh_grid G, const int32_t *box)
-{
-    __shared__ int32_t wsum[NH_SCAN_T / 64];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    // (the last block always runs: it writes the grand total, cell_start[ncells])
-    if((int)blockIdx.x != nblocks - 1 && sp_block_outside_box(G, box, blockIdx.x * NH_SCAN_T, ncells)) return;
-    // sum of the totals of the blocks before this one (and, in the last block, of all blocks)
-    int32_t part = 0, all = 0;
-    for(int k = t; k < nblocks; k += NH_SCAN_T) {
-        int32_t x = block_sum[k];
-        all += x;
-        if(k < (int)blockIdx.x) part += x;
-    }
-    const bool last = (int)blockIdx.x == nblocks - 1;
-    int32_t red = last ? all : part;          // the last block needs both: two reductions
-#pragma unroll
-    for(int d = 32; d >= 1; d >>= 1) { red += __shfl_xor(red, d); part += __shfl_xor(part, d); }
-    if(lane == 0) wsum[w] = red;
-    __syncthreads();
-    int32_t tot = 0;
-#pragma unroll
-    for(int k = 0; k < NH_SCAN_T / 64; k++) tot += wsum[k];
-    __syncthreads();
-    if(lane == 0) wsum[w] = part;
-    __syncthreads();
-    int32_t off = 0;
-#pragma unroll
-    for(int k = 0; k < NH_SCAN_T / 64; k++) off += wsum[k];
-    const int i = blockIdx.x * NH_SCAN_T + t;
-    if(i < ncells) cell_start[i] += off;
-    if(zero_counts && i < ncells) zero_counts[i] = 0;     // consumed by k_sp_scan_local: clean for the next build
-    if(last && t == 0) cell_start[ncells] = tot;
-}
-// Pass 3: entities into their cell's range in arrival order (no atomics: the rank is known)
-__global__ __launch_bounds__(256) void k_sp_scatter(const int32_t *ent_cell, const int32_t *ent_rank, int n,
-                                                    const int32_t *cell_start, int32_t *tmp_id)
-{
-    int i = blockIdx.x * 256 + threadIdx.x;
-    if(i >= n) return;
-    const int c = ent_cell[i];
-    if(c < 0) return;                            // outside the slab filter
-    tmp_id[cell_start[c] + ent_rank[i]] = i;
-}
-
-// Pass 4: per-cell order + the pool records.  bg_ent_insert pushes at the head of the cell's
-// overflow chain and bg_ent_cleanup copies the chain head-first (bitmap_grid.h:1102-1121,
-// 1515-1521), so after inserting uids 0..n-1 each cell holds its elements in DESCENDING uid order:
-// the final slot of an element is its cell's start + the number of cell mates with a larger uid
-// (one thread per element counts them: cells hold a handful of elements).
-#define SP_BLOCK 64
-__global__ __launch_bounds__(SP_BLOCK) void k_sp_place(nh_grid G, const float *pos_xz, nh_pack_src src,
-                                                  const int32_t *ent_cell, const int32_t *tmp_id,
-                                                  int n, int work_begin, int work_end,
-                                                  float4 *recA, float2 *recV, int32_t *pool_of,
-                                                  int32_t *active, int32_t *n_active)
-{
-    // one thread per ENTITY (not per pool slot): its inputs are coalesced loads that do not wait for the
-    // slot search, the only gathers are the cell's bounds and its handful of ids, and the record goes out
-    // as a scattered store.  (Per slot the kernel was a chain of five dependent gathers -- id, cell, bounds,
-    // cell mates, the entity's six attribute arrays -- and took 60 us beside the cohesion kernel.)
-    const int i = blockIdx.x * SP_BLOCK + threadIdx.x;
-    const int c = i < n ? ent_cell[i] : -1;      // (-1: outside the slab filter)
-    int slot = -1;
-    bool walks = false;
-    if(c >= 0) {
-        float4 a;
-        float2 v;
-        pool_record(i, pos_xz, src, work_begin, work_end, a, v);
-        const int b = G.cell_start[c], e = G.cell_start[c + 1];
-        int larger = 0;
-        for(int q = b; q < e; q++) larger += tmp_id[q] > i;
-        slot = b + larger;
-        recA[slot] = a;
-        recV[slot] = v;
-        pool_of[i] = slot;
-        walks = !(__float_as_uint(a.w) & NH_PB_IDLE);
-    }
-    // A rank that steps a slab: the pool slots whose entity has a work item, as a LIST (any order), so that the neighbour
-    // walk runs one row per listed slot instead of striding rows over a pool of which seven eighths are idle -- a row
-    // then walked up to six entities one after the other and the launch took as long for an eighth of the entities as
-    // for all of them (38 against 47 us).  One atomic per wave (the slab is a contiguous uid range: few waves have any).
-    if(active) {
-        const unsigned long long m = __ballot(walks);
-        if(m) {
-            const int lane = threadIdx.x & 63, leader = __ffsll((long long)m) - 1;
-            int base = 0;
-            if(lane == leader) base = atomicAdd(n_active, __popcll(m));
-            base = __shfl(base, leader);
-            if(walks) active[base + __popcll(m & ((1ull << lane) - 1ull))] = slot;
-        }
-    }
-}
+// (this code object's own copy of the table: the library is built without relocatable device code)
+static __constant__ double c_exp2_64[64] = { NH_EXP2_64_TABLE };
 
 // ---------------------------------------------------------------------------------------------
 // spatial hash: query.  All 64 lanes cooperate on ONE query; returns the number written (wave
@@ -261,99 +51,9 @@ __global__ __launch_bounds__(SP_BLOCK) void k_sp_place(nh_grid G, const float *p
 // one contiguous range that the lanes test 64 elements at a time; ballot + prefix popcount
 // appends hits in order and enforces `maxout` exactly where the reference stops.
 // The hits are POOL SLOTS (uid = recA[slot].w >> 8).
+// (No query of the movement tick reaches farther than r = 30: the slab filter of the build, SP_MAX_QUERY_R in
+// spatial_kernels.hip, leaves out what lies beyond that -- a wider query in the tick has to raise that bound.)
 // ---------------------------------------------------------------------------------------------
-// inclusive prefix sum over the 64 lanes: four row_shr steps inside each row of 16, then the two
-// row broadcasts (DPP; zero fill outside the row)
-__device__ __forceinline__ int wave_incl_scan(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);    // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);    // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);    // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);    // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1, 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2, 3
-    return v;
-}
-
-// The whole build for a SMALL world in one workgroup: counts, scan, arrival order and placement out of LDS between
-// barriers instead of five dependent launches.  The front of the step is a chain of launches of ~5 us each whatever
-// they do; for a thousand entities that chain IS the front (31 us of a 97-us tick at configs[0]), and with the step's
-// hand-overs at 2-3 us and the cohesion term enqueued first nothing else is in front of k_agent_mid any more.  (Round 6
-// built this once before the hand-overs changed and removed it: the tick was bound by its events and the host then,
-// profiles/r06_ab_small_world_hash_rejected.txt.)  Same results: the order inside a cell is fixed by the uids, not by
-// who arrives first.  Leaves the global counters untouched (they stay zero for the next large build).
-#define SP_SMALL_N     1024       /* entities */
-#define SP_SMALL_CELLS 8192       /* cells */
-#define SP_SMALL_T     256
-__global__ __launch_bounds__(SP_SMALL_T) void k_sp_build_small(nh_grid G, const float *pos_xz, nh_pack_src src, int n, int ncells,
-                                                            int work_begin, int work_end, int32_t *cell_start, float4 *recA, float2 *recV, int32_t *pool_of)
-{
-    __shared__ int32_t  start[SP_SMALL_CELLS + 1];          // counts, then the exclusive scan
-    __shared__ uint16_t ecell[SP_SMALL_N], erank[SP_SMALL_N], order[SP_SMALL_N];
-    __shared__ int32_t  wsum[SP_SMALL_T / 64];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    for(int c = t; c <= ncells; c += SP_SMALL_T) start[c] = 0;
-    __syncthreads();
-    for(int i = t; i < n; i += SP_SMALL_T) {
-        const int c = sp_cell_of(G, bg_scale(pos_xz[2 * i]), bg_scale(pos_xz[2 * i + 1]));
-        ecell[i] = (uint16_t)c;
-        erank[i] = (uint16_t)atomicAdd(&start[c], 1);
-    }
-    __syncthreads();
-    // exclusive scan, SP_SMALL_T cells at a time with a running carry
-    int32_t carry = 0;
-    for(int base = 0; base < ncells; base += SP_SMALL_T) {
-        const int c = base + t;
-        const int32_t v = c < ncells ? start[c] : 0;
-        const int32_t incl = wave_incl_scan(v);
-        if(lane == 63) wsum[w] = incl;
-        __syncthreads();
-        int32_t woff = 0, tot = 0;
-#pragma unroll
-        for(int k = 0; k < SP_SMALL_T / 64; k++) { const int32_t x = wsum[k]; if(k < w) woff += x; tot += x; }
-        if(c < ncells) { start[c] = carry + woff + incl - v; cell_start[c] = carry + woff + incl - v; }
-        carry += tot;
-        __syncthreads();
-    }
-    if(t == 0) { start[ncells] = carry; cell_start[ncells] = carry; }
-    __syncthreads();
-    for(int i = t; i < n; i += SP_SMALL_T) order[start[ecell[i]] + erank[i]] = (uint16_t)i;
-    __syncthreads();
-    // descending uid inside a cell (k_sp_place)
-    for(int i = t; i < n; i += SP_SMALL_T) {
-        float4 a;
-        float2 v;
-        pool_record(i, pos_xz, src, work_begin, work_end, a, v);
-        const int c = ecell[i], b = start[c], e = start[c + 1];
-        int larger = 0;
-        for(int q = b; q < e; q++) larger += order[q] > i;
-        recA[b + larger] = a;
-        recV[b + larger] = v;
-        pool_of[i] = b + larger;
-    }
-}
-
-// Running totals of the work units of a kernel's sub-lists, by the first wave of the workgroup: entry k
-// holds `cnt[k]` agents = (cnt[k] + per - 1) / per units; unit_end[k] = units of the entries up to and
-// including k.  (One thread adding up 128-256 entries in front of every workgroup's first barrier was 770-1 500
-// wave instructions per workgroup: a fifth of everything k_cp_small executed.)
-template <typename F>
-__device__ __forceinline__ void unit_totals(int32_t *unit_end, int ntab, F units_of)
-{
-    if(threadIdx.x >= 64) return;
-    const int lane = threadIdx.x, per_lane = (ntab + 63) >> 6;        // consecutive entries per lane
-    int local = 0;
-    for(int j = 0; j < per_lane; j++) {
-        const int k = lane * per_lane + j;
-        if(k < ntab) local += units_of(k);
-    }
-    int run = wave_incl_scan(local) - local;
-    for(int j = 0; j < per_lane; j++) {
-        const int k = lane * per_lane + j;
-        if(k < ntab) { run += units_of(k); unit_end[k] = run; }
-    }
-}
-
 // out_d2 (optional, [maxout]): squared fixed-point distance of every hit (fits int32 for the
 // ranges the movement tick uses), so that a narrower query around the same point can be derived
 // from this one without touching memory again.
@@ -496,421 +196,6 @@ __device__ int filter_garrisoned_wave(const nh_grid &G, uint32_t *ids, int count
 }
 
 // ---------------------------------------------------------------------------------------------
-// cohesion_force (movement.c:1653)
-// ---------------------------------------------------------------------------------------------
-// (cohesion_t_f32 / cohesion_t_f64 -- float t = (len - 50.0f*0.75) / 50.0f of movement.c:1668 -- live in agent_math.h)
-
-#define COH_BINS 257       /* 256 Morton blocks + 1 bin for members that take no cohesion force */
-// k_coh_plan: wave_off[f] = number of 16-member (COH_APW) waves of the flocks before f (exclusive
-// scan); one workgroup, chunked.  The launch uses the lane grouping the PREVIOUS regrouping left behind
-// (k_coh_bin .. k_coh_scatter: perm[] + its bin prefix bin_start[]) when that was built for exactly these
-// flock offsets and this work range (saved[]: offsets, then work_begin, work_end) -- flock f then gets
-// ceil(members of f inside the work range / 16) waves -- and otherwise (*perm_valid = 0: first tick, flocks
-// or slab changed) the identity over whole flocks: ceil(flock size / 16) waves.
-__global__ __launch_bounds__(256) void k_coh_plan(const int32_t *bin_start, const int32_t *flock_offsets,
-                                                  const int32_t *saved, int n_flocks, int work_begin, int work_end,
-                                                  int members_key, int32_t *wave_off, int32_t *perm_valid)
-{
-    __shared__ int32_t wsum[4];
-    __shared__ int32_t carry;
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    if(t == 0) carry = 0;
-    bool same = saved[n_flocks + 1] == work_begin && saved[n_flocks + 2] == work_end && saved[n_flocks + 3] == members_key;
-    for(int f = t; f <= n_flocks; f += 256) same = same && saved[f] == flock_offsets[f];
-    const int valid = __syncthreads_and(same);
-    for(int base = 0; base < n_flocks; base += 256) {
-        const int f = base + t;
-        int32_t v = 0;
-        if(f < n_flocks) {
-            const int32_t cnt = valid ? bin_start[(f + 1) * COH_BINS] - bin_start[f * COH_BINS]
-                                      : flock_offsets[f + 1] - flock_offsets[f];
-            v = (cnt + 15) >> 4;                                                       // COH_APW
-        }
-        int32_t incl = v;
-#pragma unroll
-        for(int d = 1; d < 64; d <<= 1) {
-            int32_t o = __shfl_up(incl, d);
-            if(lane >= d) incl += o;
-        }
-        if(lane == 63) wsum[w] = incl;
-        __syncthreads();
-        int32_t woff = 0;
-        for(int k = 0; k < w; k++) woff += wsum[k];
-        const int32_t excl = carry + woff + incl - v;
-        if(f < n_flocks) wave_off[f] = excl;
-        __syncthreads();
-        if(t == 255) carry = excl + v;
-        __syncthreads();
-    }
-    if(t == 0) { wave_off[n_flocks] = carry; *perm_valid = valid; }
-}
-
-// k_coh_bin / k_coh_scatter: per-tick lane assignment of the cohesion launch.  Which thread handles
-// which member is free (each member's sum only depends on the flock's member ORDER, which the walk
-// keeps), so the members of a flock are regrouped by 256-wu map blocks (16x16) in Morton order:
-// the 64 members of a wave are then close together and the wave can skip, exactly, every flock
-// mate that is too far from ALL of them to carry a non-zero weight (see k_cohesion).
-//   bin = flock * COH_BINS + morton(block);   perm[] = CSR entries ordered by bin (counting sort;
-//   the order inside a bin is whatever the atomics give -- it only moves members between lanes).
-// Members that take no cohesion force this tick (outside the work range, not point seeking, combat
-// hold) go to the flock's last bin: the lanes in use are packed at the front and the trailing waves
-// of a flock exit at once.
-__device__ __forceinline__ int coh_bin_of(const nh_step_params &P, int g, int *flock_out)
-{
-    int lo = 0, hi = P.n_flocks;
-    while(hi - lo > 1) {
-        int mid = (lo + hi) >> 1;
-        if(P.flock_offsets[mid] <= g) lo = mid; else hi = mid;
-    }
-    *flock_out = lo;
-    const int m = P.flock_members[g];
-    const bool act = m >= P.work_begin && m < P.work_end && state_uses_point_seek(P.state[m])
-                  && !(P.flags[m] & NAVHIP_ENTITY_FLAG_COMBAT_HELD);
-    if(!act) return lo * COH_BINS + 256;
-    const float ox = (float)P.grid.origin_x * (1.0f / 256.0f), oz = (float)P.grid.origin_y * (1.0f / 256.0f);
-    // 256-wu blocks, 16 x 16 of them before the pattern repeats (a flock spread over more than
-    // 4096 wu merely shares bins: the grouping is a locality heuristic, never a correctness matter)
-    const int bx = (int)floorf((P.pos_xz[2 * m] - ox) * (1.0f / 256.0f)) & 15;
-    const int bz = (int)floorf((P.pos_xz[2 * m + 1] - oz) * (1.0f / 256.0f)) & 15;
-    int mo = 0;
-#pragma unroll
-    for(int k = 0; k < 4; k++) mo |= (((bx >> k) & 1) << (2 * k)) | (((bz >> k) & 1) << (2 * k + 1));
-    return lo * COH_BINS + mo;
-}
-
-// (The idle members of a flock all share one bin: on a rank that steps one slab of a large job that
-// is most members, and one atomic per member on the same address serialises -- 110 us for 800 k
-// members.  Lanes of a wave that hit the same idle bin are counted by ONE atomic of the first of
-// them; active members are spread over 256 bins and use plain atomics.)
-__device__ __forceinline__ int coh_grouped_add(int32_t *counter, int bin, bool idle)
-{
-    const int lane = threadIdx.x & 63;
-    int slot = 0;
-    unsigned long long rem = __ballot(idle);
-    while(rem) {
-        const int leader = __ffsll((long long)rem) - 1;
-        const int b0 = __shfl(bin, leader);
-        const unsigned long long m = __ballot(idle && bin == b0);
-        int base = 0;
-        if(lane == leader) base = atomicAdd(&counter[b0], __popcll(m));
-        base = __shfl(base, leader);
-        if(idle && bin == b0) slot = base + __popcll(m & ((1ull << lane) - 1ull));
-        rem &= ~m;
-    }
-    if(!idle) slot = atomicAdd(&counter[bin], 1);
-    return slot;
-}
-
-// Members outside the work range [work_begin, work_end) -- on a rank that steps one slab of a large job
-// that is most of the snapshot -- leave before the flock search and get no lane at all (bin_of = -1): the
-// grouping holds the members INSIDE the range, flock by flock, active bins first.  saved[]: what the
-// grouping was built for: flock offsets, the work range, and the MEMBERSHIP KEY.  A member outside the range
-// has no lane, so a grouping made for a slab is only valid while flock_members is unchanged: equal offsets and
-// bounds do not show that (two units swap flocks of equal size; an entity removed elsewhere shifts a uid across
-// the slab boundary), and the unit that moved into the slab would keep another entity's stale force.  The key
-// is 0 for a step over the whole snapshot (every member has a lane, a change is harmless), the caller's
-// navhip_world.static_epoch for a slab step, and a number that never repeats when the caller gave none.
-__global__ __launch_bounds__(256) void k_coh_bin(nh_step_params P, int32_t *bin_of, int32_t *bin_count,
-                                                 int32_t *saved)
-{
-    const int g = blockIdx.x * 256 + threadIdx.x;
-    for(int f = g; f <= P.n_flocks; f += gridDim.x * 256) saved[f] = P.flock_offsets[f];
-    if(g == 0) { saved[P.n_flocks + 1] = P.work_begin; saved[P.n_flocks + 2] = P.work_end; saved[P.n_flocks + 3] = P.members_key; }
-    if(g >= P.flock_offsets[P.n_flocks]) return;
-    const int m = P.flock_members[g];
-    if(m < P.work_begin || m >= P.work_end) { bin_of[g] = -1; return; }
-    int f;
-    const int bin = coh_bin_of(P, g, &f);
-    bin_of[g] = bin;
-    coh_grouped_add(bin_count, bin, bin - f * COH_BINS == 256);
-}
-
-__global__ __launch_bounds__(256) void k_coh_scatter(nh_step_params P, const int32_t *bin_of,
-                                                     const int32_t *bin_start, int32_t *bin_fill,
-                                                     int32_t *perm)
-{
-    const int g = blockIdx.x * 256 + threadIdx.x;
-    if(g >= P.flock_offsets[P.n_flocks]) return;
-    const int bin = bin_of[g];
-    if(bin < 0) return;                                   // (outside the work range: no lane)
-    perm[bin_start[bin] + coh_grouped_add(bin_fill, bin, bin % COH_BINS == 256)] = g;
-}
-
-// exp(-6 t) rounds to +0 in float once the distance exceeds 904 wu (t >= 17.33); COH_FAR leaves a
-// margin for the roundings of the box test
-#define COH_FAR 906.0f
-
-// k_cohesion: one WAVE (= one 64-thread workgroup) per COH_APW = 16 members of ONE flock (perm[]
-// order); FOUR lanes share a member (lane = member << 2 | sub).  A wave never straddles two flocks.
-//
-// The flock's member positions are staged through LDS 256 at a time (coalesced gather); a
-// lane-parallel pre-pass drops the staged members that lie more than COH_FAR from the bounding box
-// of the wave's own members (their weight is exactly 0 for every lane, and adding +-0 leaves the
-// never-negative-zero running sums unchanged) and queues the survivors IN MEMBER ORDER.  Queue entry
-// k belongs to sub-lane k & 3: each lane evaluates the expensive part (distance -> t -> exp, ~36
-// instructions per entry) for a quarter of the entries only, eight at a time, two per packed f32
-// instruction.  The float sums are order dependent, so the products are then added strictly in
-// entry order: the sub-lane that owns entry k broadcasts its product to the quad (DPP quad_perm as
-// an operand of the add) and all four lanes keep the same running sum.
-//
-// Why four lanes per member: with one lane per member the launch was 1 600 long waves on 1 024 SIMDs
-// (one or two per SIMD, 25 000 instructions each, nothing to hide a wave's own scalar/LDS/
-// transcendental issue slots behind); 6 500 shorter waves fill every SIMD six deep for about the
-// same instruction total, and a 16-member box is tighter than a 64-member one.
-#define COH_APW 16
-#define COH_QS  72            /* queue slots per sub-lane: (256 staged + 31 carried) / 4 */
-#define COH_NP  2             /* entry pairs per lane and batch: a batch is COH_G = 8 * COH_NP entries
-                                 (2 measured 1.3 % faster per tick than 4: fewer VGPRs, more waves).  EVEN values only:
-                                 the queue is read four entries at a time (COH_NP = 1 compiles, loads nothing and is
-                                 11 % faster and wrong -- an A/B without a parity step found that out) */
-static_assert(COH_NP % 2 == 0, "the cohesion queue is read four entries at a time: COH_NP must be even");
-#define COH_G   (8 * COH_NP)
-
-// an empty statement the optimiser cannot see through: keeps two scalar chains from being paired into packed math
-// (paired into one v_pk_add_f32 the two ordered sums take their operands from two v_mov_b32_dpp: three instructions per
-// queue entry where each add can take its DPP operand itself: 118.5 -> 107.5 us, profiles/r05_ab_compiler_flags.txt)
-#ifdef NH_HOSTSIM
-__device__ __forceinline__ float coh_keep(float x) { return x; }
-#else
-__device__ __forceinline__ float coh_keep(float x) { asm volatile("" : "+v"(x)); return x; }
-#endif
-
-__device__ __forceinline__ float quad_bcast(float v, int sub)
-{
-    // quad_perm:[sub,sub,sub,sub]
-    switch(sub) {
-    case 0:  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x00, 0xf, 0xf, true));
-    case 1:  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x55, 0xf, 0xf, true));
-    case 2:  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xaa, 0xf, 0xf, true));
-    default: return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xff, 0xf, 0xf, true));
-    }
-}
-
-// COH_G queue entries starting at entry jj (a multiple of COH_G): this lane's 2 * COH_NP are local
-// slots jj/4 .. of its own quarter.  TAIL: entries >= n_valid are padding (weight 0).
-template <bool TAIL>
-__device__ __forceinline__ void coh_batch(const float *qx, const float *qz, const double *tab, int sub,
-                                          int jj, int n_valid, int self_k, v2 me, float &comx, float &comz)
-{
-    const f2 mex = {me.x, me.x}, mez = {me.z, me.z};
-    const int lo = sub * COH_QS + (jj >> 2);
-    constexpr int NP = COH_NP;
-    f2 X[NP], Z[NP], ss[NP], ln[NP], tt[NP], W[NP];
-    bool close = false, odd = false;
-#pragma unroll
-    for(int v = 0; v < NP / 2; v++) {
-        const f4 xa = *(const f4*)&qx[lo + 4 * v], za = *(const f4*)&qz[lo + 4 * v];
-        X[2 * v] = f2{xa.x, xa.y}; X[2 * v + 1] = f2{xa.z, xa.w};
-        Z[2 * v] = f2{za.x, za.y}; Z[2 * v + 1] = f2{za.z, za.w};
-    }
-#pragma unroll
-    for(int u = 0; u < NP; u++) {
-        const f2 dx = X[u] - mex, dz = Z[u] - mez;
-        ss[u] = dx * dx + dz * dz;
-        // sqrt_rn_normal on both halves
-        f2 r = {__builtin_amdgcn_sqrtf(ss[u].x), __builtin_amdgcn_sqrtf(ss[u].y)};
-        const f2 rm = {__int_as_float(__float_as_int(r.x) - 1), __int_as_float(__float_as_int(r.y) - 1)};
-        const f2 rp = {__int_as_float(__float_as_int(r.x) + 1), __int_as_float(__float_as_int(r.y) + 1)};
-        const f2 em = __builtin_elementwise_fma(-rm, r, ss[u]);
-        const f2 ep = __builtin_elementwise_fma(-rp, r, ss[u]);
-        r.x = (em.x <= 0.0f) ? rm.x : r.x;  r.y = (em.y <= 0.0f) ? rm.y : r.y;
-        r.x = (ep.x > 0.0f) ? rp.x : r.x;   r.y = (ep.y > 0.0f) ? rp.y : r.y;
-        ln[u] = r;
-        // outside [2^-90, 2^90] (or NaN) and not exactly 0: leave it to the general IEEE expansion
-        odd |= !(ss[u].x >= 0x1p-90f && ss[u].x <= 0x1p90f) && ss[u].x != 0.0f;
-        odd |= !(ss[u].y >= 0x1p-90f && ss[u].y <= 0x1p90f) && ss[u].y != 0.0f;
-    }
-    if(__any(odd)) {
-        asm volatile("" ::: "memory");        // keep the expansion out of the common path
-#pragma unroll
-        for(int u = 0; u < NP; u++) ln[u] = f2{__builtin_sqrtf(ss[u].x), __builtin_sqrtf(ss[u].y)};
-    }
-#pragma unroll
-    for(int u = 0; u < NP; u++) {
-        // cohesion_t_f32 on both halves
-        const f2 x = ln[u] - 37.5f;
-        const f2 q0 = x * (1.0f / 50.0f);
-        const f2 inner = __builtin_elementwise_fma(-q0, f2{50.0f, 50.0f}, x);
-        tt[u] = __builtin_elementwise_fma(inner, f2{1.0f / 50.0f, 1.0f / 50.0f}, q0);
-        close |= ln[u].x < 16.0f || ln[u].y < 16.0f;
-    }
-    if(__any(close)) {                // rare unless the flock is one dense cluster
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for(int u = 0; u < NP; u++) {
-            if(ln[u].x < 16.0f) tt[u].x = cohesion_t_f64(ln[u].x);
-            if(ln[u].y < 16.0f) tt[u].y = cohesion_t_f64(ln[u].y);
-        }
-    }
-    const int k0 = jj + sub;                  // entry number of this lane's first entry; then +4 each
-#pragma unroll
-    for(int u = 0; u < NP; u++) {
-        const f2 a = tt[u] * -6.0f;
-        float w0 = exp_f32_magic(a.x, tab), w1 = exp_f32_magic(a.y, tab);
-        // curr == uid is skipped by the reference: a zero weight adds +-0, which leaves the (never
-        // negative-zero) running sum unchanged; so does the padding of the last batch
-        const int ka = k0 + 8 * u, kb = ka + 4;
-        if(ka == self_k || (TAIL && ka >= n_valid)) w0 = 0.0f;
-        if(kb == self_k || (TAIL && kb >= n_valid)) w1 = 0.0f;
-        W[u] = f2{w0, w1};
-    }
-    // products, then the ordered sums: entry jj + 4*i + s is held by sub-lane s as element i
-#pragma unroll
-    for(int u = 0; u < NP; u++) {
-        const f2 px = X[u] * W[u], pz = Z[u] * W[u];
-#pragma unroll
-        for(int h = 0; h < 2; h++) {
-            const float tx = h ? px.y : px.x, tz = h ? pz.y : pz.x;
-#pragma unroll
-            for(int sb = 0; sb < 4; sb++) {
-                // (kept apart: paired into one v_pk_add_f32 the two sums take their operands from two v_mov_b32_dpp
-                // -- three instructions per entry; on their own each add takes its DPP operand itself, two)
-                comx = coh_keep(comx + quad_bcast(tx, sb));
-                comz = coh_keep(comz + quad_bcast(tz, sb));
-            }
-        }
-    }
-}
-
-// perm / bin_start: the lane grouping of the previous regrouping (the members inside the work range, flock f's
-// at perm[bin_start[f * COH_BINS] .. bin_start[(f + 1) * COH_BINS])); *perm_valid = 0: the identity over the
-// whole flock instead (k_coh_plan).
-// INLINE_PLAN (at most 64 flocks: lane = flock): every wave works the launch plan out for itself -- the check
-// that the grouping was built for these flock offsets and this work range, the wave prefix over the flocks --
-// instead of reading what a one-workgroup kernel in front of the launch left (k_coh_plan: 6 us and a launch
-// gap on the chain that gates k_agent_mid; here ~40 instructions per wave).
-template <bool INLINE_PLAN>
-__global__ __launch_bounds__(64) void k_cohesion(nh_step_params P, const int32_t *wave_off,
-                                                 const int32_t *perm, const int32_t *perm_valid,
-                                                 float *coh_xz, const int32_t *bin_start, const int32_t *saved)
-{
-    __shared__ double tab[64];
-    // the members of the current tile that survive the box test, in member order (+ carry-over):
-    // entry k lives in slot (k & 3) * COH_QS + (k >> 2)
-    __shared__ __attribute__((aligned(16))) float qx[4 * COH_QS];
-    __shared__ __attribute__((aligned(16))) float qz[4 * COH_QS];
-    const int t = threadIdx.x, sub = t & 3;
-    const int wv = blockIdx.x;
-    int f = 0, first_wave = 0;
-    bool use_perm;
-    if(INLINE_PLAN) {
-        const int nf = P.n_flocks;
-        bool ok = saved[nf + 1] == P.work_begin && saved[nf + 2] == P.work_end && saved[nf + 3] == P.members_key;
-        if(t <= nf) ok = ok && saved[t] == P.flock_offsets[t];
-        if(t == 0 && nf == 64) ok = ok && saved[64] == P.flock_offsets[64];
-        use_perm = __all(ok);
-        int v = 0;
-        if(t < nf) {
-            const int cnt = use_perm ? bin_start[(t + 1) * COH_BINS] - bin_start[t * COH_BINS]
-                                     : P.flock_offsets[t + 1] - P.flock_offsets[t];
-            v = (cnt + COH_APW - 1) / COH_APW;
-        }
-        const int incl = wave_incl_scan(v), excl = incl - v;
-        if(wv >= __shfl(incl, 63)) return;
-        // the last flock whose first wave is <= wv (empty flocks share their successor's prefix)
-        f = __popcll(__ballot(t < nf && excl <= wv)) - 1;
-        first_wave = __shfl(excl, f);
-    }else{
-        if(wv >= wave_off[P.n_flocks]) return;
-        // flock of this wave: binary search over the wave prefix (uniform)
-        int lo = 0, hi = P.n_flocks;
-        while(hi - lo > 1) {
-            int mid = (lo + hi) >> 1;
-            if(wave_off[mid] <= wv) lo = mid; else hi = mid;
-        }
-        f = lo;
-        first_wave = wave_off[f];
-        use_perm = *perm_valid != 0;
-    }
-    tab[t] = c_exp2_64[t];
-    const float scaled_max_force = (float)((double)(0.75f / (float)P.hz) * 20.0);
-    const int b = P.flock_offsets[f], e = P.flock_offsets[f + 1];
-    const int pb = use_perm ? bin_start[f * COH_BINS] : b;
-    const int pe = use_perm ? bin_start[(f + 1) * COH_BINS] : e;
-    const int gp = pb + (wv - first_wave) * COH_APW + (t >> 2);
-    const bool mine = gp < pe;
-    // CSR entry of this quad's member (any permutation of the flock's entries serves; a grouping
-    // made for other flock offsets or another work range is ignored)
-    const int g = mine ? (use_perm ? perm[gp] : gp) : -1;
-    const int uid = mine ? P.flock_members[g] : -1;
-    bool act = mine && uid >= P.work_begin && uid < P.work_end;
-    if(act) act = state_uses_point_seek(P.state[uid]) && !(P.flags[uid] & NAVHIP_ENTITY_FLAG_COMBAT_HELD);
-    if(!__syncthreads_or(act)) return;
-    const v2 me = act ? mkv(P.pos_xz[2 * uid], P.pos_xz[2 * uid + 1]) : mkv(0.0f, 0.0f);
-    // bounding box of the wave's active members
-    float bx0 = act ? me.x : INFINITY, bx1 = act ? me.x : -INFINITY;
-    float bz0 = act ? me.z : INFINITY, bz1 = act ? me.z : -INFINITY;
-#pragma unroll
-    for(int d = 4; d < 64; d <<= 1) {
-        bx0 = fminf(bx0, __shfl_xor(bx0, d)); bx1 = fmaxf(bx1, __shfl_xor(bx1, d));
-        bz0 = fminf(bz0, __shfl_xor(bz0, d)); bz1 = fmaxf(bz1, __shfl_xor(bz1, d));
-    }
-    const unsigned long long lt_mask = (1ull << t) - 1ull;
-    float comx = 0.0f, comz = 0.0f;
-    int self_k = -1;                                      // queue entry of this quad's own member
-    int pend = 0;                                         // entries carried over from the last tile
-    for(int jb = b; jb < e; jb += 256) {
-        // ---- stage the tile behind the carry-over [0, pend)
-        int ncnt = pend;
-        const int gl = act ? g - jb : -1;                 // own slot in the unfiltered tile, if any
-#pragma unroll
-        for(int q = 0; q < 4; q++) {
-            const int j = jb + q * 64 + t;
-            bool keep = false;
-            float2 c2 = make_float2(0.0f, 0.0f);
-            if(j < e) {
-                const int m = P.flock_members[j];
-                c2 = make_float2(P.pos_xz[2 * m], P.pos_xz[2 * m + 1]);
-                const float dx = fmaxf(fmaxf(bx0 - c2.x, c2.x - bx1), 0.0f);
-                const float dz = fmaxf(fmaxf(bz0 - c2.y, c2.y - bz1), 0.0f);
-                keep = !(dx * dx + dz * dz > COH_FAR * COH_FAR);       // NaN stays in
-            }
-            const unsigned long long mk = __ballot(keep);
-            const int at = ncnt + __popcll(mk & lt_mask);
-            if(keep) { const int sl = (at & 3) * COH_QS + (at >> 2); qx[sl] = c2.x; qz[sl] = c2.y; }
-            // (an active member lies inside the wave's box, so it is always kept)
-            const int at_self = __shfl(at, gl & 63);
-            if((gl >> 6) == q) self_k = at_self;          // gl < 0 or >= 256 never matches q = 0..3
-            ncnt += __popcll(mk);
-        }
-        const bool last = jb + 256 >= e;
-        int cnt32 = ncnt & ~(COH_G - 1);                  // whole batches
-        if(last && cnt32 < ncnt) {
-            // pad the final batch with finite dummies (their weight is forced to 0)
-            const int k = ncnt + t;
-            if(k < cnt32 + COH_G) { const int sl = (k & 3) * COH_QS + (k >> 2); qx[sl] = 0.0f; qz[sl] = 0.0f; }
-        }
-        __syncthreads();
-        if(act) {
-            for(int jj = 0; jj < cnt32; jj += COH_G)
-                coh_batch<false>(qx, qz, tab, sub, jj, ncnt, self_k, me, comx, comz);
-            if(last && cnt32 < ncnt)
-                coh_batch<true>(qx, qz, tab, sub, cnt32, ncnt, self_k, me, comx, comz);
-        }
-        if(!last) {
-            // carry the last (< COH_G) entries over: entry k -> k - cnt32 keeps its sub-lane
-            pend = ncnt - cnt32;
-            float cx = 0.0f, cz = 0.0f;
-            const int k = cnt32 + t;
-            if(t < pend) { const int sl = (k & 3) * COH_QS + (k >> 2); cx = qx[sl]; cz = qz[sl]; }
-            __syncthreads();
-            if(t < pend) { const int sl = (t & 3) * COH_QS + (t >> 2); qx[sl] = cx; qz[sl] = cz; }
-            self_k = (self_k >= cnt32) ? self_k - cnt32 : -1;
-            __syncthreads();
-        }
-    }
-    if(act && sub == 0) {
-        const int count = (e - b) - 1;
-        v2 ret = mkv(0.0f, 0.0f);
-        if(count > 0) {
-            const v2 cm = vscale(mkv(comx, comz), 1.0f / (float)count);
-            ret = vtrunc(vsub(cm, me), scaled_max_force);
-        }
-        coh_xz[2 * uid] = ret.x;
-        coh_xz[2 * uid + 1] = ret.z;
-    }
-}
-// ---------------------------------------------------------------------------------------------
 // wave-per-agent pieces of k_agent_full
 // ---------------------------------------------------------------------------------------------
 // waves (= agents) per workgroup of the wave-per-agent kernels; 2 measured best for the round-1
@@ -1048,7 +333,6 @@ __device__ int derive_r10(const nh_grid &G, v2 me, const uint32_t *ids30, const 
 // one-wave workgroups and the field builds, which take every wave slot the moment it frees up -- a workgroup
 // of four waves waits until four slots of ONE compute unit are free at the same moment.
 #define NBR_BLOCK 64
-#define SP_BLOCK 64
 template <bool STRIDED>
 __global__ __launch_bounds__(NBR_BLOCK) __attribute__((amdgpu_waves_per_eu(NBR_WAVES, 8)))
 void k_agent_nbr(nh_grid G, int npool_max, nh_nbr NB, float scaled_max_force)
@@ -1131,6 +415,27 @@ void k_agent_mid(nh_step_params P, nh_nbr NB, const float *coh_xz,
 #define CPR_WAVES 4
 // problems on the workgroup lists from which one wave takes one problem (k_cp_heavy_solo) instead of a team
 #define CP_SOLO_MIN 8192
+
+// Running totals of the work units of a kernel's sub-lists, by the first wave of the workgroup: entry k
+// holds `cnt[k]` agents = (cnt[k] + per - 1) / per units; unit_end[k] = units of the entries up to and
+// including k.  (One thread adding up 128-256 entries in front of every workgroup's first barrier was 770-1 500
+// wave instructions per workgroup: a fifth of everything k_cp_small executed.)
+template <typename F>
+__device__ __forceinline__ void unit_totals(int32_t *unit_end, int ntab, F units_of)
+{
+    if(threadIdx.x >= 64) return;
+    const int lane = threadIdx.x, per_lane = (ntab + 63) >> 6;        // consecutive entries per lane
+    int local = 0;
+    for(int j = 0; j < per_lane; j++) {
+        const int k = lane * per_lane + j;
+        if(k < ntab) local += units_of(k);
+    }
+    int run = wave_incl_scan(local) - local;
+    for(int j = 0; j < per_lane; j++) {
+        const int k = lane * per_lane + j;
+        if(k < ntab) { run += units_of(k); unit_end[k] = run; }
+    }
+}
 
 // first k with end[k] > u (n - 1 when there is none), for a wave-uniform u, by the whole wave: the running
 // totals do not decrease, so it is the number of entries <= u -- one or two ballots instead of a binary search
@@ -1481,143 +786,6 @@ __global__ __launch_bounds__(256) void k_spatial_query(nh_grid G, const float *q
     if(lane == 0) out_counts[q] = n;
 }
 
-// ---------------------------------------------------------------------------------------------
-// the arrival arm of entity_compute_update (movement.c:2303; see include/navhip.h): a row of 16 lanes
-// per unit -- the scalar tests on every lane, the flock-mate scan (:953) shared by the lanes
-// ---------------------------------------------------------------------------------------------
-// the ARRIVED members of every flock, compacted to the front of the flock's range of the member list (any order)
-__global__ __launch_bounds__(256) void k_arrived_compact(nh_step_params P, float4 *arrived, int32_t *arrived_n)
-{
-    __shared__ int count;
-    const int f = blockIdx.x;
-    if(threadIdx.x == 0) count = 0;
-    __syncthreads();
-    const int b = P.flock_offsets[f], e = P.flock_offsets[f + 1];
-    for(int k0 = b; k0 < e; k0 += 256) {
-        const int k = k0 + (int)threadIdx.x;
-        int m = -1;
-        if(k < e) { m = P.flock_members[k]; if(P.state[m] != NAVHIP_STATE_ARRIVED) m = -1; }
-        const uint64_t bal = __ballot(m >= 0);
-        int base = 0;
-        if((threadIdx.x & 63) == 0 && bal) base = atomicAdd(&count, __popcll(bal));
-        base = __shfl(base, 0);
-        if(m >= 0) {
-            const int at = b + base + __popcll(bal & ((1ull << (threadIdx.x & 63)) - 1ull));
-            // (the scratch holds n_ents rows -- an entity belongs to at most one flock; a device-side member list that
-            // breaks that promise loses rows of the scan instead of writing past the buffer)
-            if(at < P.n_ents) arrived[at] = make_float4(P.pos_xz[2 * m], P.pos_xz[2 * m + 1], P.radius[m], __int_as_float(m));
-        }
-    }
-    __syncthreads();
-    if(threadIdx.x == 0) arrived_n[f] = count;
-}
-
-__global__ __launch_bounds__(256) void k_state_update(nh_step_params P, navhip_state_in in, const float4 *arrived,
-                                                      const int32_t *arrived_n, uint8_t *out_state, uint8_t *out_flags)
-{
-    typedef grp<16> g;
-    const int uid = P.work_begin + ((blockIdx.x * 256 + threadIdx.x) >> 4);
-    const int gl = g::lane();
-    if(uid >= P.work_end) return;
-    const int state = P.state[uid];
-    uint8_t flags = 0, next = (uint8_t)state;
-    const int flock = P.flock[uid];
-    const uint32_t eflags = P.flags[uid];
-    const float radius = P.radius[uid];
-    const int layer = nav_layer_for(eflags, radius);
-    bool decided = false;
-    if(eflags & NAVHIP_ENTITY_FLAG_GARRISONED) {                           // :2344-2351
-        if(!state_is_still(state)) { flags = NAVHIP_SU_SET_STATE; next = NAVHIP_STATE_ARRIVED; }
-        decided = true;
-    }else if(state == NAVHIP_STATE_SEEK_ENEMIES || state == NAVHIP_STATE_ARRIVED) {
-        decided = true;                                                    // :2521-2528, :2643: no transition
-    }else if((state != NAVHIP_STATE_MOVING && state != NAVHIP_STATE_MOVING_IN_FORMATION) || flock < 0
-          || (in.skip && in.skip[uid]) || !P.map.layers[layer].cost || in.flock_layer[flock] != layer) {
-        flags = NAVHIP_SU_HOST;
-        decided = true;
-    }
-    if(!decided) {
-        const v2 np = mkv(in.new_pos_xz[2 * uid], in.new_pos_xz[2 * uid + 1]);
-        const v2 target = mkv(P.flock_target_xz[2 * flock], P.flock_target_xz[2 * flock + 1]);
-        if(pos_pathable(P, layer, np.x, np.z)) {                           // :2437
-            // ---- arrived(uid, new_pos), :2170
-            const float thresh = radius * 1.5f;
-            bool arr = vlen(vsub(target, np)) < thresh;
-            if(!arr) {
-                // N_IsAdjacentToImpassable, nav.c:4745: a 4-neighbour tile that n_tile_blocked (:235)
-                tiledesc t;
-                bool adj = false;
-                if(tile_for_point(P, np.x, np.z, t)) {
-                    const int ar = t.chunk_r * 64 + t.tile_r, ac = t.chunk_c * 64 + t.tile_c;
-                    const int dr[4] = {-1, 0, 0, 1}, dc[4] = {0, -1, 1, 0};
-#pragma unroll
-                    for(int k = 0; k < 4; k++) {
-                        const int r = ar + dr[k], c = ac + dc[k];
-                        if(r < 0 || c < 0 || r >= P.map.h * 64 || c >= P.map.w * 64) continue;      // M_Tile_RelativeDesc
-                        tiledesc a;
-                        a.chunk_r = r >> 6; a.chunk_c = c >> 6; a.tile_r = r & 63; a.tile_c = c & 63;
-                        adj = adj || tile_probe(P, layer, a) != 1u;          // impassable or blocked
-                    }
-                }
-                if(adj) {
-                    // N_IsMaximallyClose, nav.c:4727-4740: any of the destination's closest island tiles
-                    // within the threshold (centre as the reference computes it: map_pos -/+ tile * 4)
-                    bool close = false;
-                    for(int k = in.flock_tiles_off[flock] + gl; k < in.flock_tiles_off[flock + 1]; k += 16) {
-                        const float cx = P.map_x - (float)in.flock_tiles[2 * k + 1] * 4.0f;
-                        const float cz = P.map_z + (float)in.flock_tiles[2 * k] * 4.0f;
-                        close = close || vlen(vsub(mkv(cx, cz), np)) <= thresh;
-                    }
-                    arr = g::any(close);
-                }
-            }
-            if(!arr) {
-                const v2 nearest = mkv(in.flock_nearest_xz[2 * flock], in.flock_nearest_xz[2 * flock + 1]);
-                if(nearest.x == nearest.x) arr = vlen(vsub(nearest, np)) < thresh;                   // :2187-2192
-            }
-            if(!arr) {
-                // ---- a flock mate that touches us has arrived, :2480-2497 (positions and states of the
-                // snapshot: adjacent_flock_members reads the tick's tables).  An existence test -- order does not
-                // matter --, so the row scans the ARRIVED members only: k_arrived_compact has put {x, z, radius, uid}
-                // of those, flock by flock, where the flock's member list starts (a fresh world: none; the scan of
-                // every member cost 405 us per 100 000 units, nine tenths of the state pass)
-                const v2 me = mkv(P.pos_xz[2 * uid], P.pos_xz[2 * uid + 1]);
-                bool hit = false;
-                const int b = P.flock_offsets[flock], e = min(b + arrived_n[flock], P.n_ents);
-                for(int k0 = b; k0 < e && !g::any(hit); k0 += 16) {
-                    const int k = k0 + gl;
-                    if(k < e) {
-                        const float4 a = arrived[k];
-                        if(__float_as_int(a.w) != uid)
-                            hit = vlen(vsub(me, mkv(a.x, a.y))) <= radius + a.z + 5.0f;                  // ADJACENCY_SEP_DIST
-                    }
-                }
-                arr = g::any(hit);
-            }
-            if(arr) {
-                flags = NAVHIP_SU_SET_STATE | NAVHIP_SU_BLOCK; next = NAVHIP_STATE_ARRIVED;
-            }else{
-                const v2 vdes = mkv(in.vdes_xz[2 * uid], in.vdes_xz[2 * uid + 1]);
-                if(vlen(vdes) < 1.0f / 1024.0f) {                          // :2508
-                    flags = NAVHIP_SU_SET_STATE | NAVHIP_SU_BLOCK; next = NAVHIP_STATE_WAITING;
-                }
-            }
-        }
-    }
-    if(gl == 0) { out_state[uid] = next; out_flags[uid] = flags; }
-}
-
-void nh_launch_state_update(const nh_step_params &P, const navhip_state_in &in, float4 *d_arrived, int32_t *d_arrived_n,
-                            uint8_t *d_state, uint8_t *d_flags, hipStream_t s)
-{
-    const int n = P.work_end - P.work_begin;
-    if(n <= 0) return;
-    if(P.n_flocks > 0)
-        hipLaunchKernelGGL(k_arrived_compact, dim3(P.n_flocks), dim3(256), 0, s, P, d_arrived, d_arrived_n);
-    hipLaunchKernelGGL(k_state_update, dim3((n + 15) / 16), dim3(256), 0, s, P, in, (const float4*)d_arrived,
-                       (const int32_t*)d_arrived_n, d_state, d_flags);
-}
-
 // N_DesiredGroupArrivalVelocity (nav.c:3561): direction under each point in the chunk field of its mapping
 // row + "the tile is a sink inside the zone's disc" (:3596-3600)
 __global__ __launch_bounds__(256) void k_region_lookup(nh_step_params P, int nq, const float *pos, const int32_t *rows,
@@ -1715,50 +883,6 @@ extern "C" int navhip_debug_cp_attempts(unsigned long long out[9], int reset)
 // ---------------------------------------------------------------------------------------------
 // host-side launchers
 // ---------------------------------------------------------------------------------------------
-// Four dependent launches, no memset (cell_count is zeroed by k_sp_scan_add once it has been
-// consumed; the box of the slab filter is the exception).
-void nh_launch_spatial_build(nh_grid &G, const float *d_pos_xz, nh_spatial_scratch &S,
-                             int slab_begin, int slab_end, hipStream_t s)
-{
-    const int n = G.n, ncells = G.grid_w * G.grid_h;
-    // a strict sub-range of the entities is stepped: hash only what its queries can reach
-    const int32_t *box = nullptr;
-    int32_t *box_next = nullptr;
-    if(S.box && (slab_begin > 0 || slab_end < n)) {
-        int32_t *mine = S.box + 4 * (S.box_parity & 1);
-        box_next = S.box + 4 * ((S.box_parity & 1) ^ 1);
-        if(slab_end > slab_begin)
-            hipLaunchKernelGGL(k_sp_bbox, dim3(min(128, (slab_end - slab_begin + 255) / 256)), dim3(256), 0, s,
-                               d_pos_xz, slab_begin, slab_end, mine);
-        box = mine;
-    }
-    G.cell_start = S.cell_start; G.recA = S.recA; G.recV = S.recV; G.pool_of = S.pool_of;
-    // (a slab: the list of pool slots with a work item lives in ent_rank's buffer, which is free once k_sp_scatter has
-    // read it; its length behind the two slab boxes)
-    int32_t *active = box ? S.ent_rank : nullptr, *n_active = box ? S.box + 8 : nullptr;
-    G.active = active; G.n_active = n_active;
-    if(!box && n > 0 && n <= SP_SMALL_N && ncells <= SP_SMALL_CELLS) {
-        // a small world, all of it stepped: one workgroup instead of five launches
-        hipLaunchKernelGGL(k_sp_build_small, dim3(1), dim3(SP_SMALL_T), 0, s, G, d_pos_xz, S.src, n, ncells, slab_begin, slab_end, S.cell_start, S.recA,
-                           S.recV, S.pool_of);
-        return;
-    }
-    if(n > 0)
-        hipLaunchKernelGGL(k_sp_count, dim3((n + 255) / 256), dim3(256), 0, s, G, d_pos_xz, n,
-                           S.ent_cell, S.ent_rank, S.cell_count, box, box_next, n_active);
-    const int nblocks = (ncells + NH_SCAN_T - 1) / NH_SCAN_T;
-    hipLaunchKernelGGL(k_sp_scan_local, dim3(nblocks), dim3(NH_SCAN_T), 0, s, S.cell_count, S.cell_start,
-                       S.block_sum, ncells, G, box);
-    hipLaunchKernelGGL(k_sp_scan_add, dim3(nblocks), dim3(NH_SCAN_T), 0, s, S.cell_start, S.block_sum, ncells,
-                       nblocks, S.cell_count, G, box);
-    if(n > 0) {
-        hipLaunchKernelGGL(k_sp_scatter, dim3((n + 255) / 256), dim3(256), 0, s, S.ent_cell, S.ent_rank, n,
-                           S.cell_start, S.tmp_id);
-        hipLaunchKernelGGL(k_sp_place, dim3((n + SP_BLOCK - 1) / SP_BLOCK), dim3(SP_BLOCK), 0, s, G, d_pos_xz, S.src,
-                           S.ent_cell, S.tmp_id, n, slab_begin, slab_end, S.recA, S.recV, S.pool_of, active, n_active);
-    }
-}
-
 void nh_launch_agent_nbr(const nh_step_params &P, const nh_nbr &NB, hipStream_t s)
 {
     if(P.n_ents > 0 && P.work_end > P.work_begin) {
@@ -1776,104 +900,6 @@ void nh_launch_agent_nbr(const nh_step_params &P, const nh_nbr &NB, hipStream_t 
     }
 }
 
-// scratch of the cohesion launch: wave prefix | bin counts | bin fills | bin starts | scan block sums
-// | bin of each CSR entry | perm x2 | flock offsets the two perms were built for x2 | perm-valid flag.
-// (Tried: scan + plan + re-zeroing fused into ONE single-workgroup kernel to shorten the chain of
-// dependent launches -- 0.465 vs 0.450 ms/tick in one session: the serial chunks of a single
-// workgroup take longer than three small parallel kernels.)
-struct coh_scratch {
-    int32_t *wave_off, *bin_count, *bin_fill, *bin_start, *block_sum, *bin_of, *perm[2], *saved[2], *valid;
-    int nb, nblocks;
-};
-static coh_scratch coh_layout(int32_t *scratch, int n_flocks, int n_members)
-{
-    coh_scratch C;
-    C.nb = n_flocks * COH_BINS; C.nblocks = (C.nb + NH_SCAN_T - 1) / NH_SCAN_T;
-    C.wave_off = scratch;
-    C.bin_count = C.wave_off + n_flocks + 1;
-    C.bin_fill = C.bin_count + C.nb;
-    C.bin_start = C.bin_fill + C.nb;                      // [nb + 1]
-    C.block_sum = C.bin_start + C.nb + 1;
-    C.bin_of = C.block_sum + C.nblocks;
-    C.perm[0] = C.bin_of + n_members;
-    C.perm[1] = C.perm[0] + n_members;
-    C.saved[0] = C.perm[1] + n_members;
-    C.saved[1] = C.saved[0] + n_flocks + 4;
-    C.valid = C.saved[1] + n_flocks + 4;
-    return C;
-}
-size_t nh_cohesion_scratch_bytes(int n_flocks, int n_members)
-{
-    const size_t nb = (size_t)n_flocks * COH_BINS;
-    return sizeof(int32_t) * (3 * ((size_t)n_flocks + 4) + 3 * nb + 1 + (nb + NH_SCAN_T - 1) / NH_SCAN_T
-                              + 3 * (size_t)n_members + 1);
-}
-
-// after (re)allocation: no grouping has been built for any flock layout yet
-hipError_t nh_cohesion_scratch_reset(int32_t *scratch, int n_flocks, int n_members, hipStream_t s)
-{
-    const coh_scratch C = coh_layout(scratch, n_flocks, n_members);
-    return hipMemsetAsync(C.saved[0], 0xff, sizeof(int32_t) * 2 * ((size_t)n_flocks + 4), s);
-}
-
-__global__ void k_zero_i32(int32_t *p, int n)
-{
-    for(int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = 0;
-}
-
-// the counting sort that regroups the lanes of every flock (k_coh_bin .. k_coh_scatter) into perm[which]
-static void coh_regroup(const nh_step_params &P, const coh_scratch &C, int which, hipStream_t s)
-{
-    // (one launch: hipMemsetAsync of an unaligned range is up to three fill kernels)
-    hipLaunchKernelGGL(k_zero_i32, dim3(min(64, (2 * C.nb + 255) / 256)), dim3(256), 0, s, C.bin_count, 2 * C.nb);
-    const int gm = (P.n_members + 255) / 256;
-    hipLaunchKernelGGL(k_coh_bin, dim3(gm), dim3(256), 0, s, P, C.bin_of, C.bin_count, C.saved[which]);
-    hipLaunchKernelGGL(k_sp_scan_local, dim3(C.nblocks), dim3(NH_SCAN_T), 0, s, C.bin_count, C.bin_start,
-                       C.block_sum, C.nb, P.grid, (const int32_t*)nullptr);
-    hipLaunchKernelGGL(k_sp_scan_add, dim3(C.nblocks), dim3(NH_SCAN_T), 0, s, C.bin_start, C.block_sum, C.nb,
-                       C.nblocks, (int32_t*)nullptr, P.grid, (const int32_t*)nullptr);
-    hipLaunchKernelGGL(k_coh_scatter, dim3(gm), dim3(256), 0, s, P, C.bin_of, C.bin_start, C.bin_fill,
-                       C.perm[which]);
-}
-
-// The cohesion term of one tick.  *parity (in/out, kept by the context) = which of the two perm
-// buffers the NEXT regrouping writes.
-// k_cohesion starts at once on the grouping the PREVIOUS tick left behind (any permutation of a flock's
-// entries is valid; the grouping only has to be spatially coherent, and agents move ~1 wu per tick;
-// k_coh_plan checks that it was built for these flock offsets and this work range, else the identity is
-// used), and the regrouping for the next tick follows it -- nh_launch_cohesion_regroup, which the caller
-// launches AFTER recording its "cohesion done" event: five dependent small launches leave the tick's
-// critical path.  That holds for a rank that steps a slab as well: its grouping holds the slab's members
-// only (k_coh_bin), so the members of the other ranks occupy no lanes.
-#define COH_INLINE_PLAN_MAX 64
-bool nh_launch_cohesion(const nh_step_params &P, int32_t *scratch, float *d_coh, int *parity, hipStream_t s)
-{
-    if(!(P.n_ents > 0 && P.n_flocks > 0 && P.n_members > 0)) return false;
-    const coh_scratch C = coh_layout(scratch, P.n_flocks, P.n_members);
-    // upper bound of the number of 16-member (COH_APW) waves (the identity fallback needs a lane per
-    // member of the whole snapshot); surplus waves exit at once
-    const int nwaves = (P.n_members + 15) / 16 + P.n_flocks;
-    const int prev = *parity ^ 1;
-    if(P.n_flocks <= COH_INLINE_PLAN_MAX) {
-        hipLaunchKernelGGL(k_cohesion<true>, dim3(nwaves), dim3(64), 0, s, P, (const int32_t*)C.wave_off,
-                           (const int32_t*)C.perm[prev], (const int32_t*)C.valid, d_coh, (const int32_t*)C.bin_start,
-                           (const int32_t*)C.saved[prev]);
-        return true;
-    }
-    hipLaunchKernelGGL(k_coh_plan, dim3(1), dim3(256), 0, s, (const int32_t*)C.bin_start, P.flock_offsets,
-                       (const int32_t*)C.saved[prev], P.n_flocks, P.work_begin, P.work_end, P.members_key, C.wave_off, C.valid);
-    hipLaunchKernelGGL(k_cohesion<false>, dim3(nwaves), dim3(64), 0, s, P, (const int32_t*)C.wave_off,
-                       (const int32_t*)C.perm[prev], (const int32_t*)C.valid, d_coh, (const int32_t*)C.bin_start,
-                       (const int32_t*)C.saved[prev]);
-    return true;                                  // caller: record the event, then ..._regroup
-}
-
-void nh_launch_cohesion_regroup(const nh_step_params &P, int32_t *scratch, int *parity, hipStream_t s)
-{
-    const coh_scratch C = coh_layout(scratch, P.n_flocks, P.n_members);
-    coh_regroup(P, C, *parity, s);
-    *parity ^= 1;
-}
 // entries a sub-list can receive: its producers are the k_agent_mid waves with index = sub (mod NH_WL_SUB), each of
 // which steps 64 entities
 int nh_worklist_cap(int n_work)

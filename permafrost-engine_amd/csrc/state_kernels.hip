@@ -1,5 +1,6 @@
 // state_kernels.hip -- more of entity_compute_update (movement.c:2303) on the device, SURVEY section 8(f4):
-// the heading gate (:2319-2336), the arms of the state switch that k_state_update does not cover except
+// the heading gate (:2319-2336), the arrival arm (k_state_update with k_arrived_compact), the arms of the state switch
+// that k_state_update does not cover except
 // STATE_SURROUND_ENTITY (:2423-2437, :2569-2668), adjacent_settled_count (:982) and the arrival overlay's settle rule
 // (G_Arrival_ShouldSettle, arrival.c:946) with what it calls: N_SegmentWithinRegion (nav.c:4326) over
 // M_Tile_LineSupercoverTilesSorted (tile.c:430), arrival_near_region / arrival_near_open_slot
@@ -16,6 +17,7 @@
 #include "navhip_internal.h"
 #include "agent_internal.h"
 #include "agent_math.h"
+#include "lane_group.h"
 
 #define SK_QUERY_R   30.0f       /* SEPARATION_NEIGHB_RADIUS, movement.c:428                            */
 #define SK_QUERY_MAX 128         /* near_ents[128], movement.c:997                                      */
@@ -79,6 +81,143 @@ __global__ __launch_bounds__(256) void k_heading_gate(nh_step_params P, int begi
     }
     out_new_pos[2 * i] = np.x; out_new_pos[2 * i + 1] = np.z;
     out_gate[i] = gate;
+}
+
+// ---------------------------------------------------------------------------------------------
+// the arrival arm of entity_compute_update (movement.c:2303; see include/navhip.h): a row of 16 lanes
+// per unit -- the scalar tests on every lane, the flock-mate scan (:953) shared by the lanes
+// ---------------------------------------------------------------------------------------------
+// the ARRIVED members of every flock, compacted to the front of the flock's range of the member list (any order)
+__global__ __launch_bounds__(256) void k_arrived_compact(nh_step_params P, float4 *arrived, int32_t *arrived_n)
+{
+    __shared__ int count;
+    const int f = blockIdx.x;
+    if(threadIdx.x == 0) count = 0;
+    __syncthreads();
+    const int b = P.flock_offsets[f], e = P.flock_offsets[f + 1];
+    for(int k0 = b; k0 < e; k0 += 256) {
+        const int k = k0 + (int)threadIdx.x;
+        int m = -1;
+        if(k < e) { m = P.flock_members[k]; if(P.state[m] != NAVHIP_STATE_ARRIVED) m = -1; }
+        const uint64_t bal = __ballot(m >= 0);
+        int base = 0;
+        if((threadIdx.x & 63) == 0 && bal) base = atomicAdd(&count, __popcll(bal));
+        base = __shfl(base, 0);
+        if(m >= 0) {
+            const int at = b + base + __popcll(bal & ((1ull << (threadIdx.x & 63)) - 1ull));
+            // (the scratch holds n_ents rows -- an entity belongs to at most one flock; a device-side member list that
+            // breaks that promise loses rows of the scan instead of writing past the buffer)
+            if(at < P.n_ents) arrived[at] = make_float4(P.pos_xz[2 * m], P.pos_xz[2 * m + 1], P.radius[m], __int_as_float(m));
+        }
+    }
+    __syncthreads();
+    if(threadIdx.x == 0) arrived_n[f] = count;
+}
+
+__global__ __launch_bounds__(256) void k_state_update(nh_step_params P, navhip_state_in in, const float4 *arrived,
+                                                      const int32_t *arrived_n, uint8_t *out_state, uint8_t *out_flags)
+{
+    typedef grp<16> g;
+    const int uid = P.work_begin + ((blockIdx.x * 256 + threadIdx.x) >> 4);
+    const int gl = g::lane();
+    if(uid >= P.work_end) return;
+    const int state = P.state[uid];
+    uint8_t flags = 0, next = (uint8_t)state;
+    const int flock = P.flock[uid];
+    const uint32_t eflags = P.flags[uid];
+    const float radius = P.radius[uid];
+    const int layer = nav_layer_for(eflags, radius);
+    bool decided = false;
+    if(eflags & NAVHIP_ENTITY_FLAG_GARRISONED) {                           // :2344-2351
+        if(!state_is_still(state)) { flags = NAVHIP_SU_SET_STATE; next = NAVHIP_STATE_ARRIVED; }
+        decided = true;
+    }else if(state == NAVHIP_STATE_SEEK_ENEMIES || state == NAVHIP_STATE_ARRIVED) {
+        decided = true;                                                    // :2521-2528, :2643: no transition
+    }else if((state != NAVHIP_STATE_MOVING && state != NAVHIP_STATE_MOVING_IN_FORMATION) || flock < 0
+          || (in.skip && in.skip[uid]) || !P.map.layers[layer].cost || in.flock_layer[flock] != layer) {
+        flags = NAVHIP_SU_HOST;
+        decided = true;
+    }
+    if(!decided) {
+        const v2 np = mkv(in.new_pos_xz[2 * uid], in.new_pos_xz[2 * uid + 1]);
+        const v2 target = mkv(P.flock_target_xz[2 * flock], P.flock_target_xz[2 * flock + 1]);
+        if(pos_pathable(P, layer, np.x, np.z)) {                           // :2437
+            // ---- arrived(uid, new_pos), :2170
+            const float thresh = radius * 1.5f;
+            bool arr = vlen(vsub(target, np)) < thresh;
+            if(!arr) {
+                // N_IsAdjacentToImpassable, nav.c:4745: a 4-neighbour tile that n_tile_blocked (:235)
+                tiledesc t;
+                bool adj = false;
+                if(tile_for_point(P, np.x, np.z, t)) {
+                    const int ar = t.chunk_r * 64 + t.tile_r, ac = t.chunk_c * 64 + t.tile_c;
+                    const int dr[4] = {-1, 0, 0, 1}, dc[4] = {0, -1, 1, 0};
+#pragma unroll
+                    for(int k = 0; k < 4; k++) {
+                        const int r = ar + dr[k], c = ac + dc[k];
+                        if(r < 0 || c < 0 || r >= P.map.h * 64 || c >= P.map.w * 64) continue;      // M_Tile_RelativeDesc
+                        tiledesc a;
+                        a.chunk_r = r >> 6; a.chunk_c = c >> 6; a.tile_r = r & 63; a.tile_c = c & 63;
+                        adj = adj || tile_probe(P, layer, a) != 1u;          // impassable or blocked
+                    }
+                }
+                if(adj) {
+                    // N_IsMaximallyClose, nav.c:4727-4740: any of the destination's closest island tiles
+                    // within the threshold (centre as the reference computes it: map_pos -/+ tile * 4)
+                    bool close = false;
+                    for(int k = in.flock_tiles_off[flock] + gl; k < in.flock_tiles_off[flock + 1]; k += 16) {
+                        const float cx = P.map_x - (float)in.flock_tiles[2 * k + 1] * 4.0f;
+                        const float cz = P.map_z + (float)in.flock_tiles[2 * k] * 4.0f;
+                        close = close || vlen(vsub(mkv(cx, cz), np)) <= thresh;
+                    }
+                    arr = g::any(close);
+                }
+            }
+            if(!arr) {
+                const v2 nearest = mkv(in.flock_nearest_xz[2 * flock], in.flock_nearest_xz[2 * flock + 1]);
+                if(nearest.x == nearest.x) arr = vlen(vsub(nearest, np)) < thresh;                   // :2187-2192
+            }
+            if(!arr) {
+                // ---- a flock mate that touches us has arrived, :2480-2497 (positions and states of the
+                // snapshot: adjacent_flock_members reads the tick's tables).  An existence test -- order does not
+                // matter --, so the row scans the ARRIVED members only: k_arrived_compact has put {x, z, radius, uid}
+                // of those, flock by flock, where the flock's member list starts (a fresh world: none; the scan of
+                // every member cost 405 us per 100 000 units, nine tenths of the state pass)
+                const v2 me = mkv(P.pos_xz[2 * uid], P.pos_xz[2 * uid + 1]);
+                bool hit = false;
+                const int b = P.flock_offsets[flock], e = min(b + arrived_n[flock], P.n_ents);
+                for(int k0 = b; k0 < e && !g::any(hit); k0 += 16) {
+                    const int k = k0 + gl;
+                    if(k < e) {
+                        const float4 a = arrived[k];
+                        if(__float_as_int(a.w) != uid)
+                            hit = vlen(vsub(me, mkv(a.x, a.y))) <= radius + a.z + 5.0f;                  // ADJACENCY_SEP_DIST
+                    }
+                }
+                arr = g::any(hit);
+            }
+            if(arr) {
+                flags = NAVHIP_SU_SET_STATE | NAVHIP_SU_BLOCK; next = NAVHIP_STATE_ARRIVED;
+            }else{
+                const v2 vdes = mkv(in.vdes_xz[2 * uid], in.vdes_xz[2 * uid + 1]);
+                if(vlen(vdes) < 1.0f / 1024.0f) {                          // :2508
+                    flags = NAVHIP_SU_SET_STATE | NAVHIP_SU_BLOCK; next = NAVHIP_STATE_WAITING;
+                }
+            }
+        }
+    }
+    if(gl == 0) { out_state[uid] = next; out_flags[uid] = flags; }
+}
+
+static void nh_launch_state_update(const nh_step_params &P, const navhip_state_in &in, float4 *d_arrived, int32_t *d_arrived_n,
+                                   uint8_t *d_state, uint8_t *d_flags, hipStream_t s)
+{
+    const int n = P.work_end - P.work_begin;
+    if(n <= 0) return;
+    if(P.n_flocks > 0)
+        hipLaunchKernelGGL(k_arrived_compact, dim3(P.n_flocks), dim3(256), 0, s, P, d_arrived, d_arrived_n);
+    hipLaunchKernelGGL(k_state_update, dim3((n + 15) / 16), dim3(256), 0, s, P, in, (const float4*)d_arrived,
+                       (const int32_t*)d_arrived_n, d_state, d_flags);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -847,7 +986,7 @@ int navhip_heading_gate(navhip_ctx *ctx, const navhip_world *w, const navhip_gat
     return rc;
 }
 
-// k_state_update and k_arrived_compact (agent_kernels.hip) on device arrays
+// k_state_update and k_arrived_compact on device arrays
 int navhip_state_update_dev(navhip_ctx *ctx, const navhip_world *w, const navhip_state_in *in, uint8_t *out_state,
                             uint8_t *out_flags, void *stream)
 {

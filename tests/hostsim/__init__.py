@@ -99,7 +99,7 @@ def group_available():
 def build_group():
     src = os.path.join(HERE, "group_sim.cpp")
     deps = [src, os.path.join(HERE, "wave_emu.h")] + [os.path.join(CSRC, f) for f in
-            ("agent_group.h", "agent_thread.h", "agent_math.h", "agent_types.h", "map_view.h")]
+            ("agent_group.h", "lane_group.h", "agent_thread.h", "agent_math.h", "agent_types.h", "map_view.h")]
     deps.append(os.path.join(ROOT, "include", "navhip.h"))
     if os.path.exists(GROUP_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(GROUP_LIB) for d in deps):
         return GROUP_LIB

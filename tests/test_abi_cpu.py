@@ -469,6 +469,32 @@ def test_map_unit_holds_map_state_only_with_one_plane_table_and_one_staging_path
         assert re.search(r"^int %s\(" % entry, api, re.M), entry
 
 
+def test_agent_kernel_units_hold_their_own_kernels_and_one_unit_includes_the_group_header():
+    """The agent step's kernels live in four units: the build side of the spatial hash (spatial_kernels.hip), the cohesion
+    term (cohesion_kernels.hip), the arrival arm of the state pass (state_kernels.hip) and the step proper
+    (agent_kernels.hip).  agent_group.h defines a device variable and is included by one unit only; the state unit's
+    launcher is its own; the two scan kernels are reached from outside through nh_launch_scan, never by name."""
+    csrc = os.path.join(ROOT, "permafrost-engine_amd", "csrc")
+    units = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(".hip")}
+    headers = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(".h")}
+    home = {"spatial_kernels.hip": ("k_sp_bbox", "k_sp_count", "k_sp_scan_local", "k_sp_scan_add", "k_sp_scatter", "k_sp_place",
+                                    "k_sp_build_small"),
+            "cohesion_kernels.hip": ("k_coh_plan", "k_coh_bin", "k_coh_scatter", "k_cohesion", "k_zero_i32"),
+            "state_kernels.hip": ("k_arrived_compact", "k_state_update")}
+    for unit, kernels in home.items():
+        for k in kernels:
+            # (from __global__ to the kernel's name: attributes and the return type, no body or statement in between)
+            defined = [f for f, src in units.items() if re.search(r"__global__[^;{}]*?\b%s\s*\(" % k, src)]
+            assert defined == [unit], (k, defined)
+    including = [f for f, src in units.items() if re.search(r'#include\s+"agent_group\.h"', src)]
+    assert including == ["agent_kernels.hip"], including
+    assert not [f for f, src in headers.items() if "nh_launch_state_update" in src]
+    assert re.search(r"^static void nh_launch_state_update\(", units["state_kernels.hip"], re.M)
+    for k in ("k_sp_scan_local", "k_sp_scan_add"):
+        named = [f for f, src in {**units, **headers}.items() if k in src]
+        assert named == ["spatial_kernels.hip"], (k, named)
+
+
 def test_state_staging_tables_cover_every_array():
     """csrc/state_kernels.hip stages the input and output structs of the state half of the tick from ONE list per
     struct (sk_gate_rows, sk_state_rows, sk_aux_rows, sk_pass_out_rows, sk_settle_in_rows, sk_settle_out_rows): each

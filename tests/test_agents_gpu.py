@@ -449,6 +449,42 @@ def test_lane_grouping_carried_between_ticks_is_only_a_hint(navlib):
     shared.close()
 
 
+def test_more_than_64_flocks_step_across_a_regrouping(navlib):
+    """70 flocks of 6 on a 2 x 2-chunk map, ten ticks on ONE context.  Above 64 flocks the cohesion launch reads its plan
+    from k_coh_plan instead of working it out in every wave, and the lane regrouping that follows a tick is what the NEXT
+    tick's launch runs on.  The regrouping follows the first two steps of a flock layout and then every 8th
+    (coh_regroup_due in csrc/step_api.hip: age < 2 or age % NH_COH_REGROUP_EVERY == 0), here the 1st, 2nd and 9th of
+    the ten; its bins go through the two-pass scan the spatial hash build uses.  Every tick against the reference on the
+    same snapshot: velocities within 1e-4 relative (and bit-identical), the position accept bit of every moving agent."""
+    n, k, ticks = 420, 70, 10
+    grid, nav = cases.ref_nav_for(2, 2, seed=21)
+    world = cases.make_agents(grid, n, k, seed=13, clustered=True)
+    moving = ~np.isin(world["state"], (2, 4))
+    ctx = _upload(navlib, nav)
+    for tick in range(ticks):
+        mv, _ = cases.ref_move_for(nav, world)
+        exp_vel = mv.velocity(None)
+        vdes = mv.vdes()
+        out = ctx.agent_step(_step_arrays(world, mv, vdes))
+        err = _vel_err(out["vel_xz"][moving], exp_vel[moving])
+        assert (err <= REL_TOL).all(), (tick, int((~(err <= REL_TOL)).sum()), np.nanmax(err))
+        assert np.array_equal(out["vel_xz"][moving].view(np.uint32), exp_vel[moving].view(np.uint32)), tick
+        assert np.all(out["vel_xz"][~moving] == 0)
+        accepted = np.zeros(n, bool)
+        for uid in np.flatnonzero(moving):
+            v, pos = exp_vel[uid], world["pos_xz"][uid]
+            on_blocked = nav.position_blocked(pos)
+            accepted[uid] = (np.linalg.norm(v) > 0) and nav.position_pathable(pos + v) \
+                and (on_blocked or not nav.position_blocked(pos + v))
+        assert np.array_equal((out["status"][moving] & 1) != 0, accepted[moving]), tick
+        # the next snapshot: accepted moves, the reference's velocities
+        world["pos_xz"] = np.where(accepted[:, None], world["pos_xz"] + exp_vel, world["pos_xz"]).astype(np.float32)
+        world["vel_xz"] = exp_vel.astype(np.float32)
+    ctx.close()
+    assert moving.sum() > n // 2
+    pfref.RefMove.unload()
+
+
 def _device_snapshot(navlib, arrays):
     """(navhip_world over device copies of `arrays`, device outputs, keepalive, fetch()).  Device memory is torch's -- or,
     where the library named by NAVHIP_LIB is the host emulator, page-locked memory of the library's own (navhip_host_alloc):
