@@ -17,7 +17,8 @@ import numpy as np
 import torch
 
 from . import dist as pdist
-from . import navhip, synth
+from . import navhip, plan, synth
+from .plan import region_grid        # noqa: F401  (bench.py and the tests read it here)
 
 
 class _HostCuda:
@@ -81,15 +82,6 @@ EMULATED = os.path.basename(os.environ.get("NAVHIP_LIB", "")) == "_navhip_emu.so
 tcuda = _HostCuda if EMULATED else torch.cuda
 
 
-def region_grid(world):
-    """(rows, cols) of the region tiling for `world` ranks: cols = the smallest power of two that is
-    >= sqrt(world), rows = ceil(world / cols): 1x1, 1x2, 2x2, 2x4, 4x4."""
-    cols = 1
-    while cols * cols < world:
-        cols *= 2
-    return -(-world // cols), cols
-
-
 class NavTick:
     """World layout (weak scaling): `world` REGIONS of chunk_w x chunk_w chunks
     tiling one map (region_grid(world): 1x2, 2x2, 2x4, 4x4 ... regions; a map side is at most 64
@@ -99,7 +91,9 @@ class NavTick:
     and its `agents_per_rank` agents, flock = destination -- belongs to rank r: the agents a rank
     steps sample the fields that rank built, so the baked tiles only travel when a flock has members
     on another rank (`tile_exchange`).  The map planes and the entity snapshot are replicated; agents
-    of neighbouring regions see each other through the all-gathered snapshot."""
+    of neighbouring regions see each other through the all-gathered snapshot.  What that world is -- tiling, obstacles,
+    destinations, agents, request stream, slot tables -- is planned on the host by plan.py; this class puts it on the
+    device and enqueues the tick."""
 
     def __init__(self, chunk_w=16, fields_per_rank=64, agents_per_rank=100_000, rank=0, world=1,
                  device=0, hz=20, seed_map=1234, verbose=False, obstacles=0, move_frac=0.01,
@@ -110,272 +104,51 @@ class NavTick:
         self.rank, self.world, self.device_index = rank, world, device
         self.dev = torch.device("cpu") if EMULATED else torch.device("cuda", device)
         tcuda.set_device(self.dev)
+        t0 = time.time()
+        # ---- the plan (plan.py, host only); the two planes only the library gives come in between ---------------
+        lay = plan.layout(chunk_w, world, shared_map)
         self.W = chunk_w                            # region side in chunks
-        # shared_map (BASELINE configs[3], strong scaling): ONE chunk_w x chunk_w map for every rank;
-        # destinations and agents are split over the ranks, anywhere on the map
-        self.shared_map = bool(shared_map)
-        self.reg_rows, self.reg_cols = (1, 1) if shared_map else region_grid(world)
-        self.Wt, self.H = chunk_w * self.reg_cols, chunk_w * self.reg_rows   # whole map, in chunks
-        if max(self.Wt, self.H) > 64:
-            raise ValueError("%d regions of %d chunks do not fit a 64x64-chunk map" % (world, chunk_w))
-        self.nchunks = self.Wt * self.H
+        self.shared_map, self.reg_rows, self.reg_cols = lay.shared_map, lay.reg_rows, lay.reg_cols
+        self.Wt, self.H, self.nchunks = lay.Wt, lay.H, lay.nchunks     # whole map, in chunks
         self.K = fields_per_rank * world            # flow fields (destinations) in the whole job
         self.N = agents_per_rank * world            # agents in the whole job
         self.hz = hz
-        t0 = time.time()
-        Wt, H = self.Wt, self.H
-        rcols = chunk_w * 64                        # cell rows / columns per region
-
-        def region_cells(q):                        # (row0, row1, col0, col1) of region q, in cells
-            if self.shared_map:
-                return 0, rcols, 0, rcols
-            qr, qc = divmod(q, self.reg_cols)
-            return qr * rcols, (qr + 1) * rcols, qc * rcols, (qc + 1) * rcols
-
-        # ---- synthetic map, identical on every rank --------------------
-        grid = synth.cost_grid(Wt, H, seed=seed_map)
-        self.ctx = navhip.NavContext(Wt, H, device=device)
-        self.ctx.upload_plane(0, navhip.PLANE_COST_BASE, synth.to_chunks(grid))
-        self.ctx.upload_plane(0, navhip.PLANE_BLOCKERS, np.zeros((H, Wt, 64, 64), np.uint16))
-        self.n_obstacles = obstacles
-        blockers = None
-        if obstacles:
-            # configs[4]: dynamic obstacles (circles, radius U(2,6) wu, seed 99) dropped through the
-            # device N_BlockersIncref path; every tick `move_frac` of them move (decref + incref)
-            rng = np.random.RandomState(99)
-            cells = synth.passable_cells(grid)
-            pos = synth.cell_centre(Wt, H, *cells[rng.randint(len(cells), size=obstacles)].T)
-            circ = np.zeros(obstacles, navhip.CIRCLE_DTYPE)
-            circ["x"], circ["z"] = pos[:, 0], pos[:, 1]
-            circ["radius"] = rng.uniform(2.0, 6.0, obstacles)
-            circ["delta"] = 1
-            self._circ_host = circ.copy()       # (parity tests replay them through the reference)
-            self.ctx.N_BlockersUpdate(circ)
-            self.ctx.changed_chunks(0, clear=True)
-            blockers = synth.from_chunks(self.ctx.download_plane(0, navhip.PLANE_BLOCKERS))
-            nmove = max(1, int(round(obstacles * move_frac)))
-            moves = np.zeros((obstacle_ticks, 2 * nmove), navhip.CIRCLE_DTYPE)
-            cur = circ.copy()
-            for t in range(obstacle_ticks):
-                who = rng.choice(obstacles, nmove, replace=False)
-                moves[t, :nmove] = cur[who]
-                moves[t, :nmove]["delta"] = -1
-                npos = synth.cell_centre(Wt, H, *cells[rng.randint(len(cells), size=nmove)].T)
-                cur["x"][who], cur["z"][who] = npos[:, 0], npos[:, 1]
-                moves[t, nmove:] = cur[who]
-                moves[t, nmove:]["delta"] = 1
-            self.n_moves = 2 * nmove
-            self._moves_host = moves
-        self.ctx.relabel_local_islands(0)           # n_update_local_island_field on the device
-        liid = synth.from_chunks(self.ctx.download_plane(0, navhip.PLANE_LOCAL_ISLANDS))
-
-        # ---- destinations (cheap, all regions) and agents (replicated snapshot) ----------------
-        dests, ag_parts = [], []
-        for q in range(world):
-            r0, r1, c0, c1 = region_cells(q)
-            sub = grid[r0:r1, c0:c1]
-            d = synth.destinations(sub, fields_per_rank, seed=42 + q)
-            dests.append(d + np.array([r0, c0]))
-            a = synth.agents(grid, agents_per_rank, fields_per_rank, seed=7 + q, hz=hz, blockers=blockers,
-                             cols=(c0, c1), rows=(r0, r1), crowd_cells=crowd_cells)
-            a["flock"] = a["flock"] + q * fields_per_rank
-            ag_parts.append(a)
-        dests = np.concatenate(dests)
-        if straddle > 0 and world > 1:
-            # flocks that straddle ranks: in the last `straddle` of every rank's uid slab sit agents of the
-            # NEXT region (position and flock; the lower half of its flocks only) -- stepped here, sampling
-            # fields another rank builds
-            m = int(round(agents_per_rank * (1.0 - straddle)))
-            swapped = []
-            for q, a in enumerate(ag_parts):
-                nxt = ag_parts[(q + 1) % world]
-                take = np.zeros(agents_per_rank, bool)
-                take[m:] = (nxt["flock"][m:] % fields_per_rank) < max(1, fields_per_rank // 2)
-                swapped.append({k: (v if k == "hz" else
-                                    np.where(take.reshape((-1,) + (1,) * (np.ndim(v) - 1)), nxt[k], v))
-                                for k, v in a.items()})
-            ag_parts = swapped
-        ag = {k: (np.concatenate([a[k] for a in ag_parts]) if k != "hz" else hz) for k in ag_parts[0]}
-        # ---- request stream: region-major, destination-major inside a region -------------------
-        # tile_exchange: "auto" = only the fields some other rank samples travel (none when flocks
-        # are rank aligned, the default world; `straddle` makes some); "all" = every rank holds every
-        # tile, all-gathered every tick
-        # (SURVEY section 8(e) worst case: any agent may sample any field)
-        # solo (tests): this one process builds every region's fields and steps every agent
         self.solo = bool(solo)
-        self.tile_exchange = "all" if ((tile_exchange == "all" or solo) and world > 1) else "none"
-        # "auto": destination d (built by rank d // fields_per_rank) travels when some agent of its flock
-        # sits in another rank's uid slab
-        travels = np.zeros(self.K, bool)
-        if world > 1:
-            travels = pdist.travelling_destinations(ag["flock"], agents_per_rank, fields_per_rank, self.K)
-            if self.tile_exchange == "none" and travels.any():
-                self.tile_exchange = "auto"
-        regions = range(world) if self.tile_exchange != "none" else [rank]
-        req_parts, dest_of_req, self.req_bounds, nreq = [], [], [(0, 0)] * world, 0
-        self.xchg_bounds = [(0, 0)] * world        # the rows of a rank the others need
-        for q in regions:
-            r0, r1, c0, c1 = region_cells(q)
-            d_q = dests[q * fields_per_rank:(q + 1) * fields_per_rank] - np.array([r0, c0])
-            # the reference planner's own request stream where a fixture holds it (the single-GPU configs:
-            # tests/tools/make_requests.py), else the numpy stand-in
-            cols = synth.planner_requests(grid[r0:r1, c0:c1], d_q) if planner_requests else None
-            self.request_source = "reference planner (n_request_path) fixture" if cols is not None else \
-                "numpy stand-in (synth.whole_map_requests)"
-            if cols is None:
-                cols = synth.whole_map_requests(grid[r0:r1, c0:c1], d_q, liid[r0:r1, c0:c1])
-            n_q = len(cols["type"])
-            if self.tile_exchange == "auto":
-                # the travelling destinations' requests first: one contiguous run per rank to exchange
-                order, n_first = pdist.travel_first(np.asarray(cols["dest"]) + q * fields_per_rank, travels)
-                cols = {k: np.asarray(v)[order] for k, v in cols.items() if k in synth.REQ_FIELDS or k == "dest"}
-                self.xchg_bounds[q] = (nreq, nreq + n_first)
-            else:
-                self.xchg_bounds[q] = (nreq, nreq + n_q)
-            reqs_q = navhip.make_reqs(n_q)
-            for k in synth.REQ_FIELDS:
-                reqs_q[k] = cols[k]
-            reqs_q["chunk_r"] += r0 // 64
-            reqs_q["chunk_c"] += c0 // 64
-            portal = reqs_q["type"] == navhip.TARGET_PORTAL
-            reqs_q["next_chunk_r"][portal] += r0 // 64
-            reqs_q["next_chunk_c"][portal] += c0 // 64
-            req_parts.append(reqs_q)
-            dest_of_req.append(np.asarray(cols["dest"]) + q * fields_per_rank)
-            self.req_bounds[q] = (nreq, nreq + n_q)
-            nreq += n_q
-        reqs = np.concatenate(req_parts)
-        dest_of_req = np.concatenate(dest_of_req)
-        n_req = len(reqs)
+        # synthetic map, identical on every rank
+        self.grid = grid = synth.cost_grid(lay.Wt, lay.H, seed=seed_map)
+        self.map_cells = grid.size
+        self.n_obstacles = obstacles
         if obstacles:
-            reqs["flags"] = navhip.REQ_LIVE_IIDS | navhip.REQ_IF_CHANGED
-        # share_fields: the reference keys its field cache by N_FlowFieldID (field.c:1952) -- chunk + target, NOT
-        # the destination -- so destinations whose paths leave a chunk through the same portal share ONE field
-        # (N_FC_PutDestFFMapping maps both to it, nav.c:2008-2021), and a tick after a wholesale invalidation
-        # rebuilds every DISTINCT field once.  Identical request records are built once and every (dest, chunk)
-        # entry of the slot table points at the shared slot.  (Default off: every request is rebuilt.)
-        self.n_requests_served = n_req
-        mapped_slot = np.arange(n_req)
-        if share_fields:
-            if world != 1 or obstacles:
-                raise ValueError("share_fields: single-process worlds without moving obstacles only")
-            uniq, first, inv = np.unique(reqs, return_index=True, return_inverse=True)
-            order = np.sort(first)                       # (keep the stream's order: first occurrences)
-            rank_of = np.empty(len(first), np.int64)
-            rank_of[np.argsort(first)] = np.arange(len(first))
-            mapped_slot = rank_of[inv.reshape(-1)]
-            reqs_all, dest_all = reqs, dest_of_req
-            reqs = reqs[order]
-            dest_of_req = dest_of_req[order]
-            n_req = len(reqs)
-            self.req_bounds = [(0, n_req)]
-            self.xchg_bounds = [(0, n_req)]
+            # (_circ_host: parity tests replay the start circles through the reference)
+            self._circ_host, self._moves_host = plan.obstacle_stream(grid, lay, obstacles, move_frac, obstacle_ticks)
+            self.n_moves = self._moves_host.shape[1]
+        blockers, liid = self._make_context(grid)
+        dests, ag = plan.population(grid, lay, world, fields_per_rank, agents_per_rank, hz, blockers, crowd_cells, straddle)
+        rq = plan.request_stream(grid, lay, dests, ag["flock"], liid, rank, world, fields_per_rank, agents_per_rank,
+                                 tile_exchange, solo, planner_requests, share_fields, obstacles)
+        self.tile_exchange, self.request_source = rq.tile_exchange, rq.request_source
+        self.req_bounds, self.xchg_bounds = rq.req_bounds, rq.xchg_bounds      # (xchg: the rows of a rank the others need)
+        self.n_requests_served, self._dest_of_req = rq.n_requests_served, rq.dest_of_req
+        n_req = len(rq.reqs)
         # field slot = position in the (local) request stream
         self.req_begin, self.req_end = (0, n_req) if solo else self.req_bounds[rank]
         self.n_req_local = self.req_end - self.req_begin
         self.n_req_total = self.n_req_local * world if self.tile_exchange == "none" else n_req
-        self._dest_of_req = dest_of_req
-        slot_tbl = -np.ones((self.K, self.nchunks), np.int32)
-        if share_fields:
-            slot_tbl[dest_all, reqs_all["chunk_r"].astype(np.int64) * Wt + reqs_all["chunk_c"]] = mapped_slot
-        else:
-            slot_tbl[dest_of_req, reqs["chunk_r"].astype(np.int64) * Wt + reqs["chunk_c"]] = np.arange(n_req)
         self.agent_bounds = [pdist.slab(self.N, r, world) for r in range(world)]
-
-        offs, members = navhip.flock_csr(ag["flock"], self.K)
-        targets = synth.cell_centre(Wt, H, dests[:, 0], dests[:, 1])
         self.a0, self.a1 = (0, self.N) if solo else pdist.slab(self.N, rank, world)
-        self.grid = grid
-        self.map_cells = grid.size
-
-        # ---- device state ----------------------------------------------------------------------
-        def dev(a):
-            return torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
 
         self.tick_no = 0
         self.overlap = True
-        if obstacles:
-            self.d_moves = dev(self._moves_host.view(np.uint8).reshape(obstacle_ticks, self.n_moves, 24))
-
-        self.d_reqs = dev(reqs.view(np.uint8).reshape(n_req, 32))
-        self.pool = torch.zeros((n_req, 4096), dtype=torch.uint8, device=self.dev)
-        n = self.N
-        self.t = {
-            "pos_xz": dev(ag["pos"]), "vel_xz": dev(ag["vel"]), "radius": dev(ag["radius"]),
-            "max_speed": dev(ag["max_speed"]), "speed": dev(ag["speed"]),
-            "flags": dev(np.full(n, navhip.ENTITY_FLAG_MOVABLE, np.uint32)),
-            "state": dev(np.zeros(n, np.uint8)), "has_dest_los": dev(np.zeros(n, np.uint8)),
-            "flock": dev(ag["flock"]), "flock_target_xz": dev(targets.astype(np.float32)),
-            "flock_offsets": dev(offs), "flock_members": dev(members),
-            "flock_field_slot": dev(slot_tbl), "field_pool": self.pool,
-        }
-        self.new_pos = torch.zeros((n, 2), dtype=torch.float32, device=self.dev)
-        self.new_vel = torch.zeros((n, 2), dtype=torch.float32, device=self.dev)
-        self.status = torch.zeros(n, dtype=torch.uint8, device=self.dev)
-        self.res4 = torch.zeros((n, 4), dtype=torch.float32, device=self.dev) if world > 1 else None
-        # (parity tests: the desired direction / preferred velocity every agent was stepped with)
-        self.vdes_out = torch.zeros((n, 2), dtype=torch.float32, device=self.dev) if debug_outputs else None
-        self.vpref_out = torch.zeros((n, 2), dtype=torch.float32, device=self.dev) if debug_outputs else None
-        # host copies of what the job was built from (parity tests replay it through the reference)
-        self.host = {"reqs": reqs, "dest_of_req": dest_of_req, "slot_tbl": slot_tbl, "dests": dests,
-                     "targets": targets.astype(np.float32), "flock": ag["flock"], "flock_offsets": offs,
-                     "flock_members": members, "radius": ag["radius"], "max_speed": ag["max_speed"],
-                     "speed": ag["speed"], "liid": liid}
-        # ---- "has_dest_los computed by the reference LOS code" -----------------------
-        # los=True: the LOS fields of every (destination, chunk) the reference planner would hold -- its own
-        # N_LOSFieldCreate chain, from the fixture -- are built on the device (navhip_build_los_dev, level by level
-        # along the chain) and every agent's has_dest_los is answered per tick from them (NAVHIP_LOS_LOOKUP:
-        # N_HasDestLOS, nav.c:4026).  Built once at start-up like the reference's LOS cache (a static map).
-        # los_repair: what happens to those fields when blockers move.  None = nothing (the fields of the start-up planes
-        # answer for ever); "reference" = behind every blocker batch the fields of the changed chunks are rebuilt, each from
-        # whatever its predecessor holds (the reference's cache: fieldcache.c:526-535, nav.c:2026-2039); "downstream" = and
-        # every field built from a rebuilt one, so that the pool is the one a fresh build on the current planes gives
-        # (navhip_los_chain_*, csrc/los_chain_api.hip)
-        if los_repair not in (None, "reference", "downstream"):
-            raise ValueError("los_repair: None, 'reference' or 'downstream'")
-        self.los_repair = los_repair
-        self.los_chain = None
-        self.los_source = "has_dest_los = 0 for every agent (no LOS fields)"
-        self.n_los = 0
-        if los:
-            lc = synth.planner_los(grid, dests) if (world == 1 or shared_map) else None
-            if lc is None:
-                self.los_source = "has_dest_los = 0: no planner LOS fixture for this world"
-            else:
-                self._build_los(lc, dests, dev)
-        # the agent chain: the library's own stream (a hardware queue to itself, the same one for every context of the
-        # process -- navhip_stream_main; NAVTICK_TORCH_STREAM=1: a stream of torch's pool, as rounds 1-5 had it, for the A/B)
-        if os.environ.get("NAVTICK_TORCH_STREAM") == "1":
-            self.stream = tcuda.Stream(device=self.dev, priority=-1)
-        else:
-            self.stream = tcuda.ExternalStream(self.ctx.stream_main(), device=self.dev)
-        # multi-GPU: the slab all-gather of tick t runs on its own stream and is only awaited by the
-        # snapshot consumers of tick t+1 (spatial hash + cohesion, then the agent step); the field
-        # builds of tick t+1 do not read positions and overlap with it
-        self.pipelined = world > 1 and not solo
-        # (the library's own streams for everything beside the agent chain: each has a hardware queue to itself, on a pipe of
-        # the command processor that self.stream's queue does not sit on -- navhip_stream_beside)
-        self.comm = tcuda.ExternalStream(self.ctx.stream_beside(self.stream.cuda_stream), device=self.dev) if self.pipelined else None
-        # exchange = "navhip": the slab all-gather goes through the library's own C entry point
-        # (navhip_comm_allgather_step_dev: librccl called directly -- what a C host uses) instead of
-        # torch.distributed; rank 0's communicator id travels over the process group that launched us
-        self.exchange_mode = exchange if self.pipelined else "none"
-        if self.exchange_mode == "navhip":
-            import torch.distributed as tdist
-            box = [navhip.comm_unique_id() if rank == 0 else None]
-            tdist.broadcast_object_list(box, src=0)
-            self.ctx.comm_init(rank, world, box[0])
-            self._bounds = np.array([b for b, _ in self.agent_bounds] + [self.N], np.int32)
-        self.ev_step = tcuda.Event()
-        self.ev_comm = tcuda.Event()
-        self._comm_pending = False
-        self._stepped = False
+        self._make_device_state(rq, dests, ag, liid, debug_outputs)
+        self._make_los(los, los_repair, lay, dests)
+        self._make_streams(exchange)
         self._make_structs()
+        # ---- start-up builds ------------------------------------------------------------------------------------
         if obstacles:
             # the pool starts fully built (untimed), afterwards only changed chunks are repaired
-            full = reqs.copy()
+            full = rq.reqs.copy()
             full["flags"] = navhip.REQ_LIVE_IIDS
-            d_full = dev(full.view(np.uint8).reshape(n_req, 32))
+            d_full = self._dev(full.view(np.uint8).reshape(n_req, 32))
             self.ctx.build_fields_dev(d_full, n_req, self.pool, stream=self.stream.cuda_stream)
             self.stream.synchronize()
         # pipeline_fields: the fields tick t+1 samples are built DURING tick t, on their own stream, into
@@ -386,44 +159,154 @@ class NavTick:
         # obstacles the blocker updates of tick t+1 would race with the probes of tick t: not pipelined.)
         self.pipeline_fields = bool(pipeline_fields) and not obstacles
         if self.pipeline_fields:
-            # Where the builds of tick t+1 run inside tick t is a scheduling choice, measured (round 3, after the
-            # front of the step had become a third shorter; 20 ticks after 5 / 100 ticks, ms per tick):
-            #   configs[2] (16 384 chunk fields, 0.09 ms alone): behind the NEIGHBOUR WALK on 5 of the 8 XCDs
-            #     0.316-0.320 / 0.455-0.460 (128 ... 176 CUs all the same); on 192: 0.327 / 0.472; on all 256:
-            #     0.336 / 0.477; started with the tick on 192 (round 2's choice): 0.340 / 0.483.  The front --
-            #     spatial hash, neighbour walk: the critical path -- then only shares the chip with the cohesion
-            #     kernel, and the ClearPath phase keeps three XCDs to itself.
-            #   configs[3] (131 072 chunk fields, 0.58 ms alone -- as long as the rest of the tick): started
-            #     WITH THE TICK on ALL compute units 0.97; with the tick on 224 / 192: 1.01 / 1.08; behind the
-            #     neighbour walk on 224 / 160: 0.99 / 1.20.
-            #   configs[1] (4 096 chunk fields, 45 us): no difference (0.259-0.265).
-            ncu_all = tcuda.get_device_properties(self.dev).multi_processor_count
-            long_build = self.n_req_local >= 65536
-            ncu = int(os.environ.get("NAVTICK_FIELD_CUS", str(ncu_all if long_build else ncu_all * 5 // 8)))
-            if 0 < ncu < ncu_all:
-                self.fstream = tcuda.ExternalStream(self.ctx.stream_beside(self.stream.cuda_stream, ncu_all - ncu, ncu), device=self.dev)
-            else:
-                self.fstream = tcuda.ExternalStream(self.ctx.stream_beside(self.stream.cuda_stream), device=self.dev)
-            self.fields_after = os.environ.get("NAVTICK_FIELDS_AFTER", "start" if long_build else "neighbours")
-            # nothing wide is enqueued on self.stream between prefetch and step: the front stays on it
-            # ... and the snapshot buffers ping-pong: the one a step read is next written by the ClearPath
-            # kernels of the following step
-            self.prefetch_flags = navhip.PREFETCH_FRONT_INLINE | navhip.PREFETCH_SNAPSHOT_HELD
-            self.pool_next = torch.zeros_like(self.pool)
-            self.ev_fields, self.ev_fields_next = tcuda.Event(), tcuda.Event()
-            self.fev = []
-            if self.n_req_local:                       # the fields of tick 0 (start-up, untimed)
-                self.ctx.build_fields_dev(self.d_reqs[self.req_begin:self.req_end], self.n_req_local,
-                                          self.pool[self.req_begin:self.req_end], stream=self.stream.cuda_stream)
-            if self.tile_exchange != "none" and not self.solo:
-                with tcuda.stream(self.stream):
-                    pdist.exchange_rows(self.pool, self.xchg_bounds, self.rank, self.world)
-            self.ev_fields.record(self.stream)
-            self.stream.synchronize()
+            self._start_pipeline()
         if flow_velocities:
             self._flow_aligned_velocities()
         if not hasattr(self, "velocity_source"):
             self.velocity_source = "N(0, 0.35) per component (synth.agents)"
+        self._choose_driver(driver, serial, time_fields)
+        if verbose:
+            print("[rank %d] setup %.1fs: %d chunk-field requests (%d local), %d agents (%d local)"
+                  % (rank, time.time() - t0, n_req, self.n_req_local, self.N, self.a1 - self.a0), flush=True)
+
+    def _make_context(self, grid):
+        """The context with the map planes uploaded.  Returns the two planes of the plan that only the library gives:
+        the blocker plane behind the start circles (None without obstacles) and the local-island plane."""
+        Wt, H = self.Wt, self.H
+        self.ctx = navhip.NavContext(Wt, H, device=self.device_index)
+        self.ctx.upload_plane(0, navhip.PLANE_COST_BASE, synth.to_chunks(grid))
+        self.ctx.upload_plane(0, navhip.PLANE_BLOCKERS, np.zeros((H, Wt, 64, 64), np.uint16))
+        blockers = None
+        if self.n_obstacles:
+            self.ctx.N_BlockersUpdate(self._circ_host)
+            self.ctx.changed_chunks(0, clear=True)
+            blockers = synth.from_chunks(self.ctx.download_plane(0, navhip.PLANE_BLOCKERS))
+        self.ctx.relabel_local_islands(0)           # n_update_local_island_field on the device
+        return blockers, synth.from_chunks(self.ctx.download_plane(0, navhip.PLANE_LOCAL_ISLANDS))
+
+    def _dev(self, a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+
+    def _make_device_state(self, rq, dests, ag, liid, debug_outputs):
+        """The request stream, the move stream, the pool, the snapshot (self.t) and the step's outputs on the device;
+        self.host keeps what they were made from."""
+        dev, n, n_req = self._dev, self.N, len(rq.reqs)
+        offs, members = navhip.flock_csr(ag["flock"], self.K)
+        targets = synth.cell_centre(self.Wt, self.H, dests[:, 0], dests[:, 1])
+        if self.n_obstacles:
+            self.d_moves = dev(self._moves_host.view(np.uint8).reshape(len(self._moves_host), self.n_moves, 24))
+        self.d_reqs = dev(rq.reqs.view(np.uint8).reshape(n_req, 32))
+        self.pool = torch.zeros((n_req, 4096), dtype=torch.uint8, device=self.dev)
+        self.t = {
+            "pos_xz": dev(ag["pos"]), "vel_xz": dev(ag["vel"]), "radius": dev(ag["radius"]),
+            "max_speed": dev(ag["max_speed"]), "speed": dev(ag["speed"]),
+            "flags": dev(np.full(n, navhip.ENTITY_FLAG_MOVABLE, np.uint32)),
+            "state": dev(np.zeros(n, np.uint8)), "has_dest_los": dev(np.zeros(n, np.uint8)),
+            "flock": dev(ag["flock"]), "flock_target_xz": dev(targets.astype(np.float32)),
+            "flock_offsets": dev(offs), "flock_members": dev(members),
+            "flock_field_slot": dev(rq.slot_tbl), "field_pool": self.pool,
+        }
+        self.new_pos = torch.zeros((n, 2), dtype=torch.float32, device=self.dev)
+        self.new_vel = torch.zeros((n, 2), dtype=torch.float32, device=self.dev)
+        self.status = torch.zeros(n, dtype=torch.uint8, device=self.dev)
+        self.res4 = torch.zeros((n, 4), dtype=torch.float32, device=self.dev) if self.world > 1 else None
+        # (parity tests: the desired direction / preferred velocity every agent was stepped with)
+        self.vdes_out = torch.zeros((n, 2), dtype=torch.float32, device=self.dev) if debug_outputs else None
+        self.vpref_out = torch.zeros((n, 2), dtype=torch.float32, device=self.dev) if debug_outputs else None
+        # host copies of what the job was built from (parity tests replay it through the reference)
+        self.host = {"reqs": rq.reqs, "dest_of_req": rq.dest_of_req, "slot_tbl": rq.slot_tbl, "dests": dests,
+                     "targets": targets.astype(np.float32), "flock": ag["flock"], "flock_offsets": offs,
+                     "flock_members": members, "radius": ag["radius"], "max_speed": ag["max_speed"],
+                     "speed": ag["speed"], "liid": liid}
+
+    def _make_los(self, los, los_repair, lay, dests):
+        """"has_dest_los computed by the reference LOS code".
+        los=True: the LOS fields of every (destination, chunk) the reference planner would hold -- its own
+        N_LOSFieldCreate chain, from the fixture -- are built on the device (navhip_build_los_dev, level by level
+        along the chain) and every agent's has_dest_los is answered per tick from them (NAVHIP_LOS_LOOKUP:
+        N_HasDestLOS, nav.c:4026).  Built once at start-up like the reference's LOS cache (a static map).
+        los_repair: what happens to those fields when blockers move.  None = nothing (the fields of the start-up planes
+        answer for ever); "reference" = behind every blocker batch the fields of the changed chunks are rebuilt, each from
+        whatever its predecessor holds (the reference's cache: fieldcache.c:526-535, nav.c:2026-2039); "downstream" = and
+        every field built from a rebuilt one, so that the pool is the one a fresh build on the current planes gives
+        (navhip_los_chain_*, csrc/los_chain_api.hip)"""
+        if los_repair not in (None, "reference", "downstream"):
+            raise ValueError("los_repair: None, 'reference' or 'downstream'")
+        self.los_repair = los_repair
+        self.los_chain = None
+        self.los_source = "has_dest_los = 0 for every agent (no LOS fields)"
+        self.n_los = 0
+        if los:
+            lc = synth.planner_los(self.grid, dests) if (self.world == 1 or self.shared_map) else None
+            if lc is None:
+                self.los_source = "has_dest_los = 0: no planner LOS fixture for this world"
+            else:
+                self._build_los(plan.los_layout(lc, dests, lay, self.K))
+
+    def _make_streams(self, exchange):
+        # the agent chain: the library's own stream (a hardware queue to itself, the same one for every context of the
+        # process -- navhip_stream_main; NAVTICK_TORCH_STREAM=1: a stream of torch's pool, as rounds 1-5 had it, for the A/B)
+        if os.environ.get("NAVTICK_TORCH_STREAM") == "1":
+            self.stream = tcuda.Stream(device=self.dev, priority=-1)
+        else:
+            self.stream = tcuda.ExternalStream(self.ctx.stream_main(), device=self.dev)
+        # multi-GPU: the slab all-gather of tick t runs on its own stream and is only awaited by the
+        # snapshot consumers of tick t+1 (spatial hash + cohesion, then the agent step); the field
+        # builds of tick t+1 do not read positions and overlap with it
+        self.pipelined = self.world > 1 and not self.solo
+        # (the library's own streams for everything beside the agent chain: each has a hardware queue to itself, on a pipe of
+        # the command processor that self.stream's queue does not sit on -- navhip_stream_beside)
+        self.comm = tcuda.ExternalStream(self.ctx.stream_beside(self.stream.cuda_stream), device=self.dev) if self.pipelined else None
+        # exchange = "navhip": the slab all-gather goes through the library's own C entry point
+        # (navhip_comm_allgather_step_dev: librccl called directly -- what a C host uses) instead of
+        # torch.distributed; rank 0's communicator id travels over the process group that launched us
+        self.exchange_mode = exchange if self.pipelined else "none"
+        if self.exchange_mode == "navhip":
+            import torch.distributed as tdist
+            box = [navhip.comm_unique_id() if self.rank == 0 else None]
+            tdist.broadcast_object_list(box, src=0)
+            self.ctx.comm_init(self.rank, self.world, box[0])
+            self._bounds = np.array([b for b, _ in self.agent_bounds] + [self.N], np.int32)
+        self.ev_step = tcuda.Event()
+        self.ev_comm = tcuda.Event()
+        self._comm_pending = False
+        self._stepped = False
+
+    def _start_pipeline(self):
+        """pipeline_fields: the field stream, the second pool, and the fields of tick 0."""
+        # Where the builds of tick t+1 run inside tick t is a scheduling choice, measured (round 3, after the
+        # front of the step had become a third shorter; 20 ticks after 5 / 100 ticks, ms per tick):
+        #   configs[2] (16 384 chunk fields, 0.09 ms alone): behind the NEIGHBOUR WALK on 5 of the 8 XCDs
+        #     0.316-0.320 / 0.455-0.460 (128 ... 176 CUs all the same); on 192: 0.327 / 0.472; on all 256:
+        #     0.336 / 0.477; started with the tick on 192 (round 2's choice): 0.340 / 0.483.  The front --
+        #     spatial hash, neighbour walk: the critical path -- then only shares the chip with the cohesion
+        #     kernel, and the ClearPath phase keeps three XCDs to itself.
+        #   configs[3] (131 072 chunk fields, 0.58 ms alone -- as long as the rest of the tick): started
+        #     WITH THE TICK on ALL compute units 0.97; with the tick on 224 / 192: 1.01 / 1.08; behind the
+        #     neighbour walk on 224 / 160: 0.99 / 1.20.
+        #   configs[1] (4 096 chunk fields, 45 us): no difference (0.259-0.265).
+        ncu_all = tcuda.get_device_properties(self.dev).multi_processor_count
+        long_build = self.n_req_local >= 65536
+        ncu = int(os.environ.get("NAVTICK_FIELD_CUS", str(ncu_all if long_build else ncu_all * 5 // 8)))
+        if 0 < ncu < ncu_all:
+            self.fstream = tcuda.ExternalStream(self.ctx.stream_beside(self.stream.cuda_stream, ncu_all - ncu, ncu), device=self.dev)
+        else:
+            self.fstream = tcuda.ExternalStream(self.ctx.stream_beside(self.stream.cuda_stream), device=self.dev)
+        self.fields_after = os.environ.get("NAVTICK_FIELDS_AFTER", "start" if long_build else "neighbours")
+        # nothing wide is enqueued on self.stream between prefetch and step: the front stays on it
+        # ... and the snapshot buffers ping-pong: the one a step read is next written by the ClearPath
+        # kernels of the following step
+        self.prefetch_flags = navhip.PREFETCH_FRONT_INLINE | navhip.PREFETCH_SNAPSHOT_HELD
+        self.pool_next = torch.zeros_like(self.pool)
+        self.ev_fields, self.ev_fields_next = tcuda.Event(), tcuda.Event()
+        self.fev = []
+        self._build_fields(self.pool, self.stream)        # the fields of tick 0 (start-up, untimed)
+        with tcuda.stream(self.stream):
+            self._exchange_tiles(self.pool)
+        self.ev_fields.record(self.stream)
+        self.stream.synchronize()
+
+    def _choose_driver(self, driver, serial, time_fields):
         # driver: who enqueues a tick.  "c" = the library's own loop (navhip_tick_*, csrc/tick_api.hip: ONE call per tick,
         # the schedule below in C) -- for every world whose baked tiles do not travel; "python" = this file's compute() /
         # exchange() / advance(), the reference implementation of that schedule, which the C loop is tested against.
@@ -445,56 +328,38 @@ class NavTick:
         self.tick_every, self._tick_rec = 5, 0
         self.record = False
         self.mark_every = 20
-        if verbose:
-            print("[rank %d] setup %.1fs: %d chunk-field requests (%d local), %d agents (%d local)"
-                  % (rank, time.time() - t0, n_req, self.n_req_local, n, self.a1 - self.a0), flush=True)
 
-    def _build_los(self, lc, dests, dev):
-        """The planner's LOS chain on the device: pool slot = position in level order (level = hops from the
-        destination chunk along the chain), one navhip_build_los_dev per level, each field from its predecessor."""
-        Wt = self.Wt
-        n = len(lc["dest"])
-        key = lc["dest"] * self.nchunks + lc["chunk_r"] * Wt + lc["chunk_c"]
-        pkey = lc["dest"] * self.nchunks + (lc["chunk_r"] + lc["prev_dr"]) * Wt + (lc["chunk_c"] + lc["prev_dc"])
-        has_prev = (lc["prev_dr"] != 0) | (lc["prev_dc"] != 0)
-        index_of = {int(k): i for i, k in enumerate(key)}
-        level = np.zeros(n, np.int64)
-        prev_i = np.full(n, -1, np.int64)
-        for i in range(n):                       # (creation order: a predecessor always comes first)
-            if has_prev[i]:
-                prev_i[i] = index_of[int(pkey[i])]
-                level[i] = level[prev_i[i]] + 1
-        order = np.argsort(level, kind="stable")
-        slot_of = np.empty(n, np.int64)
-        slot_of[order] = np.arange(n)
-        reqs = np.zeros(n, navhip.LOS_REQ_DTYPE)
-        reqs["faction_id"] = navhip.FACTION_ID_NONE
-        reqs["chunk_r"], reqs["chunk_c"] = lc["chunk_r"][order], lc["chunk_c"][order]
-        d = lc["dest"][order]
-        reqs["target_chunk_r"], reqs["target_chunk_c"] = dests[d, 0] // 64, dests[d, 1] // 64
-        reqs["target_tile_r"], reqs["target_tile_c"] = dests[d, 0] % 64, dests[d, 1] % 64
-        reqs["prev_dr"], reqs["prev_dc"] = lc["prev_dr"][order], lc["prev_dc"][order]
-        prev_slot = np.where(prev_i[order] >= 0, slot_of[np.maximum(prev_i[order], 0)], 0)
-        d_reqs = dev(reqs.view(np.uint8).reshape(n, 16))
-        d_prev_slot = dev(prev_slot)
+    def _build_fields(self, pool, stream):
+        """This rank's slice of the request stream into its rows of `pool`, on `stream`."""
+        if self.n_req_local:
+            self.ctx.build_fields_dev(self.d_reqs[self.req_begin:self.req_end], self.n_req_local,
+                                      pool[self.req_begin:self.req_end], stream=stream.cuda_stream)
+
+    def _exchange_tiles(self, pool):
+        """The tile rows of `pool` that travel, to every rank (on torch's current stream)."""
+        if self.tile_exchange != "none" and not self.solo:
+            pdist.exchange_rows(pool, self.xchg_bounds, self.rank, self.world)
+
+    def _build_los(self, ll):
+        """The planner's LOS chain on the device, laid out by plan.los_layout: one navhip_build_los_dev per level, each
+        field from its predecessor."""
+        n = len(ll.reqs)
+        d_reqs = self._dev(ll.reqs.view(np.uint8).reshape(n, 16))
+        d_prev_slot = self._dev(ll.prev_slot)
         self.los_pool = torch.zeros((n, 4096), dtype=torch.uint8, device=self.dev)
-        lv = level[order]
-        bounds = np.searchsorted(lv, np.arange(lv.max() + 2))
-        self._los_build_args = (d_reqs, d_prev_slot, bounds)
+        self._los_build_args = (d_reqs, d_prev_slot, ll.bounds)
         self._build_los_pool(self.los_pool)
-        tbl = -np.ones((self.K, self.nchunks), np.int32)
-        tbl[lc["dest"], lc["chunk_r"] * Wt + lc["chunk_c"]] = slot_of
         self.t["los_pool"] = self.los_pool
-        self.t["flock_los_slot"] = dev(tbl)
+        self.t["flock_los_slot"] = self._dev(ll.slot_tbl)
         self.t["has_dest_los"] = torch.full((self.N,), navhip.LOS_LOOKUP, dtype=torch.uint8, device=self.dev)
-        self.host["los"] = {"reqs": reqs, "slot_tbl": tbl, "levels": len(bounds) - 1, "prev_slot": prev_slot,
-                            "level": lv}
+        levels = len(ll.bounds) - 1
+        self.host["los"] = {"reqs": ll.reqs, "slot_tbl": ll.slot_tbl, "levels": levels, "prev_slot": ll.prev_slot,
+                            "level": ll.level}
         self.n_los = n
         self.los_source = ("device lookup (NAVHIP_LOS_LOOKUP) in %d LOS fields built by navhip_build_los from the "
-                           "reference planner's N_LOSFieldCreate chain (fixture), %d levels" % (n, len(bounds) - 1))
+                           "reference planner's N_LOSFieldCreate chain (fixture), %d levels" % (n, levels))
         if self.los_repair is not None:
-            chain_prev = np.where(prev_i[order] >= 0, prev_slot, -1).astype(np.int32)
-            self.los_chain = self.ctx.los_chain_create(reqs, chain_prev, self.los_pool)
+            self.los_chain = self.ctx.los_chain_create(ll.reqs, ll.chain_prev, self.los_pool)
             self.los_flags = navhip.LOS_REFRESH_DOWNSTREAM if self.los_repair == "downstream" else 0
             self.los_source += ("; kept current behind every blocker batch by navhip_los_chain_refresh (%s)"
                                 % ("the changed chunks' fields and every field built from them" if self.los_flags else
@@ -527,9 +392,8 @@ class NavTick:
         keep = self.vdes_out, self.vpref_out
         self.vdes_out = torch.zeros((n, 2), dtype=torch.float32, device=self.dev)
         self.vpref_out = torch.zeros((n, 2), dtype=torch.float32, device=self.dev)
-        if not self.pipeline_fields and self.n_req_local and not self.n_obstacles:
-            self.ctx.build_fields_dev(self.d_reqs[self.req_begin:self.req_end], self.n_req_local,
-                                      self.pool[self.req_begin:self.req_end], stream=self.stream.cuda_stream)
+        if not self.pipeline_fields and not self.n_obstacles:
+            self._build_fields(self.pool, self.stream)
         self._make_structs()
         wb, we = self.world_s.work_begin, self.world_s.work_end
         self.world_s.work_begin, self.world_s.work_end = 0, n          # (every rank samples every agent: replicated)
@@ -642,13 +506,21 @@ class NavTick:
             T.advance()
         else:
             T.run(1)
-        # (the Python view of the ping-pong, without rebuilding the structs: the C tick has its own two)
+        # the Python view of the ping-pong; where it differs from advance():
+        #   the pools swap only when the C tick builds ahead (on one stream it builds in place: tick_api.hip, `ahead`)
+        #   ev_fields is not swapped: only the Python schedule waits for it, and _c_tick_drop records it afresh
+        #   no _make_structs: the C tick holds its own two sets
+        self._swap_buffers(self.pipeline_fields and not self.serial)
+        self.tick_no += 1
+
+    def _swap_buffers(self, pools):
+        """Ping-pong the snapshot: what the step wrote is the next tick's positions and velocities; `pools`: and the
+        pool built ahead is the one the next tick samples."""
         self.t["pos_xz"], self.new_pos = self.new_pos, self.t["pos_xz"]
         self.t["vel_xz"], self.new_vel = self.new_vel, self.t["vel_xz"]
-        if self.pipeline_fields and not self.serial:
+        if pools:
             self.pool, self.pool_next = self.pool_next, self.pool
             self.t["field_pool"] = self.pool
-        self.tick_no += 1
 
     def step(self):
         """One tick, asynchronous on self.stream."""
@@ -691,14 +563,11 @@ class NavTick:
                 if self.los_chain is not None:
                     self._los_refresh(s.cuda_stream)
             marks.append(self._mark("fields"))
-            if self.n_req_local:
-                self.ctx.build_fields_dev(self.d_reqs[self.req_begin:self.req_end], self.n_req_local,
-                                          self.pool[self.req_begin:self.req_end], stream=s.cuda_stream)
+            self._build_fields(self.pool, s)
             if self.n_obstacles:
                 self.ctx.clear_changed(stream=s.cuda_stream)
             marks.append(self._mark("gather_tiles"))
-            if self.tile_exchange != "none" and not self.solo:
-                pdist.exchange_rows(self.pool, self.xchg_bounds, self.rank, self.world)
+            self._exchange_tiles(self.pool)
             marks.append(self._mark("agents"))
             if self._comm_pending:
                 s.wait_event(self.ev_comm)            # the other ranks' rows of the snapshot
@@ -746,14 +615,11 @@ class NavTick:
             if timed:
                 e0 = tcuda.Event(enable_timing=True)
                 e0.record(f)
-            if self.n_req_local:
-                self.ctx.build_fields_dev(self.d_reqs[self.req_begin:self.req_end], self.n_req_local,
-                                          self.pool_next[self.req_begin:self.req_end], stream=f.cuda_stream)
+            self._build_fields(self.pool_next, f)
             if timed:
                 e1 = tcuda.Event(enable_timing=True)
                 e1.record(f)
-            if self.tile_exchange != "none" and not self.solo:
-                pdist.exchange_rows(self.pool_next, self.xchg_bounds, self.rank, self.world)
+            self._exchange_tiles(self.pool_next)
             if timed:
                 e2 = tcuda.Event(enable_timing=True)
                 e2.record(f)
@@ -793,12 +659,9 @@ class NavTick:
         """Advance the snapshot: ping-pong the position / velocity buffers."""
         with tcuda.stream(self.stream):
             self._marks.append(self._mark("end"))
-            self.t["pos_xz"], self.new_pos = self.new_pos, self.t["pos_xz"]
-            self.t["vel_xz"], self.new_vel = self.new_vel, self.t["vel_xz"]
+            self._swap_buffers(self.pipeline_fields)
             if self.pipeline_fields:
-                self.pool, self.pool_next = self.pool_next, self.pool
                 self.ev_fields, self.ev_fields_next = self.ev_fields_next, self.ev_fields
-                self.t["field_pool"] = self.pool
             self._make_structs()
         if self.record and self._marks and self._marks[0] is not None:
             self.ev.append(self._marks)

@@ -39,7 +39,7 @@ def test_request_slices_follow_destinations():
 
 
 def test_auto_tile_exchange_plan():
-    """tile_exchange="auto" (tick.NavTick): which destinations' tiles travel, and the request order that
+    """tile_exchange="auto" (plan.request_stream): which destinations' tiles travel, and the request order that
     makes them one contiguous run per rank."""
     from permafrost_engine_amd import dist as pdist
     apr, fpr, world = 10, 3, 2
@@ -68,17 +68,20 @@ def _worker(rank, world, port, n_dests, n_agents, q):
         sys.path.insert(0, ROOT)
         os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
                           WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
-        from permafrost_engine_amd import dist as pdist, synth
+        from permafrost_engine_amd import dist as pdist, plan, synth
         from tests import cases
         r, w, _ = pdist.init(backend="gloo")
         assert (r, w) == (rank, world)
 
-        # identical synthetic job on every rank (tick.NavTick.__init__)
+        # identical synthetic job on every rank, planned as tick.NavTick plans it (plan.py): ONE region whose stand-in
+        # request stream (destination-major: the order the slices below rest on) is split over the ranks by destination
         grid = synth.cost_grid(2, 2, seed=5)
-        liid = synth.local_islands(grid)
         dests = synth.destinations(grid, n_dests, seed=42)
-        cols = synth.whole_map_requests(grid, dests, liid)
+        rq = plan.request_stream(grid, plan.layout(2, 1), dests, None, synth.local_islands(grid), 0, 1, n_dests, n_agents,
+                                 planner_requests=False)
+        cols = dict({k: rq.reqs[k].astype(np.int64) for k in synth.REQ_FIELDS}, dest=rq.dest_of_req)
         n_req = len(cols["type"])
+        assert n_req > 0 and (np.diff(cols["dest"]) >= 0).all()
         oracle = cases.Oracle(grid)
         full_dirs = oracle.fields(cols)                           # single-process answer
 
@@ -141,7 +144,7 @@ def test_two_rank_gloo_tick_exchange(n_dests, n_agents):
 
 
 def test_region_agents_stay_in_their_columns():
-    """tick.NavTick's weak-scaling world: region q's agents are drawn from the passable cells of the
+    """The weak-scaling world of plan.population: region q's agents are drawn from the passable cells of the
     global columns [q*rcols, (q+1)*rcols); the unrestricted call is unchanged (world == 1)."""
     from permafrost_engine_amd import synth
     g = synth.cost_grid(4, 2, seed=1234)
