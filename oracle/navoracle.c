@@ -580,6 +580,7 @@ int no_build_region_fields(const no_map *m, const navhip_region_req *reqs, int n
  * wavefront depends on this exact pop order among equal priorities. */
 typedef struct { float prio; int cell; } rpq_node;
 typedef struct { rpq_node nodes[CELLS * 2 + 2]; int size; } rpq_t;
+static __thread int s_los_heap_peak;
 
 static void rpq_push(rpq_t *q, float prio, int cell)
 {
@@ -592,6 +593,15 @@ static void rpq_push(rpq_t *q, float prio, int cell)
     q->nodes[curr].prio = prio;
     q->nodes[curr].cell = cell;
     q->size++;
+    if(q->size > s_los_heap_peak) s_los_heap_peak = q->size;
+}
+
+/* the most nodes the heap of any LOS field held since the last reset (tests size the device heap's first launch by it) */
+int no_los_heap_peak(int reset)
+{
+    int v = s_los_heap_peak;
+    if(reset) s_los_heap_peak = 0;
+    return v;
 }
 
 static int rpq_pop(rpq_t *q)

@@ -111,6 +111,7 @@ def lib():
                                              C.c_void_p, C.c_size_t]
         L.no_build_los.argtypes = [C.POINTER(Map), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_float, C.c_float]
+        L.no_los_heap_peak.argtypes = [C.c_int]
         L.no_field_bench.restype = C.c_double
         L.no_field_bench.argtypes = [C.POINTER(Map), C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.no_agent_bench.restype = C.c_double
@@ -235,6 +236,11 @@ class OracleNav:
         if rc:
             raise ValueError("no_build_los: bad request")
         return out
+
+    @staticmethod
+    def los_heap_peak(reset=True):
+        """The most nodes the wavefront heap of any build_los field held on this thread since the last reset."""
+        return int(lib().no_los_heap_peak(int(reset)))
 
     def field_bench(self, reqs, reps=1, nthreads=1):
         reqs = np.ascontiguousarray(reqs, FIELD_REQ_DTYPE)

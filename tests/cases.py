@@ -705,3 +705,36 @@ def spatial_cases():
     out["ragged_small"] = (b,) + _sp_world(b, 700, 23, [rng.normal([1180.0, 300.0], 15.0, (150, 2))])
     _SPATIAL_CASES = out
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# chunk fields on deep, structured chunks (tests/field_shapes.py: the shapes and a numpy model of the build)
+# ---------------------------------------------------------------------------------------------
+_FIELD_SHAPE_CASES = None
+
+
+def field_shape_cases():
+    """Hand-drawn maps for the chunk-field kernels: {name: field_shapes.ShapeCase}, deterministic and built once.  Maps of
+    2 x 2 or 3 x 2 chunks whose shape chunk is never chunk (0, 0): serpentines (2 079 levels) and a spiral, serpentine
+    pieces that end exactly at L = 1 2 3 7 8 9 255 256 257 511 512 1023 1024 2047 2048 in one batch, halves joined in one
+    cell across columns 31|32 and rows 15|16, 31|32, 47|48, rim corridors, a checkerboard, a staircase, pinwheels in four
+    rotations (a diagonal that was not admitted into the minimum wins by priority), degenerate chunks, hand-made portals
+    through all four edges, costed variants for the generic kernel -- every request a second time in place.  Each case
+    carries the premise it has to meet on the model's output (field_shapes.check_premises)."""
+    global _FIELD_SHAPE_CASES
+    if _FIELD_SHAPE_CASES is None:
+        from tests import field_shapes
+        _FIELD_SHAPE_CASES = {c.name: c for c in field_shapes.build_cases()}
+    return _FIELD_SHAPE_CASES
+
+
+FIELD_SHAPE_NAMES = ("deep_serpentine", "deep_spiral", "depth_boundaries", "corner_blocks", "seams_and_rims", "checkerboard_and_staircase",
+                     "pinwheels", "pinwheels_islands_and_blockers", "degenerate", "portals", "costed", "mixed_unit_and_costed")
+
+
+def shape_oracle(case):
+    """The C restatement's (dirs, integ) for every request of a shape case, computed once."""
+    if getattr(case, "_oracle", None) is None:
+        onav = navoracle.OracleNav(case.cost, case.blockers_plane(), case.li)
+        case._oracle = onav.build_fields(case.records(navoracle.FIELD_REQ_DTYPE), inout=case.before, want_integ=True)
+    return case._oracle

@@ -39,6 +39,7 @@ SELECTION = [
     "tests/test_tick_gpu.py",          # the whole tick behind one call (navhip_tick_run) against tick.py's schedule
     "tests/test_spatial_gpu.py",       # the spatial index over grid shapes, both builds and every query-pass shape
     "tests/test_planes_gpu.py",        # plane and chunk uploads of two layers, the derived masks behind them, the refusals
+    "tests/test_field_shapes_gpu.py",  # chunk fields 2 079 levels deep, every depth boundary, the diagonal rule; region and LOS fields on the shapes
 ]
 # (agents: the tests that need torch.cuda, and the ones that take more than ~10 s each on the emulator)
 DESELECT = ["test_prefetch_overlap_gives_identical_results", "test_shared_chunk_fields_give_identical_results",
@@ -101,7 +102,7 @@ def test_gpu_parity_tests_pass_on_the_emulated_library(strict):
     assert r.returncode == 0, tail
     last = r.stdout.strip().splitlines()[-1]
     assert " passed" in last and "failed" not in last and "error" not in last, tail
-    assert int(last.split(" passed")[0].split()[-1]) >= (84 if strict else 13), tail          # (the selection really ran)
+    assert int(last.split(" passed")[0].split()[-1]) >= (118 if strict else 13), tail          # (the selection really ran)
 
 
 def test_reference_binding_drives_the_emulated_library():

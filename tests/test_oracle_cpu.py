@@ -446,3 +446,73 @@ def test_non_square_map_restatement_matches_reference(w, h):
     moving = ~np.isin(world["state"], (2, 4))
     assert np.array_equal(out["vel_xz"][moving].view(np.uint32), exp_vel[moving].view(np.uint32))
     pfref.RefMove.unload()
+
+
+# ---------------------------------------------------------------------------------------------
+# chunk fields on deep, structured chunks (cases.field_shape_cases)
+# ---------------------------------------------------------------------------------------------
+# Hand-made portal requests the harness's pfref_field_update refuses: it looks the two portals up among the portals of
+# the reference's OWN portal build (pfref_make_target), and these are cut differently -- a sub-range of a real portal, a
+# facing range that is not the one the real portal connects to.  For them the reference still runs, through
+# pfref_field_update_many (free-standing portal records; directions only, no existing field), and the in-place copies
+# stay against the restatement and the model alone.
+SHAPE_PORTALS_NOT_TAKEN = {
+    "portals": [2, 4, 5, 6, 7, 9, 10, 11, 12],
+    "mixed_unit_and_costed": [7, 8],
+}
+
+
+def test_field_shape_cases_meet_their_premises():
+    """Every shape case is what it claims to be, from the numpy model alone (field_shapes.check_premises: depth, populated
+    planes, winners of the diagonal rule, bridges, seed counts); over all cases every depth boundary is in one batch, all
+    eight directions and NONE occur, and some in-place field keeps bytes of its existing field."""
+    from tests import field_shapes as fs
+    all_cases = [cases.field_shape_cases()[n] for n in cases.FIELD_SHAPE_NAMES]
+    assert len(all_cases) == len(cases.field_shape_cases())
+    for c in all_cases:
+        fs.check_premises(c)
+        assert c.h * c.w <= 6 and (c.cost[0, 0] == 1).all() and len(c.reqs) <= 64
+    assert fs.directions_seen(all_cases) == set(range(9))
+    assert {(c.h, c.w) for c in all_cases} == {(2, 2), (2, 3)}
+    depth = cases.field_shape_cases()["depth_boundaries"]
+    assert sorted(set(depth.premise["levels"])) == list(fs.DEPTH_BOUNDARIES)
+    assert max(cases.field_shape_cases()["deep_serpentine"].premise["levels"]) == fs.SERPENTINE_DEPTH
+    some_inplace_keep = any((c.model()[0][len(c.reqs) // 2:] == c.before[len(c.reqs) // 2:]).any() for c in all_cases)
+    assert some_inplace_keep
+
+
+@needs_ref
+@pytest.mark.parametrize("name", cases.FIELD_SHAPE_NAMES)
+def test_field_shape_cases_restatement_and_model_match_reference(name):
+    """The two expected values of tests/test_field_shapes_gpu.py -- the C restatement and the numpy model -- against the
+    reference's own N_FlowFieldUpdate on every request of every shape case: directions and integration values, bit for
+    bit.  Island ids are read from the reference's own labelling (the cells they name are the case's)."""
+    from tests import field_shapes as fs
+    case = cases.field_shape_cases()[name]
+    fs.check_premises(case)
+    nav = pfref.RefNav(case.cost)
+    if case.blockers is not None:
+        nav.set_blockers(case.blockers)
+    li = nav.plane(pfref.PLANE_LOCAL_ISLANDS)
+    assert np.array_equal(li == 0xFFFF, case.li == 0xFFFF)
+    reqs = case.records(pfref.FIELD_REQ_DTYPE, li=li)
+    o_dirs, o_integ = cases.shape_oracle(case)
+    m_dirs, m_integ, _ = case.model()
+    assert np.array_equal(o_dirs, m_dirs) and np.array_equal(o_integ, m_integ)
+    n_first = len(reqs) // 2                      # (the second half: the same requests in place)
+    not_taken = []
+    for i in range(len(reqs)):
+        try:
+            d, g = nav.field_update(reqs[i], inout=case.before[i] if reqs[i]["inout"] else None, want_integ=True)
+        except ValueError:
+            if i < n_first:
+                not_taken.append(i)
+                d, g = nav.field_update_many(reqs[i:i + 1], nthreads=1)[0], None
+            else:
+                assert i - n_first in not_taken
+                continue
+        assert np.array_equal(d, m_dirs[i]), (name, i, case.reqs[i])
+        if g is not None:
+            assert np.array_equal(g, m_integ[i]), (name, i, case.reqs[i])
+    assert not_taken == SHAPE_PORTALS_NOT_TAKEN.get(name, []), not_taken
+    nav.close()
