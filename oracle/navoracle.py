@@ -68,7 +68,9 @@ class World(C.Structure):
         # paths are checked against the reference build itself)
         ("arrival_sink_xz", C.c_void_p), ("arrival_flags", C.c_void_p),
         ("los_pool", C.c_void_p), ("flock_los_slot", C.c_void_p), ("los_pos_xz", C.c_void_p),
-        ("n_los_slots", C.c_int32), ("static_epoch", C.c_uint32)]
+        ("n_los_slots", C.c_int32), ("static_epoch", C.c_uint32),
+        # region-field inputs: not modelled either (NULL / 0), declared so that the object has the size of navhip_world
+        ("region_row", C.c_void_p), ("region_field_slot", C.c_void_p), ("n_region_rows", C.c_int32)]
 
 
 class StepOut(C.Structure):

@@ -40,38 +40,52 @@ def test_header_symbols_exported_and_bound(navlib):
     assert not extra, "exported but not declared in include/navhip.h: %s" % extra
 
 
+def _header_records():
+    """{C type name: member names in order} of every record include/navhip.h defines."""
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    out = {}
+    for m in re.finditer(r"typedef struct (navhip_\w+) \{(.*?)\} \1;", src, re.S):
+        decls = [d for d in m.group(2).split(";") if d.strip()]
+        out[m.group(1)] = [re.search(r"(\w+)\s*$", part).group(1) for d in decls for part in d.split(",")]
+    return out
+
+
+def _mirror_members(rec):
+    """[(C member designator, offset)] of a record of navhip.RECORDS: every member, those of nested structures included."""
+    if isinstance(rec, np.dtype):
+        return [(name, rec.fields[name][1]) for name in rec.names]
+    out, todo = [], [("", 0, rec)]
+    while todo:
+        prefix, base, cls = todo.pop()
+        for name, typ in cls._fields_:
+            off = base + getattr(cls, name).offset
+            out.append((prefix + name, off))
+            if issubclass(typ, C.Structure):
+                todo.append((prefix + name + ".", off, typ))
+    return out
+
+
 def test_header_is_plain_c_and_layouts_match(navlib, tmp_path):
     """The header must compile as C99 (the reference's host language) and the PODs crossing the
-    boundary must have the sizes/offsets the Python mirror uses."""
+    boundary must have the sizes/offsets the Python mirror uses: every record of navhip.RECORDS, every member."""
+    from oracle import navoracle
+    header = _header_records()
+    # the mirror names every record the header defines (navhip_counters crosses as COUNTER_NAMES), member for member
+    assert sorted(navlib.RECORDS) == sorted(set(header) - {"navhip_counters"})
+    for cname, rec in navlib.RECORDS.items():
+        mine = list(rec.names) if isinstance(rec, np.dtype) else [f[0] for f in rec._fields_]
+        assert mine == header[cname], cname
+    assert list(navlib.COUNTER_NAMES) == header["navhip_counters"]
+    lines = ['printf("sizeof.%s %%zu\\n", sizeof(%s));' % (c, c) for c in header]
+    lines += ["P(%s, %s);" % (c, f) for c, rec in navlib.RECORDS.items() for f, _ in _mirror_members(rec)]
     prog = tmp_path / "layout.c"
-    prog.write_text(r'''
+    prog.write_text('''
 #include <stdio.h>
 #include <stddef.h>
 #include "navhip.h"
-#define P(T, f) printf(#T "." #f " %zu\n", offsetof(T, f))
+#define P(T, f) printf(#T "." #f " %zu\\n", offsetof(T, f))
 int main(void){
-    printf("sizeof.navhip_field_req %zu\n", sizeof(navhip_field_req));
-    printf("sizeof.navhip_world %zu\n", sizeof(navhip_world));
-    printf("sizeof.navhip_step_out %zu\n", sizeof(navhip_step_out));
-    printf("sizeof.navhip_circle %zu\n", sizeof(navhip_circle));
-    printf("sizeof.navhip_gate_in %zu\n", sizeof(navhip_gate_in));
-    printf("sizeof.navhip_arrival_zone %zu\n", sizeof(navhip_arrival_zone));
-    printf("sizeof.navhip_settle_in %zu\n", sizeof(navhip_settle_in));
-    printf("sizeof.navhip_settle_out %zu\n", sizeof(navhip_settle_out));
-    printf("sizeof.navhip_state_aux_in %zu\n", sizeof(navhip_state_aux_in));
-    printf("sizeof.navhip_state_pass_in %zu\n", sizeof(navhip_state_pass_in));
-    printf("sizeof.navhip_state_pass_out %zu\n", sizeof(navhip_state_pass_out));
-    P(navhip_state_pass_in, state); P(navhip_state_pass_in, aux);
-    P(navhip_state_aux_in, ent_rot); P(navhip_state_aux_in, range_tiles); P(navhip_state_aux_in, n_range_rows);
-    P(navhip_arrival_zone, radius); P(navhip_arrival_zone, key_end);
-    P(navhip_settle_in, zones); P(navhip_settle_in, uid); P(navhip_settle_in, stuck);
-    P(navhip_circle, radius); P(navhip_circle, faction_id); P(navhip_circle, delta);
-    P(navhip_field_req, enemies); P(navhip_field_req, chunk_r); P(navhip_field_req, tile_r);
-    P(navhip_field_req, port_r0); P(navhip_field_req, next_r0); P(navhip_field_req, next_chunk_r);
-    P(navhip_field_req, port_iid); P(navhip_field_req, next_iid);
-    P(navhip_world, pos_xz); P(navhip_world, vdes_xz); P(navhip_world, field_pool);
-    P(navhip_world, map_pos_x); P(navhip_world, grid_xmin); P(navhip_world, work_begin);
-    P(navhip_step_out, status);
+    ''' + "\n    ".join(lines) + '''
     return 0;
 }''')
     exe = tmp_path / "layout"
@@ -79,32 +93,19 @@ int main(void){
                            os.path.join(ROOT, "include"), str(prog), "-o", str(exe)])
     got = dict(l.split() for l in subprocess.check_output([str(exe)], text=True).splitlines())
     got = {k: int(v) for k, v in got.items()}
-    dt = navlib.FIELD_REQ_DTYPE
-    assert got["sizeof.navhip_field_req"] == dt.itemsize == 32
-    for f in ("enemies", "chunk_r", "tile_r", "port_r0", "next_r0", "next_chunk_r", "port_iid",
-              "next_iid"):
-        assert got["navhip_field_req." + f] == dt.fields[f][1], f
-    assert got["sizeof.navhip_world"] == C.sizeof(navlib.World)
-    assert got["sizeof.navhip_step_out"] == C.sizeof(navlib.StepOut)
+    for cname, rec in navlib.RECORDS.items():
+        assert got["sizeof." + cname] == (rec.itemsize if isinstance(rec, np.dtype) else C.sizeof(rec)), cname
+        for f, off in _mirror_members(rec):
+            assert got[cname + "." + f] == off, (cname, f)
+    assert got["sizeof.navhip_field_req"] == navlib.FIELD_REQ_DTYPE.itemsize == 32
     assert got["sizeof.navhip_circle"] == navlib.CIRCLE_DTYPE.itemsize == 24
-    for f in ("radius", "faction_id", "delta"):
-        assert got["navhip_circle." + f] == navlib.CIRCLE_DTYPE.fields[f][1], f
-    for f in ("pos_xz", "vdes_xz", "field_pool", "map_pos_x", "grid_xmin", "work_begin"):
-        assert got["navhip_world." + f] == getattr(navlib.World, f).offset, f
-    assert got["navhip_step_out.status"] == navlib.StepOut.status.offset
-    for name, cls in (("gate_in", navlib.GateIn), ("arrival_zone", navlib.ArrivalZone), ("settle_in", navlib.SettleIn),
-                      ("settle_out", navlib.SettleOut), ("state_aux_in", navlib.StateAuxIn),
-                      ("state_pass_in", navlib.StatePassIn), ("state_pass_out", navlib.StatePassOut)):
-        assert got["sizeof.navhip_" + name] == C.sizeof(cls), name
-    assert got["sizeof.navhip_arrival_zone"] == 48
-    for f in ("radius", "key_end"):
-        assert got["navhip_arrival_zone." + f] == getattr(navlib.ArrivalZone, f).offset, f
-    for f in ("zones", "uid", "stuck"):
-        assert got["navhip_settle_in." + f] == getattr(navlib.SettleIn, f).offset, f
-    for f in ("state", "aux"):
-        assert got["navhip_state_pass_in." + f] == getattr(navlib.StatePassIn, f).offset, f
-    for f in ("ent_rot", "range_tiles", "n_range_rows"):
-        assert got["navhip_state_aux_in." + f] == getattr(navlib.StateAuxIn, f).offset, f
+    assert got["sizeof.navhip_arrival_zone"] == C.sizeof(navlib.ArrivalZone) == 48
+    assert got["sizeof.navhip_counters"] == 8 * len(navlib.COUNTER_NAMES)
+    # the oracle restates the records it passes on its own (it does not import the product package)
+    assert C.sizeof(navoracle.World) == got["sizeof.navhip_world"]
+    assert C.sizeof(navoracle.StepOut) == got["sizeof.navhip_step_out"]
+    for name in ("FIELD_REQ_DTYPE", "CIRCLE_DTYPE", "LOS_REQ_DTYPE", "REGION_REQ_DTYPE"):
+        assert getattr(navoracle, name) == getattr(navlib, name), name
 
 
 def _ff_id_expected(r):
