@@ -74,7 +74,11 @@ enum {
                                     portal target, the next chunk) is flagged changed by the blocker
                                     updates since the last navhip_clear_changed; otherwise the slot
                                     is left untouched (the cached field stays valid, the device image
-                                    of N_ApplyDeferredInvalidations, nav.c:2208) */
+                                    of N_ApplyDeferredInvalidations, nav.c:2208).  A request with a
+                                    faction is also built when the per-faction flags of its own chunk
+                                    (navhip_faction_changed_chunks) name a faction that is not among
+                                    its enemies: more than the reference's dirty set (nav.c:1036),
+                                    which knows no faction and leaves such a field stale */
 #define NAVHIP_REQ_LIVE_IIDS  0x4 /* portal targets: re-read port_iid / next_iid on the device from the
                                     CURRENT local_islands plane -- the label of the first tile of the
                                     port / next portal that has one (a blocker leaves ISLAND_NONE); a
@@ -193,6 +197,16 @@ int  navhip_relabel_local_islands(navhip_ctx *ctx, int layer);
 /* The changed-chunk flags of one layer ([chunk_h*chunk_w] bytes, 1 = passability changed);
  * clear != 0 resets them afterwards. */
 int  navhip_changed_chunks(navhip_ctx *ctx, int layer, uint8_t *host_flags, int clear);
+/* The per-faction changed flags of one layer ([chunk_h*chunk_w] uint16_t): bit f = since the last navhip_clear_changed
+ * a blocker update changed WHICH tiles of the chunk faction f holds (factions[f] != 0, nav_chunk.factions
+ * nav_data.h:141) -- what an attacking path that is no enemy of f may cross (field_tile_passable_no_enemies,
+ * field.c:179-201) -- whether or not the passability without a faction, and with it the flag above, changed.  Masks, not
+ * counters: a second unit on tiles the faction holds already raises nothing, nor do an incref and a decref of one
+ * circle in one batch.  Raised by navhip_blockers_circles[_dev] only: uploads raise neither kind of flag.  All zero for
+ * a layer without a factions plane.  Runs on the context's stream like navhip_changed_chunks; clear != 0 resets these
+ * flags afterwards (and only these: navhip_changed_chunks(.., 1) resets only its own). */
+int  navhip_faction_changed_chunks(navhip_ctx *ctx, int layer, uint16_t *host_flags, int clear);
+/* Resets both kinds of flags of every layer, asynchronously on `stream` (NULL: the context's). */
 int  navhip_clear_changed(navhip_ctx *ctx, void *stream);
 
 /* ---- chunk flow fields ---------------------------------------- */
@@ -277,21 +291,24 @@ int  navhip_build_los_dev(navhip_ctx *ctx, const navhip_los_req *dev_reqs, int n
 /* A resident LOS chain: the LOS fields of a fixed set of (destination, chunk) slots, kept current while blockers move.
  * The reference drops the LOS fields of a dirty chunk together with its flow fields (fieldcache.c:213-227, 526-535) and
  * rebuilds a missing one from the cached field of the chunk before it on the path (nav.c:2026-2039, 4042-4047); a chain
- * does both on the device, behind navhip_blockers_circles[_dev] and from the changed-chunk flags those leave.
+ * does both on the device, behind navhip_blockers_circles[_dev] and from the changed-chunk flags those leave.  A slot
+ * may carry a faction (an attacking path): it follows the per-faction flags (navhip_faction_changed_chunks) as well.
  *   reqs, prev_slot  HOST arrays of n entries (copied).  Slot i is field i of dev_pool; prev_slot[i] is the slot of the
  *                    field request i continues (its prev_los), -1 for the destination chunk's own field.  Slots are
  *                    in LEVEL order (level = 0 without a predecessor, else the predecessor's + 1, non-decreasing).
  *   dev_pool         DEVICE, n * 4096 bytes, the caller's: what navhip_world.los_pool points at.  Slots never move.
  * NAVHIP_ERR_INVALID, with the reason in navhip_last_error, unless for every slot: prev_slot[i] == -1 exactly where
  * prev_dr == prev_dc == 0, otherwise 0 <= prev_slot[i] < i; the predecessor's chunk is chunk + (prev_dr, prev_dc) and its
- * layer and target are this slot's; levels do not decrease; the layer is resident -- and faction_id is
- * NAVHIP_FACTION_ID_NONE: the changed-chunk flags say "passability WITHOUT a faction changed" and do not cover the
- * field of an attacking path, which a chain could therefore not keep current. */
+ * layer and target are this slot's; levels do not decrease; the layer is resident -- and where faction_id is not
+ * NAVHIP_FACTION_ID_NONE: it is below NAVHIP_MAX_FACTIONS, the layer has a resident factions plane (without one there
+ * are no per-faction flags to follow) and the predecessor has the same faction_id and enemies.  Slots with and without
+ * a faction may share a chain. */
 typedef struct navhip_los_chain navhip_los_chain;
 enum { NAVHIP_LOS_REFRESH_DOWNSTREAM = 1u };
 typedef struct navhip_los_chain_stats {
     int32_t slots, levels;
-    int32_t stale;      /* slots whose own chunk was flagged changed, summed over every refresh so far        */
+    int32_t stale;      /* slots whose own chunk was flagged changed (by either kind of flag), summed over every
+                           refresh so far                                                                     */
     int32_t rebuilt;    /* fields the refreshes rebuilt: the same number, plus -- with NAVHIP_LOS_REFRESH_DOWNSTREAM --
                            the fields built from a stale one                                                  */
     int32_t redone;     /* fields a build left to its second launch (more than 1 022 tiles in the frontier)    */
@@ -306,7 +323,12 @@ int  navhip_los_chain_build(navhip_los_chain *chain, void *stream);
  *                                        in level order -- from whatever its predecessor holds then
  *   NAVHIP_LOS_REFRESH_DOWNSTREAM        ... and every field built from a rebuilt one: the pool equals a
  *                                        navhip_los_chain_build on the current planes
- * Reads the changed-chunk flags and clears nothing: that stays navhip_clear_changed. */
+ * A slot's chunk is changed when its changed-chunk flag is set, or -- for a slot with a faction -- a per-faction flag of
+ * a faction that is not among the slot's enemies: its field reads cost_base, blockers > 0 and, on blocked tiles, the
+ * factions rows of non-enemies; the first flag covers the first two, the third only differs when such a row does, and a
+ * row of an enemy never matters.  With flags 0 that is a superset of the reference, whose dirty set (nav.c:1036) knows
+ * no faction and leaves the field of an attacking path stale when only faction counters moved.
+ * Reads the flags and clears nothing: that stays navhip_clear_changed. */
 int  navhip_los_chain_refresh(navhip_los_chain *chain, uint32_t flags, void *stream);
 /* Waits for the last build / refresh. */
 int  navhip_los_chain_get_stats(navhip_los_chain *chain, navhip_los_chain_stats *out);

@@ -22,7 +22,8 @@
 //                      Refcounts are updated with 32-bit atomics on the containing word.
 // k_refresh_touched    one wave per chunk: rebuild the passability row masks of chunks whose
 //                      blockers were touched, flag the chunk `changed` when any mask differs; and
-//                      the facmask rows of the factions whose counters were touched there.
+//                      the facmask rows of the factions whose counters were touched there, with
+//                      bit f of `fac_changed` raised when a row of faction f differs.
 // k_local_islands      one wave per chunk: bit-parallel flood fill per component, labels kept
 //                      bit-sliced, expanded to u16 and stored coalesced through LDS.
 #include "navhip_internal.h"
@@ -225,12 +226,15 @@ __global__ __launch_bounds__(256) void k_blockers_circles(nh_blk_params P, const
 // `changed` keeps its meaning: the passability WITHOUT a faction (passmask) of the chunk differs.  The faction rows are
 // refreshed for every touched chunk whether it differs or not -- a unit of another faction that steps on tiles which
 // are blocked already changes what an attacking path may cross while passmask stays what it is -- but only the rows of
-// the factions the circle kernel touched there (fac_touched).
+// the factions the circle kernel touched there (fac_touched).  What `changed` cannot say, `fac_changed` does: bit f is
+// raised when a facmask row of faction f comes out different from what it held (masks, not counters: a second unit on
+// tiles the faction holds already, or an incref and a decref of one circle in a batch, raise nothing).  Both flags are
+// sticky until navhip_clear_changed.
 __global__ __launch_bounds__(256) void k_refresh_touched(const uint8_t *cost, const uint16_t *blockers,
                                                          uint64_t *passmask, uint64_t *probemask, uint8_t *unit_cost,
                                                          uint8_t *touched, uint8_t *changed,
                                                          const uint8_t *factions, uint64_t *facmask, uint16_t *facany,
-                                                         uint32_t *fac_touched, int nchunks)
+                                                         uint32_t *fac_touched, uint16_t *fac_changed, int nchunks)
 {
     const int chunk = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
     if(chunk >= nchunks || !touched[chunk]) return;
@@ -251,18 +255,23 @@ __global__ __launch_bounds__(256) void k_refresh_touched(const uint8_t *cost, co
     probemask[((size_t)chunk * 64 + lane) * 2 + 1] = blocked;       // (the cost half does not change here)
     const bool any_nonunit = __any(nonunit), any_diff = __any(differs);
     const bool refaction = ft != 0;
+    uint32_t fdiff = 0;
     while(ft) {
         const int f = __builtin_ctz(ft);
         ft &= ft - 1;
         const uint64_t m = nz_row_mask(factions + ((size_t)chunk * NAVHIP_MAX_FACTIONS << 12) + ((size_t)f << 12) + lane * 64);
-        facmask[((size_t)chunk * NAVHIP_MAX_FACTIONS + f) * 64 + lane] = m;
+        uint64_t *row = facmask + ((size_t)chunk * NAVHIP_MAX_FACTIONS + f) * 64 + lane;
+        const uint64_t old = *row;
+        *row = m;
         fany = __ballot(m != 0) ? (fany | (1u << f)) : (fany & ~(1u << f));
+        if(__ballot(m != old)) fdiff |= 1u << f;
     }
     if(lane == 0) {
         unit_cost[chunk] = any_nonunit ? 0 : 1;
         if(any_diff) changed[chunk] = 1;
         touched[chunk] = 0;
         if(refaction) { facany[chunk] = (uint16_t)fany; fac_touched[chunk] = 0; }
+        if(fdiff) fac_changed[chunk] |= (uint16_t)fdiff;
     }
 }
 
@@ -345,7 +354,7 @@ void nh_launch_blockers_circles(navhip_ctx *ctx, const navhip_circle *d_circles,
         if(!L.blockers || !L.cost) continue;
         hipLaunchKernelGGL(k_refresh_touched, dim3((ctx->nchunks + 3) / 4), dim3(256), 0, s, L.cost,
                            L.blockers, L.passmask, L.probemask, L.unit_cost, L.touched, L.changed,
-                           L.factions, L.facmask, L.facany, L.fac_touched, ctx->nchunks);
+                           L.factions, L.facmask, L.facany, L.fac_touched, L.fac_changed, ctx->nchunks);
         if(L.local_islands)
             hipLaunchKernelGGL(k_local_islands, dim3((ctx->nchunks + 3) / 4), dim3(256), 0, s,
                                L.passmask, L.local_islands, L.changed, ctx->nchunks);

@@ -57,6 +57,10 @@ __device__ __forceinline__ uint16_t portal_first_iid(const uint16_t *li, int r0,
 // Request flags that are resolved on the device: NAVHIP_REQ_IF_CHANGED (skip unless the chunk, or
 // the next chunk of a portal target, changed) and NAVHIP_REQ_LIVE_IIDS (island ids re-read from
 // the current labels).  Returns false when the request is to be skipped.
+// A request with a faction has also changed when a facmask row of its OWN chunk differs for a faction
+// that is no enemy of it (fac_changed): the rows of enemies never enter faction_pass_row.  The next
+// chunk of a portal target is read through local_islands alone (portal_seed, next_tile_matches), and
+// those are labelled from the faction-agnostic passmask: `changed` covers it.
 __device__ __forceinline__ bool req_prepare(const nh_map_view &map, navhip_field_req &rq)
 {
     const nh_layer_view &L = map.layers[rq.layer];
@@ -64,6 +68,8 @@ __device__ __forceinline__ bool req_prepare(const nh_map_view &map, navhip_field
     if((rq.flags & NAVHIP_REQ_IF_CHANGED) && L.changed) {
         bool ch = L.changed[(int)rq.chunk_r * map.w + rq.chunk_c] != 0;
         if(portal) ch |= L.changed[(int)rq.next_chunk_r * map.w + rq.next_chunk_c] != 0;
+        if(rq.faction_id != NAVHIP_FACTION_ID_NONE && L.fac_changed)
+            ch |= (L.fac_changed[(int)rq.chunk_r * map.w + rq.chunk_c] & ~rq.enemies & 0x7fff) != 0;
         if(!ch) return false;
     }
     if((rq.flags & NAVHIP_REQ_LIVE_IIDS) && portal && L.local_islands) {

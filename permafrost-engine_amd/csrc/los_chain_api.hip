@@ -12,6 +12,11 @@
 //   refresh  behind a blocker batch: one launch marks the slots whose chunk the batch flagged in changed[] (with
 //            NAVHIP_LOS_REFRESH_DOWNSTREAM: and everything built from them) and compacts them per level, one launch
 //            per level rebuilds them in place.  No host round trip, no allocation: everything is sized at create.
+// A slot may carry a faction (an attacking path: tiles blocked by enemies only are passable).  changed[] is passability
+// WITHOUT a faction; what it misses -- an ally on tiles an enemy holds already -- is in the layer's fac_changed[], one bit
+// per faction whose rows differ, and such a slot is also stale by a bit of a faction that is NOT among its enemies
+// (fmask[slot]).  With flags = 0 that is a superset of the reference, whose dirty set (nav.c:1036) knows no faction and
+// leaves such fields stale.
 // A unit without kernels: they are k_los_field / k_los_mark of los_kernels.hip.
 #include "navhip_internal.h"
 #include <new>
@@ -35,8 +40,11 @@ static const char *chain_request_error(const navhip_ctx *ctx, const navhip_los_r
     || r.target_chunk_c >= ctx->w || r.target_tile_r >= 64 || r.target_tile_c >= 64)
         return "chunk, target or layer outside the map";
     if(!ctx->layers[r.layer].cost) return "the layer is not resident";
-    if(r.faction_id != NAVHIP_FACTION_ID_NONE)
-        return "a request with a faction (changed[] is passability without a faction: it does not cover such a field)";
+    if(r.faction_id != NAVHIP_FACTION_ID_NONE) {
+        if(r.faction_id >= NAVHIP_MAX_FACTIONS) return "faction_id is neither a faction nor NAVHIP_FACTION_ID_NONE";
+        if(!ctx->layers[r.layer].fac_changed)
+            return "a request with a faction on a layer without a factions plane (no per-faction changed flags to follow)";
+    }
     if((prev_slot[i] == -1) != !has_prev) return "prev_slot is -1 exactly for a request without a previous chunk";
     if(!has_prev) {
         if(r.chunk_r != r.target_chunk_r || r.chunk_c != r.target_chunk_c) return "a request without a previous chunk is not on the target's chunk";
@@ -50,6 +58,8 @@ static const char *chain_request_error(const navhip_ctx *ctx, const navhip_los_r
         if(p.layer != r.layer || p.target_chunk_r != r.target_chunk_r || p.target_chunk_c != r.target_chunk_c
         || p.target_tile_r != r.target_tile_r || p.target_tile_c != r.target_tile_c)
             return "the predecessor has another layer or target";
+        if(p.faction_id != r.faction_id || (r.faction_id != NAVHIP_FACTION_ID_NONE && p.enemies != r.enemies))
+            return "the predecessor has another faction or other enemies";
     }
     if(i > 0 && level[i] < level[i - 1]) return "slots are not in level order";
     return nullptr;
@@ -67,6 +77,8 @@ int navhip_los_chain_create(navhip_ctx *ctx, const navhip_los_req *reqs, const i
     }
     std::vector<int32_t> level((size_t)n, 0);
     std::vector<uint32_t> cell((size_t)n);
+    std::vector<uint16_t> fmask((size_t)n, 0);
+    bool any_faction = false;
     for(int i = 0; i < n; i++) {
         if(prev_slot[i] >= 0 && prev_slot[i] < i) level[i] = level[prev_slot[i]] + 1;
         if(const char *why = chain_request_error(ctx, reqs, prev_slot, level, i)) {
@@ -74,6 +86,7 @@ int navhip_los_chain_create(navhip_ctx *ctx, const navhip_los_req *reqs, const i
             return NAVHIP_ERR_INVALID;
         }
         cell[i] = (uint32_t)reqs[i].layer << 24 | (uint32_t)((int)reqs[i].chunk_r * ctx->w + reqs[i].chunk_c);
+        if(reqs[i].faction_id != NAVHIP_FACTION_ID_NONE) { fmask[i] = (uint16_t)(~reqs[i].enemies & 0x7fff); any_faction = true; }
     }
     const int levels = level[n - 1] + 1;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -83,10 +96,10 @@ int navhip_los_chain_create(navhip_ctx *ctx, const navhip_los_req *reqs, const i
     c->level_begin.assign((size_t)levels + 1, n);
     for(int i = n - 1; i >= 0; i--) c->level_begin[level[i]] = i;
     c->level_begin[0] = 0;
-    // one slab: requests | prev_slot | cell | level_begin | list | count | stats | stale | overflow
+    // one slab: requests | prev_slot | cell | level_begin | list | count | stats | stale | overflow | fmask (with a faction slot)
     const size_t N = (size_t)n;
     const size_t parts[] = {N * sizeof(navhip_los_req), N * 4, N * 4, ((size_t)levels + 1) * 4, N * 4, (size_t)levels * 4,
-                            NH_LCS_COUNT * 4, N, N};
+                            NH_LCS_COUNT * 4, N, N, any_faction ? N * 2 : 0};
     size_t off[sizeof(parts) / sizeof(parts[0]) + 1] = {0};
     for(size_t k = 0; k < sizeof(parts) / sizeof(parts[0]); k++) off[k + 1] = off[k] + nh_up256(parts[k]);
     const size_t total = off[sizeof(parts) / sizeof(parts[0])];
@@ -97,10 +110,11 @@ int navhip_los_chain_create(navhip_ctx *ctx, const navhip_los_req *reqs, const i
     || hipMemcpy(base + off[0], reqs, parts[0], hipMemcpyHostToDevice) != hipSuccess
     || hipMemcpy(base + off[1], prev_slot, parts[1], hipMemcpyHostToDevice) != hipSuccess
     || hipMemcpy(base + off[2], cell.data(), parts[2], hipMemcpyHostToDevice) != hipSuccess
-    || hipMemcpy(base + off[3], c->level_begin.data(), parts[3], hipMemcpyHostToDevice) != hipSuccess)
+    || hipMemcpy(base + off[3], c->level_begin.data(), parts[3], hipMemcpyHostToDevice) != hipSuccess
+    || (any_faction && hipMemcpy(base + off[9], fmask.data(), parts[9], hipMemcpyHostToDevice) != hipSuccess))
         return fail("navhip_los_chain_create: copy to the device", NAVHIP_ERR_DEVICE);
     c->v = nh_los_chain_view{(const navhip_los_req*)(base + off[0]), (const int32_t*)(base + off[1]), (const uint32_t*)(base + off[2]),
-                             (const int32_t*)(base + off[3]), dev_pool, (uint8_t*)(base + off[7]), (uint8_t*)(base + off[8]),
+                             any_faction ? (const uint16_t*)(base + off[9]) : nullptr, (const int32_t*)(base + off[3]), dev_pool, (uint8_t*)(base + off[7]), (uint8_t*)(base + off[8]),
                              (int32_t*)(base + off[4]), (int32_t*)(base + off[5]), (int32_t*)(base + off[6]), n, levels,
                              map_pos_x, map_pos_z};
     *out = c;

@@ -326,7 +326,11 @@ void nh_launch_los_chain_stale(navhip_ctx *ctx, const nh_los_chain_view &c, int 
                            c.map_z, (uint8_t*)nullptr, ch);
 }
 
-// Which slots of a chain the changed chunks make stale: stale[i] = changed[layer][chunk] of slot i, with `downstream`
+// Which slots of a chain the changed chunks make stale: stale[i] = changed[layer][chunk] of slot i -- or, for a slot with
+// a faction, a bit of fac_changed[layer][chunk] among fmask[i], the factions that are no enemies of the slot's: its field
+// reads cost, blockers > 0 and blocked & OR(facmask rows of non-enemies); `changed` covers the first two, the third only
+// differs when such a row does, and a row of an enemy never matters (a chain without a faction slot has fmask == NULL
+// and loads what it always did) --, with `downstream`
 // also stale[prev_slot[i]] -- slots are in level order and a predecessor sits on the level before, so one pass over the
 // levels does it: ONE workgroup walks them, a barrier between two levels.  Per level the stale slots leave as a
 // compacted list in ascending slot order (list[level_begin[L] ...], count[L]): positions come from ballots and a prefix
@@ -357,6 +361,11 @@ __global__ __launch_bounds__(LM_THREADS) void k_los_mark(nh_map_view map, nh_los
                     const uint32_t cell = c.cell[i];
                     const uint8_t *chg = map.layers[cell >> 24].changed;
                     own = chg && chg[cell & 0xffffffu] != 0;
+                    if(c.fmask) {                                   // (wave-uniform: a chain with a faction slot)
+                        const uint32_t fm = c.fmask[i];
+                        const uint16_t *fchg = map.layers[cell >> 24].fac_changed;
+                        if(fm && fchg) own |= (fchg[cell & 0xffffffu] & fm) != 0;
+                    }
                     // (the predecessor's flag was stored in front of the barrier that ended its level)
                     if(downstream && L > 0) inherited = c.stale[c.prev_slot[i]] != 0;
                     c.stale[i] = (own || inherited) ? 1 : 0;

@@ -16,6 +16,7 @@ struct nh_layer_view {
     const uint64_t *probemask;     // [chunks][64][2] derived row bits: {cost_base != COST_IMPASSABLE, blockers > 0}
     const uint64_t *facmask;       // [chunks][15][64] derived row bits: factions[f] != 0 (NULL: no factions plane resident)
     const uint16_t *facany;        // [chunks]         bit f: faction f holds a tile of the chunk
+    const uint16_t *fac_changed;   // [chunks]         bit f: the facmask rows of faction f differ since navhip_clear_changed
 };
 struct nh_map_view {
     int w, h;

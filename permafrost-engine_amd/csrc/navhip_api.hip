@@ -38,6 +38,7 @@ static const derived_row derived_rows[] = {
     {offsetof(navhip_layer, changed),     1,                                           false, true},
     {offsetof(navhip_layer, facmask),     NAVHIP_MAX_FACTIONS * 64 * sizeof(uint64_t), true,  true},
     {offsetof(navhip_layer, facany),      sizeof(uint16_t),                            true,  true},
+    {offsetof(navhip_layer, fac_changed), sizeof(uint16_t),                            true,  true},
     {offsetof(navhip_layer, fac_touched), sizeof(uint32_t),                            true,  true},
 };
 
@@ -387,14 +388,29 @@ int navhip_changed_chunks(navhip_ctx *ctx, int layer, uint8_t *host_flags, int c
     return NAVHIP_OK;
 }
 
+int navhip_faction_changed_chunks(navhip_ctx *ctx, int layer, uint16_t *host_flags, int clear)
+{
+    if(!ctx || !host_flags || layer < 0 || layer >= NAVHIP_NAV_LAYER_MAX) return NAVHIP_ERR_INVALID;
+    navhip_layer &L = ctx->layers[layer];
+    const size_t bytes = (size_t)ctx->nchunks * sizeof(uint16_t);
+    if(!L.fac_changed) { memset(host_flags, 0, bytes); return NAVHIP_OK; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipMemcpyAsync(host_flags, L.fac_changed, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if(clear) HIPCHK(ctx, hipMemsetAsync(L.fac_changed, 0, bytes, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return NAVHIP_OK;
+}
+
 int navhip_clear_changed(navhip_ctx *ctx, void *stream)
 {
     if(!ctx) return NAVHIP_ERR_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    for(int l = 0; l < NAVHIP_NAV_LAYER_MAX; l++)
-        if(ctx->layers[l].changed)
-            HIPCHK(ctx, hipMemsetAsync(ctx->layers[l].changed, 0, (size_t)ctx->nchunks, s));
+    for(int l = 0; l < NAVHIP_NAV_LAYER_MAX; l++) {
+        const navhip_layer &L = ctx->layers[l];
+        if(L.changed) HIPCHK(ctx, hipMemsetAsync(L.changed, 0, (size_t)ctx->nchunks, s));
+        if(L.fac_changed) HIPCHK(ctx, hipMemsetAsync(L.fac_changed, 0, (size_t)ctx->nchunks * sizeof(uint16_t), s));
+    }
     return NAVHIP_OK;
 }
 

@@ -166,6 +166,9 @@ struct navhip_layer {
                                // the factions plane               (field_tile_passable_no_enemies, field.c:179)
     uint16_t *facany = nullptr;        // [nchunks]      bit f = faction f holds a tile of the chunk (facmask row f not empty)
     uint32_t *fac_touched = nullptr;   // [nchunks]      device: bit f = counters of faction f modified since the last refresh
+    uint16_t *fac_changed = nullptr;   // [nchunks]      device: bit f = the facmask rows of faction f differ (what an attacking
+                               //                path that is no enemy of f may cross) since navhip_clear_changed; raised by
+                               //                the blocker updates only, like `changed`; allocated with the factions plane
     uint8_t  *unit_cost = nullptr;     // [nchunks]      1 when every cost != 0xff cell has cost 1
     uint8_t  *touched = nullptr;       // [nchunks]      device: blockers modified since the last refresh
     uint8_t  *changed = nullptr;       // [nchunks]      device: passability WITHOUT a faction (passmask) changed since
@@ -275,7 +278,7 @@ static inline void nh_fill_map_view(const navhip_ctx *ctx, nh_map_view *mv)
         const navhip_layer &L = ctx->layers[l];
         mv->layers[l] = nh_layer_view{L.cost, L.blockers, L.local_islands, L.factions,
                                       L.passmask, L.unit_cost, L.changed, L.islands, L.probemask,
-                                      L.facmask, L.facany};
+                                      L.facmask, L.facany, L.fac_changed};
     }
 }
 
@@ -387,6 +390,8 @@ struct nh_los_chain_view {
     const navhip_los_req *reqs;         // [slots]
     const int32_t  *prev_slot;          // [slots]      -1: the destination chunk's own field
     const uint32_t *cell;               // [slots]      layer << 24 | chunk_r * w + chunk_c
+    const uint16_t *fmask;              // [slots]      the factions whose fac_changed bit makes the slot stale: ~enemies & 0x7fff
+                                        //              of a slot with a faction, 0 of one without; NULL: no slot has a faction
     const int32_t  *level_begin;        // [levels + 1]
     uint8_t        *pool;               // [slots][4096] the caller's
     uint8_t        *stale;              // [slots]      of the last refresh

@@ -246,6 +246,7 @@ _SIGS = {
     "navhip_blockers_circles_dev": (_I, [_P, _P, _I, _F, _F, _P]),
     "navhip_relabel_local_islands": (_I, [_P, _I]),
     "navhip_changed_chunks": (_I, [_P, _I, _P, _I]),
+    "navhip_faction_changed_chunks": (_I, [_P, _I, _P, _I]),
     "navhip_clear_changed": (_I, [_P, _P]),
     "navhip_build_region_fields": (_I, [_P, _P, _I, _P, _Z, _P, _Z, _P, _Z]),
     "navhip_build_region_fields_dev": (_I, [_P, _P, _I, _I, _P, _P, _P, _Z, _P]),
@@ -689,6 +690,12 @@ class NavContext(_Handle):
     def changed_chunks(self, layer=0, clear=False):
         out = np.zeros(self.w * self.h, np.uint8)
         self._call("navhip_changed_chunks", layer, _hp(out), int(clear))
+        return out.reshape(self.h, self.w)
+
+    def faction_changed_chunks(self, layer=0, clear=False):
+        """[h][w] u16: bit f = a blocker update changed which tiles of the chunk faction f holds."""
+        out = np.zeros(self.w * self.h, np.uint16)
+        self._call("navhip_faction_changed_chunks", layer, _hp(out), int(clear))
         return out.reshape(self.h, self.w)
 
     def clear_changed(self, stream=None):
