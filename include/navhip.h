@@ -33,6 +33,7 @@ extern "C" {
 
 #define NAVHIP_OK                 0
 #define NAVHIP_ERR_INVALID       -1   /* bad argument                         */
+#define NAVHIP_ERR_ARG           NAVHIP_ERR_INVALID   /* the same code, as navhip_dest_queries names it */
 #define NAVHIP_ERR_DEVICE        -2   /* HIP runtime error (see last_error)   */
 #define NAVHIP_ERR_NOMEM         -3
 #define NAVHIP_ERR_NOT_UPLOADED  -4   /* a plane the request needs is missing */
@@ -775,6 +776,46 @@ int  navhip_state_update(navhip_ctx *ctx, const navhip_world *world, const navhi
 /* Everything resident on the device, asynchronous on `stream`. */
 int  navhip_state_update_dev(navhip_ctx *ctx, const navhip_world *dev_world, const navhip_state_in *dev_in,
                              uint8_t *dev_out_state, uint8_t *dev_out_flags, void *stream);
+
+/* ---- the two destination queries of arrived() on the device ----------------------------------------------------
+ *
+ * flock_nearest_xz and flock_tiles above (and range_tiles of navhip_state_aux_in below) are answers of two nav queries
+ * that depend on the destination only: N_ClosestPathable(layer, target) (nav.c:4126) and the tiles N_IsMaximallyClose
+ * walks (nav.c:4707): n_closest_island_tiles(dest tile, its global island id, ignore_blockers = false) (nav.c:1226,
+ * called at :4725).  Both read the blockers, which every unit that stops or starts changes: a host that caches them has
+ * to ask again on almost every tick.  These entry points answer them from the resident planes -- the probemask rows
+ * (cost_base != 0xff, blockers > 0: n_tile_blocked, nav.c:235), kept current behind navhip_blockers_circles[_dev], and
+ * NAVHIP_PLANE_ISLANDS -- bit for bit, the order of the tile list included.  16 bytes. */
+typedef struct navhip_dest_query { float x, z; int32_t layer; uint32_t flags; } navhip_dest_query;
+#define NAVHIP_DQ_NEAREST  0x1u   /* N_ClosestPathable(layer, (x, z))                                            */
+#define NAVHIP_DQ_TILES    0x2u   /* the closest island tiles of (x, z)                                          */
+#define NAVHIP_DQ_HOST     0x80   /* out_status: not decided here -- a search that has to visit a tile outside the window
+                                     of 127 x 127 tiles centred on the destination's tile (a map that fits the window
+                                     never does).  The row's nearest is (NaN, 0) and its tile list is empty, as with
+                                     NAVHIP_SU_HOST: the host makes both queries for that row                    */
+/* n queries, host buffers.  The outputs have the shapes of navhip_state_in.flock_nearest_xz / .flock_tiles_off /
+ * .flock_tiles and navhip_state_aux_in.range_tiles_off / .range_tiles:
+ *   out_nearest_xz [n][2]   the answer of NAVHIP_DQ_NEAREST; (NaN, 0) when the reference returns false (nothing on the map
+ *                           is free) or the bit was not asked for
+ *   out_tiles_off  [n + 1]  CSR offsets into out_tiles
+ *   out_tiles      [tiles_cap][2]  absolute nav tiles (row, column) in the reference's output order, at most 256 per
+ *                           query (FIELD_RES_R * 2 + FIELD_RES_C * 2, nav.c:4722); empty without NAVHIP_DQ_TILES
+ *   out_status     [n]      0 = answered, NAVHIP_DQ_HOST
+ * tiles_cap < 256 * n is accepted when the lists fit; when they do not -- known once the queries have run -- the call fails
+ * with NAVHIP_ERR_ARG and no output is written.
+ * NAVHIP_ERR_ARG, with the reason in navhip_last_error and before anything is launched: flags without a known bit or
+ * with an unknown one; a layer without resident cost_base and blockers planes, or -- with NAVHIP_DQ_TILES -- without the
+ * islands plane; a position outside the map (the reference asserts there). */
+int  navhip_dest_queries(navhip_ctx *ctx, const navhip_dest_query *q, int n, float map_pos_x, float map_pos_z,
+                         float *out_nearest_xz, int32_t *out_tiles_off, int16_t *out_tiles, int tiles_cap,
+                         uint8_t *out_status);
+/* Everything resident on the device, asynchronous on `stream`, no allocation after the first call at a given n: the
+ * results can be handed to navhip_state_update_dev as they are.  The records are not readable before the launch: a
+ * row the host form would refuse comes back NAVHIP_DQ_HOST.  dev_out_tiles_off always holds the true offsets; tiles
+ * beyond tiles_cap are not written (dev_out_tiles_off[n] > tiles_cap says so). */
+int  navhip_dest_queries_dev(navhip_ctx *ctx, const navhip_dest_query *dev_q, int n, float map_pos_x, float map_pos_z,
+                             float *dev_out_nearest_xz, int32_t *dev_out_tiles_off, int16_t *dev_out_tiles, int tiles_cap,
+                             uint8_t *dev_out_status, void *stream);
 
 /* ---- more of entity_compute_update: the heading gate, the arms of the state switch that flags, a
  *      counter, an angle or a distance decide, the arrival overlay's settle rule, and all of it but the last in one call ----

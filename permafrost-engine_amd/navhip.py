@@ -25,6 +25,7 @@ LIB_PATH = os.environ.get("NAVHIP_LIB") or os.path.join(_HERE, "libnavhip.so")
 # ---------------------------------------------------------------------------------------------
 OK = 0
 ERR_INVALID, ERR_DEVICE, ERR_NOMEM, ERR_NOT_UPLOADED = -1, -2, -3, -4        # NAVHIP_ERR_*
+ERR_ARG = ERR_INVALID
 FIELD_RES = 64
 FIELD_CELLS = 4096
 COST_IMPASSABLE = 0xFF
@@ -59,6 +60,8 @@ GATE_TURN, GATE_HOST = 0x01, 0x80
 SU_SET_MOVING, SU_TARGET_DIR, SU_SET_DEST, SU_SURROUND_DEST, SU_SURROUND_PREV = 0x04, 0x08, 0x10, 0x20, 0x40
 SQ_ADJACENT, SQ_HAS_DEST_0, SQ_HAS_DEST_1 = 0x01, 0x02, 0x04
 FS_MEMBER, FS_READY, FS_ASSIGNED, FS_IN_RANGE, FS_ARRIVED = 0x01, 0x02, 0x04, 0x08, 0x10
+DQ_NEAREST, DQ_TILES, DQ_HOST = 0x1, 0x2, 0x80
+DQ_MAX_TILES = 256                                                           # per query: FIELD_RES_R * 2 + FIELD_RES_C * 2
 
 # the whole tick behind one call
 TICK_SERIAL, TICK_TIME_FIELDS, TICK_OWNS_SNAPSHOT = 0x2, 0x8, 0x10
@@ -98,6 +101,10 @@ REGION_REQ_DTYPE = np.dtype([("layer", np.uint8), ("out_mode", np.uint8), ("enem
                              ("coff", np.uint16), ("seed_begin", np.uint32), ("seed_count", np.uint32),
                              ("overlay_begin", np.uint32), ("overlay_count", np.uint32)])
 assert REGION_REQ_DTYPE.itemsize == 32
+
+# navhip_dest_query, include/navhip.h (16 bytes)
+DEST_QUERY_DTYPE = np.dtype([("x", np.float32), ("z", np.float32), ("layer", np.int32), ("flags", np.uint32)])
+assert DEST_QUERY_DTYPE.itemsize == 16
 
 
 class World(C.Structure):
@@ -288,6 +295,9 @@ _SIGS = {
     "navhip_arrival_settle": (_I, [_P, _WORLD, C.POINTER(SettleIn), C.POINTER(SettleOut)]),
     "navhip_arrival_settle_dev": (_I, [_P, _WORLD, C.POINTER(SettleIn), C.POINTER(SettleOut), _P]),
     "navhip_arrival_settle_resident": (_I, [_P, _P, _P, _P]),
+    # dest_query_kernels: the destination queries of arrived()
+    "navhip_dest_queries": (_I, [_P, _P, _I, _F, _F, _P, _P, _P, _I, _P]),
+    "navhip_dest_queries_dev": (_I, [_P, _P, _I, _F, _F, _P, _P, _P, _I, _P, _P]),
     # pool_api: the resident field pool
     "navhip_pool_create": (_I, [_P, _I, _I]),
     "navhip_pool_destroy": (None, [_P]),
@@ -339,7 +349,7 @@ _SIGS = {
 # ---------------------------------------------------------------------------------------------
 RECORDS = {
     "navhip_field_req": FIELD_REQ_DTYPE, "navhip_circle": CIRCLE_DTYPE, "navhip_los_req": LOS_REQ_DTYPE,
-    "navhip_region_req": REGION_REQ_DTYPE, "navhip_world": World, "navhip_step_out": StepOut,
+    "navhip_region_req": REGION_REQ_DTYPE, "navhip_dest_query": DEST_QUERY_DTYPE, "navhip_world": World, "navhip_step_out": StepOut,
     "navhip_state_in": StateIn, "navhip_state_aux_in": StateAuxIn, "navhip_gate_in": GateIn,
     "navhip_state_pass_in": StatePassIn, "navhip_state_pass_out": StatePassOut,
     "navhip_arrival_zone": ArrivalZone, "navhip_settle_in": SettleIn, "navhip_settle_out": SettleOut,
@@ -869,6 +879,25 @@ class NavContext(_Handle):
         st, fl = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
         self._call("navhip_state_update", C.byref(w), C.byref(si), _hp(st), _hp(fl))
         return st, fl
+
+    # -- dest_query_kernels: the destination queries of arrived() ---------------------------------------
+    def dest_queries(self, queries, tiles_cap=None):
+        """N_ClosestPathable (nav.c:4126) and the closest island tiles of N_IsMaximallyClose (nav.c:4707) for the
+        DEST_QUERY_DTYPE records `queries`.  Returns (nearest_xz [n][2] with x = NaN for "none", list of [k, 2] int16
+        tile arrays, status [n]: 0 or DQ_HOST).  tiles_cap: rows of the tile buffer (default: 256 per query)."""
+        q = _arr(queries, DEST_QUERY_DTYPE)
+        n = len(q)
+        cap = DQ_MAX_TILES * n if tiles_cap is None else int(tiles_cap)
+        nearest, off = np.zeros((n, 2), np.float32), np.zeros(n + 1, np.int32)
+        tiles, status = np.zeros((max(cap, 1), 2), np.int16), np.zeros(n, np.uint8)
+        self._call("navhip_dest_queries", _hp(q), n, *self.map_pos(), _hp(nearest), _hp(off), _hp(tiles), cap, _hp(status))
+        return nearest, [tiles[off[i]:off[i + 1]].copy() for i in range(n)], status
+
+    def dest_queries_dev(self, d_queries, n, d_nearest_xz, d_tiles_off, d_tiles, tiles_cap, d_status, stream=None):
+        """navhip_dest_queries_dev: every buffer a torch CUDA tensor, asynchronous on `stream`; the outputs are what
+        navhip_state_in.flock_nearest_xz / .flock_tiles_off / .flock_tiles take."""
+        self._call("navhip_dest_queries_dev", dev_ptr(d_queries), int(n), *self.map_pos(), dev_ptr(d_nearest_xz),
+                   dev_ptr(d_tiles_off), dev_ptr(d_tiles), int(tiles_cap), dev_ptr(d_status), _stream(stream))
 
     def state_update_aux(self, arrays, fstate, wait_ticks_left, wait_prev, new_pos_xz, state, flags, work=None,
                          ent_rot=None, target_dir=None, range_in=None, surround=None, vdes_xz=None, hz=20):
