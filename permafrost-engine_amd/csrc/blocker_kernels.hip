@@ -135,12 +135,36 @@ __device__ __forceinline__ void add_u16(uint16_t *p, int delta)
     else           atomicSub(word, (unsigned)(-delta) << sh);
 }
 
+// A faction counter is a uint8_t in the reference and wraps modulo 256 (nav_data.h:141; n_update_blockers, nav.c:1032,
+// adds without an assert): 256 units of one faction over a tile read as 0.  Here four counters share the word the atomic
+// adds to, and a counter that wraps hands a unit to its neighbour -- which may wrap in turn, up to the top byte, whose
+// unit leaves the word.  Every add is therefore one unit on one byte, and takes the old word back: the bytes it wrapped
+// are the run of 0xff (going up; of 0x00 going down) that starts at its own byte, and for each of them it owes the byte
+// above the opposite unit, paid as another such add.  Only the add that caused a wrap can see it, and it sees it
+// exactly (the old word is the state the add met); so when every add is done each byte has been handed and paid back the
+// same number of units, and holds its own deltas modulo 256 -- in whatever order the adds of all the waves arrived,
+// word arithmetic being commutative.  A debt is always to a higher byte: the loop ends.  (Without a wrap: one atomic.)
 __device__ __forceinline__ void add_u8(uint8_t *p, int delta)
 {
     unsigned int *word = (unsigned int*)((uintptr_t)p & ~(uintptr_t)3);
-    const unsigned sh = (unsigned)((uintptr_t)p & 3) * 8u;
-    if(delta >= 0) atomicAdd(word, (unsigned)delta << sh);
-    else           atomicSub(word, (unsigned)(-delta) << sh);
+    const int at = (int)((uintptr_t)p & 3);
+    int owed[4];
+#pragma unroll
+    for(int i = 0; i < 4; i++) owed[i] = (i == at) ? delta : 0;
+#pragma unroll
+    for(int i = 0; i < 4; i++) {
+        while(owed[i]) {
+            const int s = owed[i] > 0 ? 1 : -1;
+            owed[i] -= s;
+            const unsigned old = atomicAdd(word, (unsigned)s << (8 * i));
+            const unsigned full = s > 0 ? 0xffu : 0u;
+#pragma unroll
+            for(int j = i; j < 3; j++) {
+                if(((old >> (8 * j)) & 0xffu) != full) break;
+                owed[j + 1] -= s;
+            }
+        }
+    }
 }
 
 __global__ __launch_bounds__(256) void k_blockers_circles(nh_blk_params P, const navhip_circle *circles,

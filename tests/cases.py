@@ -23,6 +23,23 @@ def random_blockers(grid, seed, frac=0.03):
     return synth.to_chunks(b)
 
 
+# crowds on single tiles of chunk (0, 0) of a map two chunks wide: (tile row, tile column, faction, entity flags).  The
+# faction counters are bytes, four to a word: one site per byte lane (column mod 4 = 0, 1, 2, 3), one in column 63 whose
+# contours of the 3x3 / 5x5 / 7x7 layers reach into chunk (0, 1), one in row 0 whose contours the map edge clips, one of air
+# units (layers 8-11).  No two 7x7 footprints (+-3 tiles) overlap.
+CROWD_SITES = ((8, 8, 14, 0), (8, 17, 5, 0), (8, 26, 0, 0), (8, 35, 3, 0), (24, 63, 7, 0), (40, 31, 9, 1 << 15), (0, 46, 4, 0))
+
+
+def crowd_circles(w, h, sites, count, delta):
+    """`count` circles of radius 1.0 (one tile on the 1x1 layers) on the centre of every site's tile, the sites
+    interleaved: site 0, site 1, ..., site 0, site 1, ..."""
+    c = np.zeros(len(sites) * count, navoracle.CIRCLE_DTYPE)
+    rows, cols, fac, flags = (np.tile(np.array(v), count) for v in zip(*sites))
+    xz = synth.cell_centre(w, h, rows, cols)
+    c["x"], c["z"], c["radius"], c["faction_id"], c["flags"], c["delta"] = xz[:, 0], xz[:, 1], 1.0, fac, flags, delta
+    return c
+
+
 def tile_requests(grid, k, seed):
     """k TARGET_TILE requests on random cells (passable or not: an impassable target must
     give an all-NONE field, field.c:1118-1124)."""

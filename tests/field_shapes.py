@@ -286,7 +286,31 @@ def staircase_path():
     return path + [(63, 63)]
 
 
-# the pinwheel about a cell X, offsets (row, col) from X.  X has walls to its N and W; E, S and SE are open and E, S have no
+def closed_chunk():
+    return np.full((64, 64), IMP, np.uint8)
+
+
+def anti_diagonal():
+    """The 64 cells (i, 63 - i): each touches the next at a corner only."""
+    return from_path([(i, 63 - i) for i in range(64)])
+
+
+def island_shapes():
+    """[(name, cost plane, number of 4-connected components)] for the local-island labelling, the counts known by
+    construction: 2 048 components fill every label plane of k_local_islands, the corridors are one component thousands of
+    cells long, the seams join halves in one cell, a closed chunk has no component at all."""
+    holed = checkerboard()
+    holed[32, 32] = IMP
+    last = closed_chunk()
+    last[63, 63] = 1
+    return [("checkerboard", checkerboard(), 2048), ("checkerboard_less_one", holed, 2047),
+            ("serpentine", from_path(serpentine_path()), 1), ("spiral", from_path(spiral_path()), 1),
+            ("rim", from_path(rim_path()), 1), ("column_seam", column_seam()[0], 1), ("row_seams", row_seams()[0], 1),
+            ("staircase", from_path(staircase_path()), 1), ("anti_diagonal", anti_diagonal(), 64), ("open", open_chunk(), 1),
+            ("closed", closed_chunk(), 0), ("last_cell", last, 1)]
+
+
+# the pinwheel about a cell X, offsets (row, col) from X. X has walls to its N and W; E, S and SE are open and E, S have no
 # other way out, so X is reached through them from SE.  With the target in the NE (or SW) quadrant of X, NW and SE are
 # equally far from it: X is at d, SE at d - 2 with both side tiles reached (admitted: it sets the minimum), NW at d - 2 behind
 # the two walls (not admitted) -- and NW comes first in the priority order.
