@@ -111,6 +111,16 @@ static const char *run(int n, void (*body)(void *), void *user, long *n_collecti
                         for(int k = w0; k < w0 + WS; k++) if(!w->done[k] && w->kind[k] == w->kind[l] && w->site[k] == w->site[l]) there++;
                         if(there != live_w) continue;
                     }
+                    // A shuffle whose source lane is alive but behind, alone at a counter read the others did not take
+                    // (`if(lane == 0 && load(ticket) < n) v = draw; t = shfl(v, 0)`: the one-problem-per-wave loop of
+                    // k_cp_heavy): the hardware runs the guarded read first and reconverges at the shuffle.  Served
+                    // without its source every lane would get its own value back and leave the loop, lane 0 drawing
+                    // the remaining tickets as a wave of one.  So the shuffle waits; with nothing else to serve the
+                    // second pass takes the lowest site, which is that read.
+                    if(pass == 0 && w->kind[l] == K_SHFL) {
+                        const int sl = w0 + (w->arg[l] & (WS - 1));
+                        if(!w->done[sl] && w->kind[sl] == K_WAVE_ALL && w->site[sl] < w->site[l]) continue;
+                    }
                     site = w->site[l]; first = l;
                 }
             if(first < 0) {
