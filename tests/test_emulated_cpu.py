@@ -41,6 +41,7 @@ SELECTION = [
     "tests/test_planes_gpu.py",        # plane and chunk uploads of two layers, the derived masks behind them, the refusals
     "tests/test_field_shapes_gpu.py",  # chunk fields 2 079 levels deep, every depth boundary, the diagonal rule; region and LOS fields on the shapes
     "tests/test_dispatch_gpu.py",      # the work-list dispatch: sparse lists taking turns on one context, an empty slab between them
+    "tests/test_cohesion_gpu.py",      # the cohesion launch plan: 1, 63, 64 and 65 flocks with empty ones, a slab that leaves flocks without a member
 ]
 # (agents: the tests that need torch.cuda, and the ones that take more than ~10 s each on the emulator)
 DESELECT = ["test_prefetch_overlap_gives_identical_results", "test_shared_chunk_fields_give_identical_results",
@@ -67,6 +68,14 @@ DESELECT_SPATIAL = ["test_device_lists_equal_restatement_reference_and_model[man
 DESELECT_DISPATCH = ["test_ladder_of_neighbour_counts[ladder]", "test_ladder_of_neighbour_counts[ladder_garrisoned]",
                      "test_one_list_full_deals_units_out_statically", "test_solo_heavy_takes_a_problem_per_wave",
                      "test_retry_flood_puts_a_quarter_of_the_agents_on_the_retry_list", "test_a_jam_between_two_sparse_steps"]
+
+
+# (cohesion: run one by one beside each other, interpreter start included -- the probes in the window 32 s each, the 4 096
+# lengths 37 s, 256 / 257 / 513 flocks 29 s, 30 s and 48 s: all of them pass there, run by hand; the far clusters -- 3 160 members
+# in waves that keep 15 .. 632 queue entries each, four ticks -- did not finish within 240 s and have NOT been seen to pass
+# there.  The plans of 1, 63, 64 and 65 flocks, 2-7 s each, run here.)
+DESELECT_COHESION = ["test_window_probes[20]", "test_window_probes[1]", "test_arith_lengths", "test_far_clusters",
+                     "test_plan_shapes[256]", "test_plan_shapes[257]", "test_plan_shapes[513]"]
 
 
 # device buffers ARE the test's host arrays in these (the mailbox transport between ranks of one process): they run
@@ -103,6 +112,8 @@ def test_gpu_parity_tests_pass_on_the_emulated_library(strict):
         cmd += ["--deselect", "tests/test_spatial_gpu.py::" + name]
     for name in DESELECT_DISPATCH:
         cmd += ["--deselect", "tests/test_dispatch_gpu.py::" + name]
+    for name in DESELECT_COHESION:
+        cmd += ["--deselect", "tests/test_cohesion_gpu.py::" + name]
     try:
         import xdist  # noqa: F401
         cmd += ["-n", str(min(8, os.cpu_count() or 1))]
@@ -113,7 +124,7 @@ def test_gpu_parity_tests_pass_on_the_emulated_library(strict):
     assert r.returncode == 0, tail
     last = r.stdout.strip().splitlines()[-1]
     assert " passed" in last and "failed" not in last and "error" not in last, tail
-    assert int(last.split(" passed")[0].split()[-1]) >= (135 if strict else 13), tail          # (the selection really ran)
+    assert int(last.split(" passed")[0].split()[-1]) >= (139 if strict else 13), tail          # (the selection really ran)
 
 
 def test_reference_binding_drives_the_emulated_library():
