@@ -223,7 +223,10 @@ int  navhip_clear_changed(navhip_ctx *ctx, void *stream);
  *               INFINITY where unreached.  Debug/parity output; the reference never exposes it. */
 int  navhip_build_fields(navhip_ctx *ctx, const navhip_field_req *reqs, int n,
                          uint8_t *inout_dirs, float *out_integ);
-/* Same with every buffer resident on the device (no PCIe in the call). */
+/* Same with every buffer resident on the device (no PCIe in the call).  Equal records of one call are built once and the
+ * field stored into the slot of each (requests that read their slot -- NAVHIP_REQ_INOUT, the repairs -- excepted); the
+ * scratch that finds them belongs to the context: at most ONE chunk-field build of a context (this call,
+ * navhip_build_fields, navhip_pool_build, a tick's) may be in flight at a time unless all of them run on one stream. */
 int  navhip_build_fields_dev(navhip_ctx *ctx, const navhip_field_req *dev_reqs, int n,
                              uint8_t *dev_inout_dirs, float *dev_out_integ, void *stream);
 

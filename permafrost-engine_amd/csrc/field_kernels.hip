@@ -174,6 +174,87 @@ void nh_launch_derive(navhip_ctx *ctx, int layer, const uint32_t *d_chunk_list, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// k_field_classes : equal requests of one build call form a class; its leader builds, and stores every copy
+// ---------------------------------------------------------------------------------------------
+// A planner asks for the same chunk field once per destination that routes through it (the reference keys its cache by
+// N_FlowFieldID for that reason): the request list of a tick holds each distinct 32-byte record about nine times.  What a
+// build does is a function of the record and the map state (req_uses_bfs, req_prepare, the faction rows), so equal
+// records give equal tiles -- unless the build READS its own slot (NAVHIP_REQ_INOUT and the two repairs): those are
+// classes of one.
+// One thread per request: hash the record, probe an open-addressed table of request indices (+1; 0 = empty).  The first
+// arrival of a record takes the entry and is the class's LEADER; a later arrival compares all 32 bytes with the
+// leader's and pushes itself onto the leader's list (head[leader] -> link[i].next -> ...; +1, 0 ends it), with the slot
+// its copy goes to beside the link so that the copying wave has one dependent load per member.  Which member leads
+// depends on the race, the tiles do not.  Entries never change once taken, so two equal records always meet: they walk
+// the same probe sequence, and the second finds the first in the entry it would have taken itself.
+struct __attribute__((aligned(8))) nh_class_link { int32_t next, slot; };     // next member + 1 | where this member's copy goes
+struct nh_class_view {
+    int32_t *table; uint32_t tmask;     // [tmask + 1] zero on entry
+    uint32_t tagmask;                   // the bits of an entry above the index: hash bits
+    int32_t *head;                      // [n] zero on entry
+    int32_t *leader_of;                 // [n] written for every request
+    struct nh_class_link *link;         // [n] of every request that is no leader
+    int32_t *other_table, *other_head;  // the set of the build before: k_field_generic zeroes clear_table / clear_heads words
+    int clear_table, clear_heads;
+};
+
+__device__ __forceinline__ bool req_reads_own_slot(const navhip_field_req &rq)
+{
+    return (rq.flags & (NAVHIP_REQ_INOUT | NAVHIP_REQ_ISLAND_NEAREST)) != 0 || rq.type == NAVHIP_TARGET_NEAREST_PATHABLE;
+}
+
+__device__ __forceinline__ uint32_t req_hash(const uint4 &a, const uint4 &b)
+{
+    uint32_t h = 0x9e3779b9u;
+    const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+    for(int k = 0; k < 8; k++) { h = (h ^ w[k]) * 0x85ebca6bu; h ^= h >> 15; }
+    h *= 0xc2b2ae35u;
+    return h ^ (h >> 16);
+}
+
+// gen_reqs: the word that counts the REQUESTS (not the leaders) which k_field_generic owns, or nullptr
+__global__ __launch_bounds__(256) void k_field_classes(nh_map_view map, const navhip_field_req *reqs, int n,
+                                                       nh_class_view cv, const int32_t *out_slot, int32_t *gen_reqs)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    bool generic = false;
+    if(i < n) {
+        const uint4 a = ((const uint4*)(reqs + i))[0], b = ((const uint4*)(reqs + i))[1];
+        navhip_field_req rq;                                          // (the record, from the two loads)
+        __builtin_memcpy(&rq, &a, 16);
+        __builtin_memcpy((char*)&rq + 16, &b, 16);
+        generic = !req_uses_bfs(map, rq, 0);
+        int leader = i;
+        if(!req_reads_own_slot(rq)) {
+            // (an entry: the request's index + 1 in the low bits, bits of its hash above them -- a probe that meets
+            // another record is over with the compare-and-swap itself, without a look at that record.  The kernel is as
+            // long as its longest chain of probes, each a round trip to L2: hence the tag, and a table of 8 n entries)
+            const uint32_t h = req_hash(a, b), tag = h & cv.tagmask;
+            for(uint32_t e = h & cv.tmask;; e = (e + 1) & cv.tmask) {
+                const uint32_t got = (uint32_t)atomicCAS(&cv.table[e], 0, (int32_t)(tag | (uint32_t)(i + 1)));
+                if(got == 0) break;                                   // first of its record
+                if((got & cv.tagmask) != tag) continue;
+                const int32_t was = (int32_t)(got & ~cv.tagmask);
+                const uint4 *o = (const uint4*)(reqs + (was - 1));
+                const uint4 oa = o[0], ob = o[1];
+                if(oa.x == a.x && oa.y == a.y && oa.z == a.z && oa.w == a.w
+                && ob.x == b.x && ob.y == b.y && ob.z == b.z && ob.w == b.w) {
+                    leader = was - 1;
+                    cv.link[i] = nh_class_link{atomicExch(&cv.head[leader], i + 1), out_slot ? out_slot[i] : i};
+                    break;
+                }
+            }
+        }
+        cv.leader_of[i] = leader;
+    }
+    if(gen_reqs) {
+        const uint64_t m = __ballot(generic);
+        if(m && (threadIdx.x & 63) == 0) atomicAdd(gen_reqs, __popcll(m));
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // k_field_bfs : one wave per request, lane = row
 // ---------------------------------------------------------------------------------------------
 // Row `lane` of the passability of a request WITH a faction (field_tile_passable_no_enemies, field.c:179-201): a
@@ -204,7 +285,7 @@ template <bool WANT_INTEG>
 __global__ __launch_bounds__(BFS_WAVES * 64) void k_field_bfs(nh_map_view map, const navhip_field_req *reqs,
                                                    int n, uint8_t *dirs, float *integ,
                                                    int force_generic, int32_t *gen_list, int gen_slot,
-                                                   const int32_t *out_slot)
+                                                   const int32_t *out_slot, nh_class_view cv)
 {
     // 4 KB of LDS per wave: staging buffer to turn "lane owns a 64-byte row" into fully
     // coalesced 16 B/lane global accesses (both for the INOUT read and for the final write).
@@ -214,11 +295,12 @@ __global__ __launch_bounds__(BFS_WAVES * 64) void k_field_bfs(nh_map_view map, c
     const int wave = blockIdx.x * BFS_WAVES + wib;
     const int lane = threadIdx.x & 63;
     if(wave >= n) return;
-
+    // (the record and the leader's index are independent loads: neither waits for the other)
     navhip_field_req rq = reqs[wave];
+    if(cv.leader_of[wave] != wave) return;        // its class's leader stores this request's copy
     if(!req_uses_bfs(map, rq, force_generic)) {
-        // not a unit-cost BFS (costs other than 1 in the chunk, a repair build): hand the request to k_field_generic
-        if(lane == 0) gen_list[2 + atomicAdd(&gen_list[gen_slot], 1)] = wave;
+        // not a unit-cost BFS (costs other than 1 in the chunk, a repair build): hand the class to k_field_generic
+        if(lane == 0) gen_list[NH_GEN_HEADER + atomicAdd(&gen_list[gen_slot], 1)] = wave;
         return;
     }
     if(!req_prepare(map, rq)) return;
@@ -309,6 +391,11 @@ __global__ __launch_bounds__(BFS_WAVES * 64) void k_field_bfs(nh_map_view map, c
             out[lane * 64 + c] = fin ? (float)d : __builtin_inff();
         }
     }
+    // the other members of the class (k_field_classes): needed behind the bake, loaded here so that the two dependent
+    // loads run beside it and the BFS in front never waits for them
+    int32_t member = cv.head[wave];
+    nh_class_link node = nh_class_link{0, 0};
+    if(member) node = cv.link[member - 1];
 
     // ---- bit-sliced bake (field_flow_dir, field.c:355-433) -----------------------------------
     // zero = cells with integration value 0
@@ -415,9 +502,30 @@ __global__ __launch_bounds__(BFS_WAVES * 64) void k_field_bfs(nh_map_view map, c
         }
     }
     __builtin_amdgcn_wave_barrier();
+    uint4 tile[4];
 #pragma unroll
-    for(int j = 0; j < 4; j++)
-        *(uint4*)(out + j * 1024 + lane * 16) = *(const uint4*)(st + j * 1024 + lane * 16);
+    for(int j = 0; j < 4; j++) tile[j] = *(const uint4*)(st + j * 1024 + lane * 16);
+#pragma unroll
+    for(int j = 0; j < 4; j++) *(uint4*)(out + j * 1024 + lane * 16) = tile[j];
+    // ... and the same tile to the slot of every other member: the next node is loaded before this copy's stores
+    // are issued, so the one dependent load of the walk hides behind them
+    while(member) {
+        uint8_t *o = dirs + ((size_t)node.slot << 12);
+        member = node.next;
+        if(member) node = cv.link[member - 1];
+#pragma unroll
+        for(int j = 0; j < 4; j++) *(uint4*)(o + j * 1024 + lane * 16) = tile[j];
+    }
+    if(WANT_INTEG) {
+        // (debug / parity output, indexed by request) every member gets the leader's integration field: each lane copies
+        // the row it wrote itself above -- its own stores, in program order -- so the distance planes need not outlive the bake
+        const uint4 *src = (const uint4*)(integ + ((size_t)wave << 12) + lane * 64);
+        for(int32_t m = cv.head[wave]; m; m = cv.link[m - 1].next) {
+            uint4 *dst = (uint4*)(integ + ((size_t)(m - 1) << 12) + lane * 64);
+#pragma unroll 4
+            for(int j = 0; j < 16; j++) dst[j] = src[j];
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -433,7 +541,7 @@ struct generic_lds {
 
 __device__ void field_generic_one(generic_lds &S, const nh_map_view &map, const navhip_field_req *reqs,
                                   int ri, uint8_t *dirs, float *integ, int force_generic,
-                                  const int32_t *out_slot)
+                                  const int32_t *out_slot, const nh_class_view &cv)
 {
     uint32_t (&dist)[NH_CELLS] = S.dist;
     uint8_t (&pc)[NH_CELLS] = S.pc;
@@ -444,6 +552,7 @@ __device__ void field_generic_one(generic_lds &S, const nh_map_view &map, const 
     int &s_nlist = S.s_nlist, &s_D = S.s_D;
 
     const int t = threadIdx.x;
+    if(cv.leader_of[ri] != ri) return;                    // its class's leader stores this request's copy
     navhip_field_req rq = reqs[ri];
     if(req_uses_bfs(map, rq, force_generic)) return;      // the BFS kernel owns this request
     if(!req_prepare(map, rq)) return;
@@ -687,47 +796,100 @@ __device__ void field_generic_one(generic_lds &S, const nh_map_view &map, const 
 #pragma unroll
     for(int k = 0; k < 16; k++) pc[k * 256 + t] = res[k];
     __syncthreads();
-    *(uint4*)(out + t * 16) = *(const uint4*)(pc + t * 16);
+    const uint4 tile = *(const uint4*)(pc + t * 16);
+    *(uint4*)(out + t * 16) = tile;
+    // the same tile (and integration field: dist[] is final) for every other member of the class, as in k_field_bfs
+    int32_t member = cv.head[ri];
+    nh_class_link node = member ? cv.link[member - 1] : nh_class_link{0, 0};
+    while(member) {
+        const int m = member - 1;
+        uint8_t *o = dirs + ((size_t)node.slot << 12);
+        member = node.next;
+        if(member) node = cv.link[member - 1];
+        *(uint4*)(o + t * 16) = tile;
+        if(integ) {
+#pragma unroll 4
+            for(int k = 0; k < 16; k++) {
+                const int i = k * 256 + t;
+                const uint32_t d = dist[i];
+                integ[((size_t)m << 12) + i] = (d >= NH_INF_U32) ? __builtin_inff() : (float)d;
+            }
+        }
+    }
 }
 
-// The launch is a fixed, small grid: workgroups stride over the list of requests the BFS kernel
-// declined (gen_list: two counters, then the ids; gen_list == nullptr: every request, in order).  A
+// The launch is a fixed, small grid: workgroups stride over the list of class leaders the BFS kernel
+// declined (gen_list: NH_GEN_HEADER words, then the ids; gen_list == nullptr: every request, in order,
+// of which the leaders build).  The header is two list lengths and, beside them, two counts of the
+// REQUESTS those classes stand for (k_field_classes; navhip_last_fields_split reports requests).  A
 // tick whose requests are all unit-cost BFS fields pays for a few hundred workgroups that read one
 // counter, not for one empty workgroup per request.  The two counters alternate between launches:
-// this launch reads counter `gen_slot` and zeroes the other one for the next launch (which starts
-// after this one in stream order) -- no reset pass, no completion atomics.
+// this launch reads counter `gen_slot` and zeroes the other one (and its request count) for the next
+// launch (which starts after this one in stream order) -- no reset pass, no completion atomics.
 __global__ __launch_bounds__(256) void k_field_generic(nh_map_view map, const navhip_field_req *reqs,
                                                        int n, uint8_t *dirs, float *integ,
                                                        int force_generic, int32_t *gen_list, int gen_slot,
-                                                       const int32_t *out_slot)
+                                                       const int32_t *out_slot, nh_class_view cv)
 {
     __shared__ generic_lds S;
     const int count = gen_list ? gen_list[gen_slot] : n;
-    if(gen_list && blockIdx.x == 0 && threadIdx.x == 0) gen_list[gen_slot ^ 1] = 0;
+    if(gen_list && blockIdx.x == 0 && threadIdx.x == 0) gen_list[gen_slot ^ 1] = gen_list[2 + (gen_slot ^ 1)] = 0;
+    // ... and the same idiom for the classing scratch: the table and list heads of the build BEFORE this one (the other
+    // of two sets, which the next build takes) are zeroed here, over what that build used
+    for(int i = blockIdx.x * 256 + threadIdx.x; i < cv.clear_table; i += gridDim.x * 256) cv.other_table[i] = 0;
+    for(int i = blockIdx.x * 256 + threadIdx.x; i < cv.clear_heads; i += gridDim.x * 256) cv.other_head[i] = 0;
     for(int w = blockIdx.x; w < count; w += gridDim.x) {
-        const int ri = gen_list ? gen_list[2 + w] : w;
-        field_generic_one(S, map, reqs, ri, dirs, integ, force_generic, out_slot);
+        const int ri = gen_list ? gen_list[NH_GEN_HEADER + w] : w;
+        field_generic_one(S, map, reqs, ri, dirs, integ, force_generic, out_slot, cv);
         __syncthreads();
     }
 }
 
 // ---------------------------------------------------------------------------------------------
+// The classing scratch for up to `cap` requests (even): two sets of {table [tcap], head [cap]} that alternate between
+// builds, then leader_of [cap] and link [cap].  Zero when allocated; from then on every build leaves the set of the build
+// before it zeroed (k_field_generic), so no build starts with a reset of its own.
+static size_t classes_tcap(int cap)
+{
+    size_t t = 64;
+    while(t < 8 * (size_t)cap) t <<= 1;
+    return t;
+}
+size_t nh_field_classes_bytes(int cap) { return (2 * classes_tcap(cap) + 5 * (size_t)cap) * sizeof(int32_t); }
+
 int nh_launch_fields(navhip_ctx *ctx, const navhip_field_req *d_reqs, int n, uint8_t *d_dirs,
-                     float *d_integ, int32_t *d_gen_list, hipStream_t s, const int32_t *d_out_slot)
+                     float *d_integ, int32_t *d_gen_list, int32_t *d_classes, hipStream_t s, const int32_t *d_out_slot)
 {
     nh_map_view mv;
     nh_fill_map_view(ctx, &mv);
     const int force_generic = ctx->field_kernel_mode == 1;
     // (only launches that use the list alternate its counters)
     const int gen_slot = force_generic ? 0 : (int)(ctx->gen_launches++ & 1);
+    const int cap = ctx->classes.cap;
+    const size_t tcap = classes_tcap(cap), set = tcap + (size_t)cap;
+    const int mine = (int)(ctx->classes.builds++ & 1);
+    const size_t tsize = classes_tcap(n);                       // (<= tcap: n <= cap)
+    nh_class_view cv;
+    cv.table = d_classes + mine * set; cv.tmask = (uint32_t)(tsize - 1);
+    cv.head = cv.table + tcap;
+    const int idx_bits = 32 - __builtin_clz((unsigned)n);      // (entries hold 1 .. n)
+    cv.tagmask = idx_bits >= 32 ? 0u : ~((1u << idx_bits) - 1u);
+    cv.other_table = d_classes + (mine ^ 1) * set;
+    cv.other_head = cv.other_table + tcap;
+    cv.clear_table = ctx->classes.last_table; cv.clear_heads = ctx->classes.last_heads;
+    ctx->classes.last_table = (int)tsize; ctx->classes.last_heads = n;
+    cv.leader_of = d_classes + 2 * set;
+    cv.link = (nh_class_link*)(cv.leader_of + cap);
+    hipLaunchKernelGGL(k_field_classes, dim3((n + 255) / 256), dim3(256), 0, s, mv, d_reqs, n, cv, d_out_slot,
+                       force_generic ? (int32_t*)nullptr : d_gen_list + 2 + gen_slot);
     if(!force_generic) {
         dim3 grid((n + BFS_WAVES - 1) / BFS_WAVES);
         if(d_integ)
             hipLaunchKernelGGL(k_field_bfs<true>, grid, dim3(BFS_WAVES * 64), 0, s, mv, d_reqs, n, d_dirs,
-                               d_integ, force_generic, d_gen_list, gen_slot, d_out_slot);
+                               d_integ, force_generic, d_gen_list, gen_slot, d_out_slot, cv);
         else
             hipLaunchKernelGGL(k_field_bfs<false>, grid, dim3(BFS_WAVES * 64), 0, s, mv, d_reqs, n, d_dirs,
-                               d_integ, force_generic, d_gen_list, gen_slot, d_out_slot);
+                               d_integ, force_generic, d_gen_list, gen_slot, d_out_slot, cv);
     }
     // The relaxation kernel strides over the requests the BFS kernel declined.  Usually that list is empty
     // or short (repairs): 512 workgroups that mostly read one counter.  A map with real
@@ -736,6 +898,6 @@ int nh_launch_fields(navhip_ctx *ctx, const navhip_field_req *d_reqs, int n, uin
     for(int l = 0; l < NAVHIP_NAV_LAYER_MAX; l++) heavy = heavy || (ctx->layers[l].cost && ctx->layers[l].nonunit_costs);
     const int gmax = heavy ? 2048 : 512;
     hipLaunchKernelGGL(k_field_generic, dim3(n < gmax ? n : gmax), dim3(256), 0, s, mv, d_reqs, n, d_dirs,
-                       d_integ, force_generic, force_generic ? (int32_t*)nullptr : d_gen_list, gen_slot, d_out_slot);
+                       d_integ, force_generic, force_generic ? (int32_t*)nullptr : d_gen_list, gen_slot, d_out_slot, cv);
     return force_generic ? -1 : gen_slot;
 }

@@ -190,11 +190,20 @@ static int build_fields_on(navhip_ctx *ctx, const navhip_field_req *dev_reqs, in
     if(rc) return rc;
     // work list of the generic kernel: the header is zero between launches (the kernel resets it)
     const void *old_list = ctx->gen_list.p;
-    rc = nh_ensure_buf(ctx, ctx->gen_list, ((size_t)n + 2) * sizeof(int32_t));
+    rc = nh_ensure_buf(ctx, ctx->gen_list, ((size_t)n + NH_GEN_HEADER) * sizeof(int32_t));
     if(rc) return rc;
-    if(ctx->gen_list.p != old_list) HIPCHK(ctx, hipMemsetAsync(ctx->gen_list.p, 0, 2 * sizeof(int32_t), s));
+    if(ctx->gen_list.p != old_list) HIPCHK(ctx, hipMemsetAsync(ctx->gen_list.p, 0, NH_GEN_HEADER * sizeof(int32_t), s));
+    // scratch of the classing pass: zero when it is (re)allocated, kept zero between builds by the builds themselves
+    if(n > ctx->classes.cap) {
+        const int cap = (n + n / 2 + 1) & ~1;
+        ctx->classes = {};
+        rc = nh_ensure_buf(ctx, ctx->field_classes, nh_field_classes_bytes(cap));
+        if(rc) return rc;
+        HIPCHK(ctx, hipMemsetAsync(ctx->field_classes.p, 0, nh_field_classes_bytes(cap), s));
+        ctx->classes.cap = cap;
+    }
     ctx->last_fields.gen_slot = nh_launch_fields(ctx, dev_reqs, n, dev_inout_dirs, dev_out_integ, (int32_t*)ctx->gen_list.p,
-                                                 s, dev_slots);
+                                                 (int32_t*)ctx->field_classes.p, s, dev_slots);
     ctx->last_fields.n = n; ctx->last_fields.stream = s;
     HIPCHK(ctx, hipGetLastError());
     ctx->counters.field_calls++; ctx->counters.chunk_fields += (uint64_t)n;
@@ -628,7 +637,8 @@ int navhip_last_fields_split(navhip_ctx *ctx, int32_t out[2])
     int32_t generic = ctx->last_fields.n;           // (forced: no list, k_field_generic built every request)
     if(ctx->last_fields.gen_slot >= 0)
         // the counter the two kernels keep anyway: it stays until the launch after the next one zeroes it
-        HIPCHK(ctx, hipMemcpyAsync(&generic, (const int32_t*)ctx->gen_list.p + ctx->last_fields.gen_slot, sizeof(int32_t),
+        // (the REQUESTS of the classes on the list, two words behind the list's length)
+        HIPCHK(ctx, hipMemcpyAsync(&generic, (const int32_t*)ctx->gen_list.p + 2 + ctx->last_fields.gen_slot, sizeof(int32_t),
                                    hipMemcpyDeviceToHost, ctx->last_fields.stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->last_fields.stream));
     out[0] = ctx->last_fields.n - generic; out[1] = generic;

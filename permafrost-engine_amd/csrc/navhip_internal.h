@@ -253,7 +253,13 @@ struct navhip_ctx {
     int          field_kernel_mode = 0;
     // scratch for the host-buffer entry points
     nh_buf       d_dirty_list;              // chunks whose derived masks are rebuilt
-    nh_buf       gen_list;     // [2 + n] requests the BFS kernel left to k_field_generic: 2 counters, ids
+    nh_buf       gen_list;     // [NH_GEN_HEADER + n] class leaders the BFS kernel left to k_field_generic: 2 list lengths, 2 counts
+                               // of the requests they stand for, ids
+    nh_buf       field_classes; // scratch of k_field_classes (nh_field_classes_bytes): equal requests of a build call are built once.
+                               // ONE chunk-field build of a context in flight at a time, or all of them on one stream: a second
+                               // build on another stream would share the table and the lists, and so the bytes of the output
+    struct { int cap = 0; unsigned builds = 0; int last_table = 0, last_heads = 0; } classes;   // its capacity in requests, parity of the
+                               // set a build takes, what the last build used of its set (the next one zeroes that)
     unsigned     gen_launches = 0; // parity selects the counter of a launch
     // the last chunk-field build (navhip_last_fields_split): its requests, the counter of gen_list it used (-1: every
     // request went to k_field_generic, no list), the stream it runs on
@@ -286,7 +292,7 @@ static inline void nh_fill_map_view(const navhip_ctx *ctx, nh_map_view *mv)
 // every device buffer of the context that nh_ensure grows, for navhip_ctx_destroy
 template<class F> static inline void nh_ctx_each_buf(navhip_ctx *ctx, F f)
 {
-    nh_buf *one[] = {&ctx->d_dirty_list, &ctx->gen_list, &ctx->state_arrived, &ctx->state_arrived_n, &ctx->dest_query_scratch};
+    nh_buf *one[] = {&ctx->d_dirty_list, &ctx->gen_list, &ctx->field_classes, &ctx->state_arrived, &ctx->state_arrived_n, &ctx->dest_query_scratch};
     for(nh_buf *b : one) f(*b);
     for(auto &b : ctx->step.buf) f(b);
     for(auto &b : ctx->stage) f(b);
@@ -370,9 +376,13 @@ int nh_pool_slots(const navhip_ctx *ctx);
 // launched by navhip_api.hip
 void nh_launch_derive(navhip_ctx *ctx, int layer, const uint32_t *d_chunk_list, int n,
                       hipStream_t s);
-// (returns the counter of d_gen_list that holds the number of requests left to k_field_generic, -1: all of them)
+// (returns the counter of d_gen_list that holds the number of class leaders left to k_field_generic -- the requests they
+// stand for are counted two words on -- or -1: all of them.  d_classes: ctx->field_classes, nh_field_classes_bytes(
+// ctx->classes.cap) of scratch, zero when allocated)
+#define NH_GEN_HEADER 4
+size_t nh_field_classes_bytes(int cap);
 int  nh_launch_fields(navhip_ctx *ctx, const navhip_field_req *d_reqs, int n, uint8_t *d_dirs,
-                      float *d_integ, int32_t *d_gen_list, hipStream_t s,
+                      float *d_integ, int32_t *d_gen_list, int32_t *d_classes, hipStream_t s,
                       const int32_t *d_out_slot = nullptr);
 
 void nh_launch_blockers_circles(navhip_ctx *ctx, const navhip_circle *d_circles, int n, float map_x,
