@@ -820,6 +820,43 @@ int  navhip_dest_queries_dev(navhip_ctx *ctx, const navhip_dest_query *dev_q, in
                              float *dev_out_nearest_xz, int32_t *dev_out_tiles_off, int16_t *dev_out_tiles, int tiles_cap,
                              uint8_t *dev_out_status, void *stream);
 
+/* ---- the two unit queries of STATE_SURROUND_ENTITY on the device ---------------------------------------------------
+ *
+ * navhip_state_aux_in.surround_query / .surround_dest_xz (below) are the answers of M_NavObjAdjacentFrom (map.c:1061 ->
+ * n_objects_adjacent, nav.c:1682: do the unit's tiles touch the target's?) and M_NavClosestReachableAdjacentPosFrom
+ * (map.c:860 -> n_closest_adjacent_pos, nav.c:1636: the closest reachable tile next to the target, one
+ * n_closest_island_tiles flood per tile under the target's circle) from both positions the tick can test.  Both read the
+ * blockers; for a MOVABLE target these entry points answer them from the resident planes (probemask rows, islands), bit
+ * for bit with the reference.
+ *   world          n_ents, pos_xz, radius, flags, map_pos_x / _z
+ *   new_vel_xz     [n_ents][2] the ungated velocity of the step (move_work_out.ent_vel)
+ *   units, target  [nq] row k concerns unit units[k] and target row target[k] (< 0: no target).  units == NULL is the
+ *                  dense form: nq == n_ents and row i is unit i -- the sparse and the dense layouts of
+ *                  navhip_state_aux_in
+ *   out_query      [nq] NAVHIP_SQ_ADJACENT | NAVHIP_SQ_HAS_DEST_0 | NAVHIP_SQ_HAS_DEST_1 | NAVHIP_SQ_HOST.  No target: 0.
+ *                  Touching: NAVHIP_SQ_ADJACENT alone, nothing else is computed.
+ *   out_dest_xz    [nq][2][2] the closest position from pos + new velocity ([k][0]) and from pos ([k][1]): the corner of
+ *                  the winning tile; 0 where the bit is clear
+ * NAVHIP_SQ_HOST is never a wrong answer.  It comes back for: a target row >= n_ents; a target without
+ * NAVHIP_ENTITY_FLAG_MOVABLE (a static target needs its OBB, which stays the host's); ceil(radius / 4) of unit or target
+ * above 8 (radius 32); a NaN radius or position; a source off the map (the reference asserts there); a flood of the row
+ * that has to push a tile outside the window of 127 x 127 tiles centred on its target tile in front of its answer (the
+ * rule of NAVHIP_DQ_HOST).
+ * NAVHIP_ERR_ARG, with the reason in navhip_last_error, before anything is launched and with the outputs untouched: a
+ * missing array; nq < 0; the dense form with nq != n_ents; a unit row outside [0, n_ents); a unit on a layer
+ * (Entity_NavLayerWithRadius of its flags and radius) without resident cost_base, blockers and islands planes. */
+#define NAVHIP_SQ_HOST 0x80   /* out_query: not decided here; the row's other bits are 0 and its dest is 0 */
+int  navhip_surround_queries(navhip_ctx *ctx, const navhip_world *world, const float *new_vel_xz,
+                             const int32_t *units, const int32_t *target, int nq,
+                             uint8_t *out_query, float *out_dest_xz);
+/* Everything resident on the device (dev_world: a host struct of device pointers), asynchronous on `stream`, no
+ * allocation after the first call at a given nq: the dense form's outputs can be handed to navhip_state_update_aux_dev
+ * as they are.  The rows are not readable before the launch: a unit row outside the world or on a layer without
+ * resident planes comes back NAVHIP_SQ_HOST. */
+int  navhip_surround_queries_dev(navhip_ctx *ctx, const navhip_world *dev_world, const float *dev_new_vel_xz,
+                                 const int32_t *dev_units, const int32_t *dev_target, int nq,
+                                 uint8_t *dev_out_query, float *dev_out_dest_xz, void *stream);
+
 /* ---- more of entity_compute_update: the heading gate, the arms of the state switch that flags, a
  *      counter, an angle or a distance decide, the arrival overlay's settle rule, and all of it but the last in one call ----
  *
@@ -908,8 +945,9 @@ typedef struct navhip_state_aux_in {
     const int16_t  *range_tiles;      /* [..][2] absolute nav tiles (row, column)                                        */
     int32_t         n_range_rows;     /* rows of range_tiles_off (host-buffer call: sizes the transfer)                  */
     /* STATE_SURROUND_ENTITY (:2509-2567), surround_target NULL = its units stay NAVHIP_SU_HOST (as do all of them at a
-     * rate below 20 Hz).  The two nav queries on the unit-query context stay the host's, handed over per unit exactly as
-     * flock_nearest_xz is for arrived(): whether the unit already touches its target (M_NavObjAdjacentFrom, map.c:1061 --
+     * rate below 20 Hz).  The two nav queries on the unit-query context are handed over per unit exactly as
+     * flock_nearest_xz is for arrived() -- by the host, or by navhip_surround_queries[_dev] above, whose NAVHIP_SQ_HOST
+     * rows stay NAVHIP_SU_HOST here --: whether the unit already touches its target (M_NavObjAdjacentFrom, map.c:1061 --
      * or the target is gone), and the closest reachable position next to the target (M_NavClosestReachableAdjacentPosFrom,
      * map.c:860) from BOTH positions the tick can test: pos + new velocity, and pos (the heading gate zeroed the
      * velocity).  The host only needs to fill the query answers for units that reach the query (:2532-2545: the target
@@ -939,6 +977,7 @@ typedef struct navhip_state_aux_in {
 #define NAVHIP_SQ_ADJACENT   0x01   /* !entity_exists(target) || M_NavObjAdjacentFrom(map, uid, target, ctx)              */
 #define NAVHIP_SQ_HAS_DEST_0 0x02   /* M_NavClosestReachableAdjacentPosFrom(.., pos + new velocity, ..) found a position */
 #define NAVHIP_SQ_HAS_DEST_1 0x04   /* ... from pos                                                                      */
+/* (NAVHIP_SQ_HOST 0x80, above: the query was not decided on the device; a unit with a target keeps NAVHIP_SU_HOST)        */
 int  navhip_state_update_aux(navhip_ctx *ctx, const navhip_world *world, const navhip_state_aux_in *in,
                              uint8_t *inout_state, uint8_t *inout_flags, int32_t *out_wait_ticks_left);
 /* Everything resident on the device, asynchronous on `stream`. */

@@ -291,7 +291,8 @@ __global__ __launch_bounds__(256) void k_state_aux(nh_step_params P, const float
                 const int tgt = in.surround_target[i];
                 const uint8_t sq = in.surround_query[i];
                 const int flock = P.flock[i];
-                if(tgt < 0 || (sq & NAVHIP_SQ_ADJACENT)) { next = NAVHIP_STATE_ARRIVED; fl = NAVHIP_SU_SET_STATE | NAVHIP_SU_BLOCK; }
+                if(tgt >= 0 && (sq & NAVHIP_SQ_HOST)) decided = false;           // (navhip_surround_queries left the row to the host)
+                else if(tgt < 0 || (sq & NAVHIP_SQ_ADJACENT)) { next = NAVHIP_STATE_ARRIVED; fl = NAVHIP_SU_SET_STATE | NAVHIP_SU_BLOCK; }
                 else if(flock < 0) decided = false;                             // (the reference asserts a flock)
                 else{
                     const v2 np = mkv(in.new_pos_xz[2 * i], in.new_pos_xz[2 * i + 1]);

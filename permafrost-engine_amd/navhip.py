@@ -58,7 +58,7 @@ STEP_PHASES = ("sp_build", "agent_nbr", "cohesion", "coh_regroup", "agent_finish
 SU_SET_STATE, SU_BLOCK, SU_HOST = 0x01, 0x02, 0x80
 GATE_TURN, GATE_HOST = 0x01, 0x80
 SU_SET_MOVING, SU_TARGET_DIR, SU_SET_DEST, SU_SURROUND_DEST, SU_SURROUND_PREV = 0x04, 0x08, 0x10, 0x20, 0x40
-SQ_ADJACENT, SQ_HAS_DEST_0, SQ_HAS_DEST_1 = 0x01, 0x02, 0x04
+SQ_ADJACENT, SQ_HAS_DEST_0, SQ_HAS_DEST_1, SQ_HOST = 0x01, 0x02, 0x04, 0x80
 FS_MEMBER, FS_READY, FS_ASSIGNED, FS_IN_RANGE, FS_ARRIVED = 0x01, 0x02, 0x04, 0x08, 0x10
 DQ_NEAREST, DQ_TILES, DQ_HOST = 0x1, 0x2, 0x80
 DQ_MAX_TILES = 256                                                           # per query: FIELD_RES_R * 2 + FIELD_RES_C * 2
@@ -298,6 +298,9 @@ _SIGS = {
     # dest_query_kernels: the destination queries of arrived()
     "navhip_dest_queries": (_I, [_P, _P, _I, _F, _F, _P, _P, _P, _I, _P]),
     "navhip_dest_queries_dev": (_I, [_P, _P, _I, _F, _F, _P, _P, _P, _I, _P, _P]),
+    # surround_query_kernels: the two unit queries of the surround arm
+    "navhip_surround_queries": (_I, [_P, _WORLD, _P, _P, _P, _I, _P, _P]),
+    "navhip_surround_queries_dev": (_I, [_P, _WORLD, _P, _P, _P, _I, _P, _P, _P]),
     # pool_api: the resident field pool
     "navhip_pool_create": (_I, [_P, _I, _I]),
     "navhip_pool_destroy": (None, [_P]),
@@ -898,6 +901,30 @@ class NavContext(_Handle):
         navhip_state_in.flock_nearest_xz / .flock_tiles_off / .flock_tiles take."""
         self._call("navhip_dest_queries_dev", dev_ptr(d_queries), int(n), *self.map_pos(), dev_ptr(d_nearest_xz),
                    dev_ptr(d_tiles_off), dev_ptr(d_tiles), int(tiles_cap), dev_ptr(d_status), _stream(stream))
+
+    # -- surround_query_kernels: the two unit queries of the surround arm -------------------------------
+    def surround_queries(self, arrays, new_vel, target, units=None):
+        """M_NavObjAdjacentFrom and M_NavClosestReachableAdjacentPosFrom (from pos + new_vel and from pos) for movable
+        targets.  arrays: pos_xz, radius, flags of the snapshot; target [nq]: the target's row or < 0; units [nq]: the
+        rows' units, None = the dense form (row i is unit i).  Returns (query [nq] SQ_*, dest_xz [nq][2][2]): the shapes
+        of `surround` in state_update_aux."""
+        w, keep = self._world(arrays)
+        vel = _arr(new_vel, np.float32, w.n_ents, 2)
+        tgt = _arr(target, np.int32)
+        un = None if units is None else _arr(units, np.int32)
+        nq = len(tgt)
+        query, dest = np.zeros(nq, np.uint8), np.zeros((nq, 2, 2), np.float32)
+        self._call("navhip_surround_queries", C.byref(w), _hp(vel), None if un is None else _hp(un), _hp(tgt), nq,
+                   _hp(query), _hp(dest))
+        return query, dest
+
+    def surround_queries_dev(self, world, d_new_vel_xz, d_units, d_target, nq, d_query, d_dest_xz, stream=None):
+        """navhip_surround_queries_dev: `world` a World of device pointers (make_world of torch CUDA tensors), every
+        buffer a torch CUDA tensor (d_units None: the dense form), asynchronous on `stream`; the dense outputs are what
+        navhip_state_aux_in.surround_query / .surround_dest_xz take."""
+        self._call("navhip_surround_queries_dev", C.byref(world), dev_ptr(d_new_vel_xz),
+                   None if d_units is None else dev_ptr(d_units), dev_ptr(d_target), int(nq), dev_ptr(d_query),
+                   dev_ptr(d_dest_xz), _stream(stream))
 
     def state_update_aux(self, arrays, fstate, wait_ticks_left, wait_prev, new_pos_xz, state, flags, work=None,
                          ent_rot=None, target_dir=None, range_in=None, surround=None, vdes_xz=None, hz=20):
