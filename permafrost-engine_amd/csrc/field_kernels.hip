@@ -32,6 +32,7 @@
 // int->float conversion of the optional integration output, which is exact anyway).
 #include "navhip_internal.h"
 
+#include "field_cells.h"
 #include "wave_bits.h"
 
 __device__ __forceinline__ bool req_uses_bfs(const nh_map_view &map, const navhip_field_req &rq,
@@ -539,264 +540,197 @@ struct generic_lds {
     int s_list[128], s_dmin[128], s_nlist, s_D;
 };
 
-__device__ void field_generic_one(generic_lds &S, const nh_map_view &map, const navhip_field_req *reqs,
-                                  int ri, uint8_t *dirs, float *integ, int force_generic,
-                                  const int32_t *out_slot, const nh_class_view &cv)
-{
-    uint32_t (&dist)[NH_CELLS] = S.dist;
-    uint8_t (&pc)[NH_CELLS] = S.pc;
-    uint8_t (&raw)[NH_CELLS] = S.raw;
-    uint8_t (&fl)[NH_CELLS] = S.fl;
-    int (&s_list)[128] = S.s_list;
-    int (&s_dmin)[128] = S.s_dmin;
-    int &s_nlist = S.s_nlist, &s_D = S.s_D;
-
-    const int t = threadIdx.x;
-    if(cv.leader_of[ri] != ri) return;                    // its class's leader stores this request's copy
-    navhip_field_req rq = reqs[ri];
-    if(req_uses_bfs(map, rq, force_generic)) return;      // the BFS kernel owns this request
-    if(!req_prepare(map, rq)) return;
-
-    const nh_layer_view &L = map.layers[rq.layer];
-    const size_t cbase = (size_t)((int)rq.chunk_r * map.w + rq.chunk_c) << 12;
-    const bool faction = rq.faction_id != NAVHIP_FACTION_ID_NONE;
+// The phases of one build, in the order field_generic_one runs them.  Every thread of the workgroup enters every phase
+// it is sent to (the conditions are uniform), so the barriers inside are reached by all 256.  Thread t owns the cells
+// i = k*256 + t, k < 16 (conflict-free LDS layout).
+struct generic_job {
+    navhip_field_req rq;
+    const nh_layer_view *L;
+    size_t cbase;               // of the chunk in the layer's planes
     // repair builds: N_FlowFieldUpdateToNearestPathable (field.c:2247) and
     // N_FlowFieldUpdateIslandToNearest (field.c:2307); both work on an existing field
-    const bool modeA = rq.type == NAVHIP_TARGET_NEAREST_PATHABLE;
-    const bool modeB = !modeA && (rq.flags & NAVHIP_REQ_ISLAND_NEAREST) != 0;
+    bool nearest_pathable, island_nearest;
+};
 
-    // ---- stage cost + passability: cell index i = k*256 + t (conflict-free LDS layout) --------
+// ---- stage cost + passability ------------------------------------------------------------------
+__device__ __forceinline__ void generic_stage(generic_lds &S, const generic_job &J)
+{
+    const int t = threadIdx.x;
+    const bool faction = J.rq.faction_id != NAVHIP_FACTION_ID_NONE;
 #pragma unroll 4
     for(int k = 0; k < 16; k++) {
         int i = k * 256 + t;
-        uint32_t cst = L.cost[cbase + i];
-        uint32_t blk = L.blockers ? L.blockers[cbase + i] : 0;
-        bool passable;
-        if(cst == NAVHIP_COST_IMPASSABLE) {
-            passable = false;
-        }else if(!faction) {
-            passable = (blk == 0);                                        // field.c:117
-        }else{
-            // field_tile_passable_no_enemies, field.c:179-201
-            bool enemies_only = true;
-            if(L.factions) {
-                const uint8_t *fp = L.factions + cbase * NAVHIP_MAX_FACTIONS + i;
-                for(int f = 0; f < NAVHIP_MAX_FACTIONS; f++) {
-                    if(fp[(size_t)f << 12] && !(rq.enemies & (1u << f))) { enemies_only = false; break; }
-                }
-            }
-            passable = enemies_only || (blk == 0);
-        }
-        pc[i] = passable ? (uint8_t)cst : (uint8_t)NAVHIP_COST_IMPASSABLE;
-        raw[i] = (uint8_t)cst;
-        fl[i] = (cst != NAVHIP_COST_IMPASSABLE && blk == 0) ? 1 : 0;
-        dist[i] = NH_INF_U32;
+        uint32_t cst = J.L->cost[J.cbase + i];
+        uint32_t blk = J.L->blockers ? J.L->blockers[J.cbase + i] : 0;
+        const bool passable = field_cell_enterable(*J.L, J.cbase + i, cst, blk, faction, J.rq.enemies);
+        S.pc[i] = passable ? (uint8_t)cst : (uint8_t)NAVHIP_COST_IMPASSABLE;
+        S.raw[i] = (uint8_t)cst;
+        S.fl[i] = (cst != NAVHIP_COST_IMPASSABLE && blk == 0) ? 1 : 0;
+        S.dist[i] = NH_INF_U32;
     }
-    if(t == 0) { s_nlist = 0; s_D = 0x7fffffff; }
-    if(t < 128) s_dmin[t] = 0x7fffffff;
+    if(t == 0) { S.s_nlist = 0; S.s_D = 0x7fffffff; }
+    if(t < 128) S.s_dmin[t] = 0x7fffffff;
     __syncthreads();
+}
 
-    if(modeA) {
-        // ---- field_passable_frontier (field.c:1441): flood the NON-passable 4-connected region of
-        // the start tile; the passable tiles bordering it are the frontier
-        const int start = rq.tile_r * 64 + rq.tile_c;
-        if(t == 0) fl[start] |= 2;
-        __syncthreads();
-        if(!(fl[start] & 1)) {
-            for(;;) {
-                int changed = 0;
-#pragma unroll 4
-                for(int k = 0; k < 16; k++) {
-                    int i = k * 256 + t;
-                    if(fl[i] & 3) continue;                 // passable, or already in the region
-                    int r = i >> 6, c = i & 63;
-                    bool nb = (r > 0 && (fl[i - 64] & 2)) || (r < 63 && (fl[i + 64] & 2))
-                           || (c > 0 && (fl[i - 1] & 2)) || (c < 63 && (fl[i + 1] & 2));
-                    if(nb) { fl[i] |= 2; changed = 1; }
-                }
-                if(!__syncthreads_or(changed)) break;
-            }
-#pragma unroll 4
-            for(int k = 0; k < 16; k++) {
-                int i = k * 256 + t;
-                if(!(fl[i] & 1)) continue;
-                int r = i >> 6, c = i & 63;
-                bool nb = (r > 0 && (fl[i - 64] & 2)) || (r < 63 && (fl[i + 64] & 2))
-                       || (c > 0 && (fl[i - 1] & 2)) || (c < 63 && (fl[i + 1] & 2));
-                if(nb) dist[i] = 0;
-            }
-        }else if(t == 0) {
-            dist[start] = 0;                                // a passable start is its own frontier
-        }
-        __syncthreads();
-        // ---- field_build_integration_nonpass (field.c:643): relax only NON-passable tiles, step
-        // cost = cost_base of the tile entered
+// has the cell a 4-neighbour in the flooded region (fl bit 1)?
+__device__ __forceinline__ bool generic_beside_region(const generic_lds &S, int i)
+{
+    const int r = i >> 6, c = i & 63;
+    return (r > 0 && (S.fl[i - 64] & 2)) || (r < 63 && (S.fl[i + 64] & 2))
+        || (c > 0 && (S.fl[i - 1] & 2)) || (c < 63 && (S.fl[i + 1] & 2));
+}
+
+// ---- nearest pathable: field_passable_frontier (field.c:1441) floods the NON-passable 4-connected region of the
+// start tile, the passable tiles bordering it are the frontier; then field_build_integration_nonpass (field.c:643)
+// relaxes only NON-passable tiles, step cost = cost_base of the tile entered
+__device__ __forceinline__ void generic_nearest_pathable(generic_lds &S, const generic_job &J)
+{
+    const int t = threadIdx.x;
+    const int start = J.rq.tile_r * 64 + J.rq.tile_c;
+    if(t == 0) S.fl[start] |= 2;
+    __syncthreads();
+    if(!(S.fl[start] & 1)) {
         for(;;) {
             int changed = 0;
 #pragma unroll 4
             for(int k = 0; k < 16; k++) {
                 int i = k * 256 + t;
-                if(fl[i] & 1) continue;
-                int r = i >> 6, c = i & 63;
-                uint32_t m = NH_INF_U32;
-                if(r > 0)  m = min(m, dist[i - 64]);
-                if(r < 63) m = min(m, dist[i + 64]);
-                if(c > 0)  m = min(m, dist[i - 1]);
-                if(c < 63) m = min(m, dist[i + 1]);
-                if(m < NH_INF_U32) {
-                    uint32_t nd = m + raw[i];
-                    if(nd < dist[i]) { dist[i] = nd; changed = 1; }
-                }
+                if(S.fl[i] & 3) continue;                 // passable, or already in the region
+                if(generic_beside_region(S, i)) { S.fl[i] |= 2; changed = 1; }
             }
             if(!__syncthreads_or(changed)) break;
+        }
+#pragma unroll 4
+        for(int k = 0; k < 16; k++) {
+            int i = k * 256 + t;
+            if((S.fl[i] & 1) && generic_beside_region(S, i)) S.dist[i] = 0;
+        }
+    }else if(t == 0) {
+        S.dist[start] = 0;                                // a passable start is its own frontier
+    }
+    __syncthreads();
+    field_relax_to_fixpoint(field_grid_chunk{}, S.dist, [&](int i) {
+        return (S.fl[i] & 1) ? FIELD_NO_STEP : (uint32_t)S.raw[i];
+    });
+}
+
+// ---- seeds (field_initial_frontier, field.c:1372): distance 0, or -- for the island repair -- the list of frontier
+// tiles from which the nearest island tiles are looked up
+__device__ __forceinline__ void generic_seeds(generic_lds &S, const nh_map_view &map, const generic_job &J)
+{
+    const int t = threadIdx.x;
+    const navhip_field_req &rq = J.rq;
+    if(rq.type == NAVHIP_TARGET_TILE) {
+        if(t == 0) {
+            int i = rq.tile_r * 64 + rq.tile_c;
+            if(S.pc[i] != NAVHIP_COST_IMPASSABLE) {
+                if(J.island_nearest) S.s_list[S.s_nlist++] = i; else S.dist[i] = 0;
+            }
         }
     }else{
-        // ---- seeds (field_initial_frontier, field.c:1372); for the island repair they only form
-        // the frontier from which the nearest island tiles are looked up
-        if(rq.type == NAVHIP_TARGET_TILE) {
-            if(t == 0) {
-                int i = rq.tile_r * 64 + rq.tile_c;
-                if(pc[i] != NAVHIP_COST_IMPASSABLE) {
-                    if(modeB) s_list[s_nlist++] = i; else dist[i] = 0;
-                }
+        int nr = rq.port_r1 - rq.port_r0 + 1, nc = rq.port_c1 - rq.port_c0 + 1;
+        for(int j = t; j < nr * nc; j += 256) {
+            int r = rq.port_r0 + j / nc, c = rq.port_c0 + j % nc;
+            if(portal_seed(map, rq, r, c, S.pc[r * 64 + c] != NAVHIP_COST_IMPASSABLE)) {
+                if(J.island_nearest) { int p = atomicAdd(&S.s_nlist, 1); if(p < 128) S.s_list[p] = r * 64 + c; }
+                else S.dist[r * 64 + c] = 0;
             }
-        }else{
-            int nr = rq.port_r1 - rq.port_r0 + 1, nc = rq.port_c1 - rq.port_c0 + 1;
-            for(int j = t; j < nr * nc; j += 256) {
-                int r = rq.port_r0 + j / nc, c = rq.port_c0 + j % nc;
-                if(portal_seed(map, rq, r, c, pc[r * 64 + c] != NAVHIP_COST_IMPASSABLE)) {
-                    if(modeB) { int p = atomicAdd(&s_nlist, 1); if(p < 128) s_list[p] = r * 64 + c; }
-                    else dist[r * 64 + c] = 0;
-                }
-            }
-        }
-        __syncthreads();
-        if(modeB) {
-            // completely blocked target: retry ignoring blockers (field.c:2352-2355; only the tile
-            // frontier honours ignoreblock, field.c:1112-1115)
-            if(t == 0 && s_nlist == 0 && rq.type == NAVHIP_TARGET_TILE)
-                s_list[s_nlist++] = rq.tile_r * 64 + rq.tile_c;
-            __syncthreads();
-            const int nl = min(s_nlist, 128);
-            const uint16_t *li = L.local_islands + cbase;
-            const uint16_t *gi = L.islands ? L.islands + cbase : nullptr;
-            const uint32_t want = rq.aux_iid;
-            // field_closest_tiles_local (field.c:1010) for every frontier tile: the qualifying tiles
-            // (passable, unblocked, local island `want`, same global island as the frontier tile) at
-            // the minimum Manhattan distance
-            for(int q = 0; q < nl; q++) {
-                const int f = s_list[q], fr = f >> 6, fc = f & 63;
-                const uint32_t giid = gi ? gi[f] : NAVHIP_ISLAND_NONE;
-                int best = 0x7fffffff;
-#pragma unroll 4
-                for(int k = 0; k < 16; k++) {
-                    int i = k * 256 + t;
-                    if(!(fl[i] & 1)) continue;
-                    if(want != NAVHIP_ISLAND_NONE && li[i] != want) continue;
-                    if(giid != NAVHIP_ISLAND_NONE && gi[i] != giid) continue;
-                    int d = abs((i >> 6) - fr) + abs((i & 63) - fc);
-                    best = min(best, d);
-                }
-                if(best < 0x7fffffff) atomicMin(&s_dmin[q], best);
-            }
-            __syncthreads();
-            if(t == 0) {
-                int D = 0x7fffffff;
-                for(int q = 0; q < nl; q++) D = min(D, s_dmin[q]);
-                s_D = D;
-            }
-            __syncthreads();
-            const int D = s_D;
-            if(D < 0x7fffffff) {
-                for(int q = 0; q < nl; q++) {
-                    if(s_dmin[q] != D) continue;
-                    const int f = s_list[q], fr = f >> 6, fc = f & 63;
-                    const uint32_t giid = gi ? gi[f] : NAVHIP_ISLAND_NONE;
-#pragma unroll 4
-                    for(int k = 0; k < 16; k++) {
-                        int i = k * 256 + t;
-                        if(!(fl[i] & 1)) continue;
-                        if(want != NAVHIP_ISLAND_NONE && li[i] != want) continue;
-                        if(giid != NAVHIP_ISLAND_NONE && gi[i] != giid) continue;
-                        if(abs((i >> 6) - fr) + abs((i & 63) - fc) == D) dist[i] = 0;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-
-        // ---- chaotic (in-place) min-plus relaxation to the fixpoint --------------------------
-        // d[x] = min(d[x], min_{4-nbrs y} d[y] + cost[x]) for passable x.  Values only decrease and
-        // never drop below the true shortest distance, so the fixpoint is the Dijkstra result of
-        // field_build_integration bit for bit; an iteration in which no thread lowered anything
-        // proves every read saw final values.
-        for(;;) {
-            int changed = 0;
-#pragma unroll 4
-            for(int k = 0; k < 16; k++) {
-                int i = k * 256 + t;
-                uint32_t cst = pc[i];
-                if(cst == NAVHIP_COST_IMPASSABLE) continue;
-                int r = i >> 6, c = i & 63;
-                uint32_t m = NH_INF_U32;
-                if(r > 0)  m = min(m, dist[i - 64]);
-                if(r < 63) m = min(m, dist[i + 64]);
-                if(c > 0)  m = min(m, dist[i - 1]);
-                if(c < 63) m = min(m, dist[i + 1]);
-                if(m < NH_INF_U32) {
-                    uint32_t nd = m + cst;
-                    if(nd < dist[i]) { dist[i] = nd; changed = 1; }
-                }
-            }
-            if(!__syncthreads_or(changed)) break;
         }
     }
+    __syncthreads();
+}
 
-    // ---- bake (field_flow_dir, field.c:355-433) + fixup; result staged in pc[] ----------------
-    const bool inout = (rq.flags & NAVHIP_REQ_INOUT) != 0 || modeA || modeB;
+// field_closest_tiles_local (field.c:1010) chooses among the tiles that are passable, unblocked, on local island `want`
+// and on the global island `giid` of the frontier tile f: the Manhattan distance from f to such a tile i, else 0x7fffffff
+struct generic_island_filter { const uint16_t *li, *gi; uint32_t want; };
+__device__ __forceinline__ int generic_island_dist(const generic_lds &S, const generic_island_filter &F, uint32_t giid, int f, int i)
+{
+    if(!(S.fl[i] & 1)) return 0x7fffffff;
+    if(F.want != NAVHIP_ISLAND_NONE && F.li[i] != F.want) return 0x7fffffff;
+    if(giid != NAVHIP_ISLAND_NONE && F.gi[i] != giid) return 0x7fffffff;
+    return abs((i >> 6) - (f >> 6)) + abs((i & 63) - (f & 63));
+}
+
+// ---- island nearest: the seeds are, for every frontier tile, its qualifying tiles at the minimum Manhattan distance
+// (field_closest_tiles_local), of the frontier tiles whose minimum is the least
+__device__ __forceinline__ void generic_island_seeds(generic_lds &S, const generic_job &J)
+{
+    const int t = threadIdx.x;
+    // completely blocked target: retry ignoring blockers (field.c:2352-2355; only the tile
+    // frontier honours ignoreblock, field.c:1112-1115)
+    if(t == 0 && S.s_nlist == 0 && J.rq.type == NAVHIP_TARGET_TILE)
+        S.s_list[S.s_nlist++] = J.rq.tile_r * 64 + J.rq.tile_c;
+    __syncthreads();
+    const int nl = min(S.s_nlist, 128);
+    const generic_island_filter F = {J.L->local_islands + J.cbase, J.L->islands ? J.L->islands + J.cbase : nullptr, J.rq.aux_iid};
+    for(int q = 0; q < nl; q++) {
+        const int f = S.s_list[q];
+        const uint32_t giid = F.gi ? F.gi[f] : NAVHIP_ISLAND_NONE;
+        int best = 0x7fffffff;
+#pragma unroll 4
+        for(int k = 0; k < 16; k++) best = min(best, generic_island_dist(S, F, giid, f, k * 256 + t));
+        if(best < 0x7fffffff) atomicMin(&S.s_dmin[q], best);
+    }
+    __syncthreads();
+    if(t == 0) {
+        int D = 0x7fffffff;
+        for(int q = 0; q < nl; q++) D = min(D, S.s_dmin[q]);
+        S.s_D = D;
+    }
+    __syncthreads();
+    const int D = S.s_D;
+    if(D < 0x7fffffff) {
+        for(int q = 0; q < nl; q++) {
+            if(S.s_dmin[q] != D) continue;
+            const int f = S.s_list[q];
+            const uint32_t giid = F.gi ? F.gi[f] : NAVHIP_ISLAND_NONE;
+#pragma unroll 4
+            for(int k = 0; k < 16; k++) {
+                const int i = k * 256 + t;
+                if(generic_island_dist(S, F, giid, f, i) == D) S.dist[i] = 0;       // (D < 0x7fffffff)
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// (debug / parity output, indexed by request)
+__device__ __forceinline__ void generic_store_integ(float *integ, int req, int i, uint32_t d)
+{
+    integ[((size_t)req << 12) + i] = (d >= NH_INF_U32) ? __builtin_inff() : (float)d;
+}
+
+// ---- bake (field_flow_dir) + fixup, staged in pc[]; the tile goes to the request's slot and to every member's ----
+__device__ __forceinline__ void generic_bake_store(generic_lds &S, const generic_job &J, int ri, uint8_t *dirs,
+                                                   float *integ, const int32_t *out_slot, const nh_class_view &cv)
+{
+    const int t = threadIdx.x;
+    const navhip_field_req &rq = J.rq;
+    const bool inout = (rq.flags & NAVHIP_REQ_INOUT) != 0 || J.nearest_pathable || J.island_nearest;
     uint8_t *out = dirs + ((size_t)(out_slot ? out_slot[ri] : ri) << 12);
     const uint32_t fixdir = (rq.type == NAVHIP_TARGET_PORTAL) ? portal_fix_dir(rq) : NAVHIP_FD_NONE;
     uint8_t res[16];
 #pragma unroll 4
     for(int k = 0; k < 16; k++) {
         int i = k * 256 + t;
-        int r = i >> 6, c = i & 63;
-        uint32_t d = dist[i];
+        uint32_t d = S.dist[i];
         uint32_t dir;
         if(d >= NH_INF_U32) {
             dir = inout ? out[i] : NAVHIP_FD_NONE;
         }else if(d == 0) {
-            dir = modeA ? out[i] : fixdir;           // field.c:2297: frontier tiles are left alone
+            dir = J.nearest_pathable ? out[i] : fixdir;     // field.c:2297: frontier tiles are left alone
         }else{
-            const uint32_t I = NH_INF_U32;
-            uint32_t dn = r > 0  ? dist[i - 64] : I, ds = r < 63 ? dist[i + 64] : I;
-            uint32_t dw = c > 0  ? dist[i - 1]  : I, de = c < 63 ? dist[i + 1]  : I;
-            uint32_t dnw = (r > 0  && c > 0)  ? dist[i - 65] : I;
-            uint32_t dne = (r > 0  && c < 63) ? dist[i - 63] : I;
-            uint32_t dsw = (r < 63 && c > 0)  ? dist[i + 63] : I;
-            uint32_t dse = (r < 63 && c < 63) ? dist[i + 65] : I;
-            uint32_t mc = min(min(dn, ds), min(dw, de));
-            if(dn < I && dw < I) mc = min(mc, dnw);
-            if(dn < I && de < I) mc = min(mc, dne);
-            if(ds < I && dw < I) mc = min(mc, dsw);
-            if(ds < I && de < I) mc = min(mc, dse);
-            if(dn == mc)       dir = NAVHIP_FD_N;
-            else if(ds == mc)  dir = NAVHIP_FD_S;
-            else if(de == mc)  dir = NAVHIP_FD_E;
-            else if(dw == mc)  dir = NAVHIP_FD_W;
-            else if(dnw == mc) dir = NAVHIP_FD_NW;
-            else if(dne == mc) dir = NAVHIP_FD_NE;
-            else if(dsw == mc) dir = NAVHIP_FD_SW;
-            else               dir = NAVHIP_FD_SE;
+            dir = field_flow_dir(field_grid_chunk{}, S.dist, i);
         }
         res[k] = (uint8_t)dir;
-        if(integ) integ[((size_t)ri << 12) + i] = (d >= NH_INF_U32) ? __builtin_inff() : (float)d;
+        if(integ) generic_store_integ(integ, ri, i, d);
     }
     __syncthreads();            // every read of pc[] (none left) / out[] done before overwrite
 #pragma unroll
-    for(int k = 0; k < 16; k++) pc[k * 256 + t] = res[k];
+    for(int k = 0; k < 16; k++) S.pc[k * 256 + t] = res[k];
     __syncthreads();
-    const uint4 tile = *(const uint4*)(pc + t * 16);
+    const uint4 tile = *(const uint4*)(S.pc + t * 16);
     *(uint4*)(out + t * 16) = tile;
     // the same tile (and integration field: dist[] is final) for every other member of the class, as in k_field_bfs
     int32_t member = cv.head[ri];
@@ -809,13 +743,35 @@ __device__ void field_generic_one(generic_lds &S, const nh_map_view &map, const 
         *(uint4*)(o + t * 16) = tile;
         if(integ) {
 #pragma unroll 4
-            for(int k = 0; k < 16; k++) {
-                const int i = k * 256 + t;
-                const uint32_t d = dist[i];
-                integ[((size_t)m << 12) + i] = (d >= NH_INF_U32) ? __builtin_inff() : (float)d;
-            }
+            for(int k = 0; k < 16; k++) generic_store_integ(integ, m, k * 256 + t, S.dist[k * 256 + t]);
         }
     }
+}
+
+__device__ void field_generic_one(generic_lds &S, const nh_map_view &map, const navhip_field_req *reqs,
+                                  int ri, uint8_t *dirs, float *integ, int force_generic,
+                                  const int32_t *out_slot, const nh_class_view &cv)
+{
+    // (all three returns are uniform over the workgroup: no thread is left behind at a barrier below)
+    if(cv.leader_of[ri] != ri) return;                    // its class's leader stores this request's copy
+    generic_job J;
+    J.rq = reqs[ri];
+    if(req_uses_bfs(map, J.rq, force_generic)) return;    // the BFS kernel owns this request
+    if(!req_prepare(map, J.rq)) return;
+    J.L = &map.layers[J.rq.layer];
+    J.cbase = (size_t)((int)J.rq.chunk_r * map.w + J.rq.chunk_c) << 12;
+    J.nearest_pathable = J.rq.type == NAVHIP_TARGET_NEAREST_PATHABLE;
+    J.island_nearest = !J.nearest_pathable && (J.rq.flags & NAVHIP_REQ_ISLAND_NEAREST) != 0;
+
+    generic_stage(S, J);
+    if(J.nearest_pathable) {
+        generic_nearest_pathable(S, J);
+    }else{
+        generic_seeds(S, map, J);
+        if(J.island_nearest) generic_island_seeds(S, J);
+        field_relax_to_fixpoint(field_grid_chunk{}, S.dist, field_cost_bytes{S.pc});
+    }
+    generic_bake_store(S, J, ri, dirs, integ, out_slot, cv);
 }
 
 // The launch is a fixed, small grid: workgroups stride over the list of class leaders the BFS kernel

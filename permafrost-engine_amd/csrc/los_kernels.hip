@@ -23,6 +23,7 @@
 // LOS fields are built once per (destination, chunk) when a path is planned and then cached
 // (nav.c:1840-1847,2026-2039), so this kernel is latency- not throughput-critical.
 #include "navhip_internal.h"
+#include "field_cells.h"
 
 #define LF_VISIBLE   0x01      /* struct LOS_field bit 0 (field.h:48-54)                     */
 #define LF_WFB       0x02      /* struct LOS_field bit 1: wavefront_blocked                  */
@@ -143,20 +144,7 @@ __global__ __launch_bounds__(64) void k_los_field(nh_map_view map, const navhip_
         const int i = k * 64 + lane;
         const uint32_t cst = L.cost[cbase + i];
         const uint32_t blk = L.blockers ? L.blockers[cbase + i] : 0;
-        bool passable;
-        if(cst == NAVHIP_COST_IMPASSABLE) {
-            passable = false;
-        }else if(!faction) {
-            passable = blk == 0;
-        }else{
-            bool enemies_only = true;
-            if(L.factions) {
-                const uint8_t *fp = L.factions + cbase * NAVHIP_MAX_FACTIONS + i;
-                for(int f = 0; f < NAVHIP_MAX_FACTIONS; f++)
-                    if(fp[(size_t)f << 12] && !(rq.enemies & (1u << f))) { enemies_only = false; break; }
-            }
-            passable = enemies_only || blk == 0;
-        }
+        const bool passable = field_cell_enterable(L, cbase + i, cst, blk, faction, rq.enemies);
         uint8_t v = 0;
         if(!passable || cst > 1) v |= LF_COSTLY;
         if(cst == NAVHIP_COST_IMPASSABLE || blk > 0) v |= LF_RAWBLK;

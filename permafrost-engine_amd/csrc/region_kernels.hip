@@ -17,6 +17,7 @@
 // (96x96: 45 KB, 128x128: 80 KB); chaotic min-plus relaxation to the integer-exact fixpoint, then
 // the bake with the reference's neighbour priority.
 #include "navhip_internal.h"
+#include "field_cells.h"
 
 static_assert(sizeof(navhip_region_req) == 32, "navhip_region_req must stay 32 bytes");
 
@@ -42,22 +43,8 @@ __global__ __launch_bounds__(256) void k_region_field(nh_map_view map, const nav
             const size_t cell = ((size_t)((ar >> 6) * map.w + (ac >> 6)) << 12) + (ar & 63) * 64 + (ac & 63);
             const uint32_t cst = L.cost[cell];
             const uint32_t blk = L.blockers ? L.blockers[cell] : 0;
-            bool passable;
-            if(cst == NAVHIP_COST_IMPASSABLE) {
-                passable = false;
-            }else if(rq.enemies == 0) {
-                passable = blk == 0;                                 // field_tile_passable
-            }else{
-                bool enemies_only = true;                            // field_tile_passable_no_enemies
-                if(L.factions) {
-                    const size_t cb = (size_t)((ar >> 6) * map.w + (ac >> 6)) << 12;
-                    const uint8_t *fp = L.factions + cb * NAVHIP_MAX_FACTIONS + (ar & 63) * 64 + (ac & 63);
-                    for(int f = 0; f < NAVHIP_MAX_FACTIONS; f++)
-                        if(fp[(size_t)f << 12] && !(rq.enemies & (1u << f))) { enemies_only = false; break; }
-                }
-                passable = enemies_only || blk == 0;
-            }
-            if(passable) v = (uint8_t)cst;
+            // (a job "has a faction" when it names enemies)
+            if(field_cell_enterable(L, cell, cst, blk, rq.enemies != 0, rq.enemies)) v = (uint8_t)cst;
         }
         pc[i] = v;
         dist[i] = NH_INF_U32;
@@ -79,24 +66,8 @@ __global__ __launch_bounds__(256) void k_region_field(nh_map_view map, const nav
     __syncthreads();
 
     // ---- relaxation to the fixpoint (== Dijkstra distances, integer exact) ---------------------
-    for(;;) {
-        int changed = 0;
-        for(int i = t; i < cells; i += 256) {
-            const uint32_t cst = pc[i];
-            if(cst == NAVHIP_COST_IMPASSABLE) continue;
-            const int r = i / dim, c = i % dim;
-            uint32_t m = NH_INF_U32;
-            if(r > 0)       m = min(m, dist[i - dim]);
-            if(r < dim - 1) m = min(m, dist[i + dim]);
-            if(c > 0)       m = min(m, dist[i - 1]);
-            if(c < dim - 1) m = min(m, dist[i + 1]);
-            if(m < NH_INF_U32) {
-                const uint32_t nd = m + cst;
-                if(nd < dist[i]) { dist[i] = nd; changed = 1; }
-            }
-        }
-        if(!__syncthreads_or(changed)) break;
-    }
+    const field_grid_square g = {dim};
+    field_relax_to_fixpoint(g, dist, field_cost_bytes{pc});
 
     // ---- bake ---------------------------------------------------------------------------------
     uint8_t *o = out + (size_t)ri * out_stride;
@@ -122,26 +93,7 @@ __global__ __launch_bounds__(256) void k_region_field(nh_map_view map, const nav
             }else if(d == 0) {
                 dir = NAVHIP_FD_NONE;
             }else{
-                const uint32_t I = NH_INF_U32;
-                const uint32_t dn = r > 0 ? dist[i - dim] : I, ds = r < dim - 1 ? dist[i + dim] : I;
-                const uint32_t dw = c > 0 ? dist[i - 1] : I,   de = c < dim - 1 ? dist[i + 1] : I;
-                const uint32_t dnw = (r > 0 && c > 0) ? dist[i - dim - 1] : I;
-                const uint32_t dne = (r > 0 && c < dim - 1) ? dist[i - dim + 1] : I;
-                const uint32_t dsw = (r < dim - 1 && c > 0) ? dist[i + dim - 1] : I;
-                const uint32_t dse = (r < dim - 1 && c < dim - 1) ? dist[i + dim + 1] : I;
-                uint32_t mc = min(min(dn, ds), min(dw, de));
-                if(dn < I && dw < I) mc = min(mc, dnw);
-                if(dn < I && de < I) mc = min(mc, dne);
-                if(ds < I && dw < I) mc = min(mc, dsw);
-                if(ds < I && de < I) mc = min(mc, dse);
-                if(dn == mc)       dir = NAVHIP_FD_N;
-                else if(ds == mc)  dir = NAVHIP_FD_S;
-                else if(de == mc)  dir = NAVHIP_FD_E;
-                else if(dw == mc)  dir = NAVHIP_FD_W;
-                else if(dnw == mc) dir = NAVHIP_FD_NW;
-                else if(dne == mc) dir = NAVHIP_FD_NE;
-                else if(dsw == mc) dir = NAVHIP_FD_SW;
-                else               dir = NAVHIP_FD_SE;
+                dir = field_flow_dir(g, dist, i);
             }
             if(window) {
                 if(write) byte = (uint8_t)dir; else keep_byte = true;

@@ -415,6 +415,17 @@ def region_cases(nav, grid, seed, n_each=6, dim=96):
     return reqs, S, O, np.stack(inout), np.stack(exp)
 
 
+def small_region_world():
+    """[128, 128] u8 cost grid of 2 x 2 chunks, open but for a few walls and cost-3 tiles at the map's corners and round
+    the chunk corner (64, 64): under the regions of a few tiles a side that the region-field tests build there."""
+    grid = np.ones((128, 128), np.uint8)
+    for r, c in ((0, 1), (2, 0), (62, 63), (64, 65), (65, 62), (126, 125), (1, 63), (4, 66)):
+        grid[r, c] = 0xff
+    for r, c in ((1, 1), (63, 64), (66, 63), (125, 126), (2, 65)):
+        grid[r, c] = 3
+    return grid
+
+
 def region_reqs_to(dtype, reqs):
     out = np.zeros(len(reqs), dtype)
     for i, r in enumerate(reqs):

@@ -246,6 +246,34 @@ def test_region_fields_over_serpentine_and_spiral(navlib):
     ctx.close()
 
 
+def test_window_fields_of_regions_smaller_than_a_chunk(navlib):
+    """out_mode 1 (the window written in place into a 64 x 64 field) over regions of 2 x 2 and 6 x 6 tiles: the window is
+    the whole region then, its rows 64 bytes apart, and every border test of the relaxation and the bake is most of the
+    region.  The reference builds such fields over 64- and 128-wide regions only (field_update_zone, field.c:1835), so
+    the expected bytes are the restatement's, which tests/test_oracle_cpu.py pins to the reference."""
+    cost = cases.synth.to_chunks(cases.small_region_world())
+    # (side, base tile, seed tile): round the chunk corner, off the map at both ends, one row of two on the map
+    regions = [(2, (63, 63), (64, 63)), (6, (61, 61), (66, 61)), (6, (-2, -2), (0, 2)), (6, (123, 123), (127, 127)),
+               (2, (-1, 4), (0, 4))]
+    reqs = [dict(out_mode=1, base_abs_r=b[0], base_abs_c=b[1], rdim=d, cdim=d, roff=0, coff=0, seed_begin=k, seed_count=1)
+            for k, (d, b, _s) in enumerate(regions)]
+    seeds = np.array([s for _d, _b, s in regions], np.int16)
+    inout = np.zeros((len(reqs), 8192), np.uint8)
+    inout[:, :4096] = np.random.RandomState(5).randint(0, 9, (len(reqs), 4096))
+    onav = navoracle.OracleNav(cost, np.zeros(cost.shape, np.uint16))
+    exp = onav.build_region_fields(cases.region_reqs_to(navoracle.REGION_REQ_DTYPE, reqs), seeds, None, inout=inout)
+    for k, (d, _b, _s) in enumerate(regions):
+        win = np.zeros((64, 64), bool)
+        win[:d, :d] = True
+        changed = exp[k, :4096].reshape(64, 64) != inout[k, :4096].reshape(64, 64)
+        assert changed[win].any() and not changed[~win].any(), regions[k]
+    ctx = navlib.NavContext(2, 2)
+    ctx.upload_plane(0, navlib.PLANE_COST_BASE, cost)
+    got = ctx.build_region_fields(cases.region_reqs_to(navlib.REGION_REQ_DTYPE, reqs), seeds, None, inout=inout)
+    assert np.array_equal(got, exp)
+    ctx.close()
+
+
 def los_shape_requests():
     """(cost planes, LOS requests) on a 2 x 2 map with the serpentine at (0, 1) and the checkerboard at (1, 1): pairs of a
     destination chunk's field and one chained neighbour -- targets inside the shapes (walls on every side: LOS corners

@@ -117,7 +117,7 @@ def test_region_fields_match_reference(navlib, seed, blk):
 @pytest.mark.parametrize("seed", [1, 2])
 def test_attacking_path_fields_match_reference(navlib, seed):
     """faction_id != NONE: tiles blocked only by enemy factions are passable
-    (field_tile_passable_no_enemies, field.c:179); served by the generic kernel."""
+    (field_tile_passable_no_enemies, field.c:179); served by the BFS kernel in mode 0 (the chunks have unit costs)."""
     from oracle import pfref
     grid, nav, reqs, enemies, exp_dirs, exp_integ = cases.faction_cases(seed)
     ctx = navlib.NavContext(3, 3)
@@ -140,7 +140,7 @@ def test_region_field_with_enemy_mask(navlib):
     rng = np.random.RandomState(0)
     cells = cases.synth.passable_cells(grid)
     dim = 96
-    reqs, seeds, exp = [], [], []
+    reqs, seeds, exp, masked_differs = [], [], [], []
     for k in range(6):
         cen = cells[rng.randint(len(cells))]
         tgt = np.clip(cen + rng.randint(-30, 31, 2), 0, [191, 191])
@@ -148,9 +148,12 @@ def test_region_field_with_enemy_mask(navlib):
         base = np.where(tgt - base >= dim, tgt - (dim - 1), base)
         e = enemies if k % 2 == 0 else 0
         exp.append(nav.cell_arrival_field(dim, tgt, cen, enemies=e))
+        if e:
+            masked_differs.append(not np.array_equal(exp[k], nav.cell_arrival_field(dim, tgt, cen, enemies=0)))
         reqs.append(dict(out_mode=0, enemies=e, base_abs_r=int(base[0]), base_abs_c=int(base[1]), rdim=dim,
                          cdim=dim, seed_begin=len(seeds), seed_count=1))
         seeds.append(tgt)
+    assert any(masked_differs), "the mask changes none of the reference's fields: the test would not see it ignored"
     ctx = navlib.NavContext(3, 3)
     ctx.upload_plane(0, navlib.PLANE_COST_BASE, nav.plane(0))
     ctx.upload_plane(0, navlib.PLANE_BLOCKERS, nav.plane(1))
@@ -158,7 +161,39 @@ def test_region_field_with_enemy_mask(navlib):
     got = ctx.build_region_fields(cases.region_reqs_to(navlib.REGION_REQ_DTYPE, reqs), np.asarray(seeds, np.int16))
     for k in range(6):
         assert np.array_equal(got[k, :dim * dim // 2], exp[k]), k
-    assert not np.array_equal(exp[0], nav.cell_arrival_field(dim, seeds[0], cells[0], enemies=0)) or True
+    ctx.close()
+
+
+# (side, centre tile, target tile) of cell-arrival fields whose region is smaller than a chunk: the sides at which a border
+# test of the relaxation or the bake (r < dim - 1, ...) is most of the region.  Base = centre - side / 2 (field.c:2475).
+SMALL_REGIONS = [(2, (40, 40), (40, 39)),            # inside a chunk
+                 (2, (0, 5), (0, 4)),                # base row -1: two tiles of four on the map
+                 (2, (64, 64), (63, 64)),            # the four tiles round the chunk corner
+                 (6, (1, 1), (0, 2)),                # base (-2, -2)
+                 (6, (64, 64), (66, 61)),            # rows and columns 61 .. 66: across the chunk corner
+                 (6, (126, 126), (127, 127)),        # rows and columns 123 .. 128: off the map on the far side
+                 (6, (2, 64), (0, 66))]              # base row -1, columns 61 .. 66
+
+
+def test_small_region_fields_match_reference(navlib):
+    """N_CellArrivalFieldCreate over regions of 2 x 2 and 6 x 6 tiles (packed output), partly off the map and across the
+    chunk corner: the other region tests are 96 and 128 tiles wide."""
+    from oracle import pfref
+    grid = cases.small_region_world()
+    nav = pfref.RefNav(cases.synth.to_chunks(grid))
+    reqs, seeds, exp = [], [], []
+    for dim, cen, tgt in SMALL_REGIONS:
+        exp.append(nav.cell_arrival_field(dim, tgt, cen))
+        reqs.append(dict(out_mode=0, base_abs_r=cen[0] - dim // 2, base_abs_c=cen[1] - dim // 2, rdim=dim, cdim=dim,
+                         seed_begin=len(seeds), seed_count=1))
+        seeds.append(tgt)
+    assert all(e.any() for e in exp)                              # (every region holds a tile with a direction)
+    ctx = navlib.NavContext(2, 2)
+    ctx.upload_plane(0, navlib.PLANE_COST_BASE, nav.plane(0))
+    ctx.upload_plane(0, navlib.PLANE_BLOCKERS, nav.plane(1))
+    got = ctx.build_region_fields(cases.region_reqs_to(navlib.REGION_REQ_DTYPE, reqs), np.asarray(seeds, np.int16))
+    for k, (dim, _cen, _tgt) in enumerate(SMALL_REGIONS):
+        assert np.array_equal(got[k, :dim * dim // 2], exp[k]), SMALL_REGIONS[k]
     ctx.close()
 
 
