@@ -838,7 +838,7 @@ int  navhip_dest_queries_dev(navhip_ctx *ctx, const navhip_dest_query *dev_q, in
  *   out_dest_xz    [nq][2][2] the closest position from pos + new velocity ([k][0]) and from pos ([k][1]): the corner of
  *                  the winning tile; 0 where the bit is clear
  * NAVHIP_SQ_HOST is never a wrong answer.  It comes back for: a target row >= n_ents; a target without
- * NAVHIP_ENTITY_FLAG_MOVABLE (a static target needs its OBB, which stays the host's); ceil(radius / 4) of unit or target
+ * NAVHIP_ENTITY_FLAG_MOVABLE (a static target is answered by navhip_surround_queries_ex below); ceil(radius / 4) of unit or target
  * above 8 (radius 32); a NaN radius or position; a source off the map (the reference asserts there); a flood of the row
  * that has to push a tile outside the window of 127 x 127 tiles centred on its target tile in front of its answer (the
  * rule of NAVHIP_DQ_HOST).
@@ -856,6 +856,37 @@ int  navhip_surround_queries(navhip_ctx *ctx, const navhip_world *world, const f
 int  navhip_surround_queries_dev(navhip_ctx *ctx, const navhip_world *dev_world, const float *dev_new_vel_xz,
                                  const int32_t *dev_units, const int32_t *dev_target, int nq,
                                  uint8_t *dev_out_query, float *dev_out_dest_xz, void *stream);
+
+/* ---- the same two queries for a STATIC target (a resource, a storage site, a building) ---------------------------------
+ *
+ * The reference answers them from the tile list of the target's OBB: N_ObjAdjacentToStaticWith (nav.c:4932) and
+ * N_ClosestReachableAdjacentPosStatic (nav.c:4621) call M_Tile_AllUnderObj (tile.c:594) and then the functions above.
+ * Buildings do not move: the host computes a building's list once, with the reference's own M_Tile_AllUnderObj, and
+ * registers it here.  Nothing rasterises an OBB on the device.
+ *
+ * navhip_static_targets_set replaces the context's whole table of lists (n_sets == 0 clears it; the table is freed with
+ * the context).  tiles_off [n_sets + 1] is a CSR index into tiles[][2], absolute nav tiles (row, column) in the order
+ * M_Tile_AllUnderObj returned them, duplicates and all, at most 2048 per list (the reference's tds[2048]; a list the
+ * reference truncated is passed truncated).  The library keeps the first occurrence of every tile of a list, in order:
+ * a later duplicate can neither win n_closest_adjacent_pos's strict < nor change n_objects_adjacent.
+ * NAVHIP_ERR_ARG, with the reason in navhip_last_error and the table as it was: a missing array, non-monotonic offsets, a
+ * list longer than 2048, a tile off the map.  The call waits for the context's stream; a query on another stream that
+ * still reads the old table is the caller's to wait for. */
+int  navhip_static_targets_set(navhip_ctx *ctx, int n_sets, const int32_t *tiles_off, const int16_t *tiles);
+/* navhip_surround_queries[_dev] with target_set [nq]: the table row of row k's target when that target has no
+ * NAVHIP_ENTITY_FLAG_MOVABLE; ignored for a MOVABLE target.  target_set == NULL is navhip_surround_queries[_dev], bit for
+ * bit.  Outputs as above.  A static row is answered in LIST order: of equal lengths the earlier entry of the list wins,
+ * whichever tile its answer is.  It comes back NAVHIP_SQ_HOST only for: a set outside the table or an empty table (device
+ * form; the host form refuses the call with NAVHIP_ERR_ARG before anything is launched); ceil(radius / 4) of the unit
+ * above 8; a NaN radius or position of the unit; a source off the map; a flood that has to leave the window of 127 x 127
+ * tiles around the list entry it starts on.  The length of the list is never a reason.  The scratch is sized from nq and
+ * the longest registered list: no allocation after the first call at a given nq and table. */
+int  navhip_surround_queries_ex(navhip_ctx *ctx, const navhip_world *world, const float *new_vel_xz,
+                                const int32_t *units, const int32_t *target, const int32_t *target_set, int nq,
+                                uint8_t *out_query, float *out_dest_xz);
+int  navhip_surround_queries_ex_dev(navhip_ctx *ctx, const navhip_world *dev_world, const float *dev_new_vel_xz,
+                                    const int32_t *dev_units, const int32_t *dev_target, const int32_t *dev_target_set,
+                                    int nq, uint8_t *dev_out_query, float *dev_out_dest_xz, void *stream);
 
 /* ---- more of entity_compute_update: the heading gate, the arms of the state switch that flags, a
  *      counter, an angle or a distance decide, the arrival overlay's settle rule, and all of it but the last in one call ----

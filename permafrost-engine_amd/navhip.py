@@ -301,6 +301,9 @@ _SIGS = {
     # surround_query_kernels: the two unit queries of the surround arm
     "navhip_surround_queries": (_I, [_P, _WORLD, _P, _P, _P, _I, _P, _P]),
     "navhip_surround_queries_dev": (_I, [_P, _WORLD, _P, _P, _P, _I, _P, _P, _P]),
+    "navhip_static_targets_set": (_I, [_P, _I, _P, _P]),
+    "navhip_surround_queries_ex": (_I, [_P, _WORLD, _P, _P, _P, _P, _I, _P, _P]),
+    "navhip_surround_queries_ex_dev": (_I, [_P, _WORLD, _P, _P, _P, _P, _I, _P, _P, _P]),
     # pool_api: the resident field pool
     "navhip_pool_create": (_I, [_P, _I, _I]),
     "navhip_pool_destroy": (None, [_P]),
@@ -903,28 +906,40 @@ class NavContext(_Handle):
                    dev_ptr(d_tiles_off), dev_ptr(d_tiles), int(tiles_cap), dev_ptr(d_status), _stream(stream))
 
     # -- surround_query_kernels: the two unit queries of the surround arm -------------------------------
-    def surround_queries(self, arrays, new_vel, target, units=None):
-        """M_NavObjAdjacentFrom and M_NavClosestReachableAdjacentPosFrom (from pos + new_vel and from pos) for movable
-        targets.  arrays: pos_xz, radius, flags of the snapshot; target [nq]: the target's row or < 0; units [nq]: the
-        rows' units, None = the dense form (row i is unit i).  Returns (query [nq] SQ_*, dest_xz [nq][2][2]): the shapes
-        of `surround` in state_update_aux."""
+    def static_targets_set(self, tile_lists):
+        """navhip_static_targets_set: the table of static targets' tile lists, replaced as a whole.  tile_lists: one [k, 2]
+        int16 array of absolute (row, column) tiles per set, in M_Tile_AllUnderObj's order; an empty list clears the table."""
+        offs, tiles = _tiles_csr(list(tile_lists))
+        self._call("navhip_static_targets_set", len(offs) - 1, _hp(offs), _hp(tiles))
+
+    def surround_queries(self, arrays, new_vel, target, units=None, target_set=None):
+        """M_NavObjAdjacentFrom and M_NavClosestReachableAdjacentPosFrom (from pos + new_vel and from pos).  arrays: pos_xz,
+        radius, flags of the snapshot; target [nq]: the target's row or < 0; units [nq]: the rows' units, None = the dense
+        form (row i is unit i); target_set [nq]: the row of static_targets_set's table for a target without
+        ENTITY_FLAG_MOVABLE, None = movable targets only.  Returns (query [nq] SQ_*, dest_xz [nq][2][2]): the shapes of
+        `surround` in state_update_aux."""
         w, keep = self._world(arrays)
         vel = _arr(new_vel, np.float32, w.n_ents, 2)
         tgt = _arr(target, np.int32)
-        un = None if units is None else _arr(units, np.int32)
+        un, ts = _arr(units, np.int32), _arr(target_set, np.int32)
         nq = len(tgt)
         query, dest = np.zeros(nq, np.uint8), np.zeros((nq, 2, 2), np.float32)
-        self._call("navhip_surround_queries", C.byref(w), _hp(vel), None if un is None else _hp(un), _hp(tgt), nq,
-                   _hp(query), _hp(dest))
+        if ts is None:
+            self._call("navhip_surround_queries", C.byref(w), _hp(vel), _opt(un), _hp(tgt), nq, _hp(query), _hp(dest))
+        else:
+            self._call("navhip_surround_queries_ex", C.byref(w), _hp(vel), _opt(un), _hp(tgt), _hp(ts), nq, _hp(query), _hp(dest))
         return query, dest
 
-    def surround_queries_dev(self, world, d_new_vel_xz, d_units, d_target, nq, d_query, d_dest_xz, stream=None):
-        """navhip_surround_queries_dev: `world` a World of device pointers (make_world of torch CUDA tensors), every
-        buffer a torch CUDA tensor (d_units None: the dense form), asynchronous on `stream`; the dense outputs are what
-        navhip_state_aux_in.surround_query / .surround_dest_xz take."""
-        self._call("navhip_surround_queries_dev", C.byref(world), dev_ptr(d_new_vel_xz),
-                   None if d_units is None else dev_ptr(d_units), dev_ptr(d_target), int(nq), dev_ptr(d_query),
-                   dev_ptr(d_dest_xz), _stream(stream))
+    def surround_queries_dev(self, world, d_new_vel_xz, d_units, d_target, nq, d_query, d_dest_xz, stream=None, d_target_set=None):
+        """navhip_surround_queries[_ex]_dev: `world` a World of device pointers (make_world of torch CUDA tensors), every
+        buffer a torch CUDA tensor (d_units None: the dense form; d_target_set None: movable targets only), asynchronous on
+        `stream`; the dense outputs are what navhip_state_aux_in.surround_query / .surround_dest_xz take."""
+        if d_target_set is None:
+            self._call("navhip_surround_queries_dev", C.byref(world), dev_ptr(d_new_vel_xz), _opt(d_units, dev_ptr),
+                       dev_ptr(d_target), int(nq), dev_ptr(d_query), dev_ptr(d_dest_xz), _stream(stream))
+        else:
+            self._call("navhip_surround_queries_ex_dev", C.byref(world), dev_ptr(d_new_vel_xz), _opt(d_units, dev_ptr),
+                       dev_ptr(d_target), dev_ptr(d_target_set), int(nq), dev_ptr(d_query), dev_ptr(d_dest_xz), _stream(stream))
 
     def state_update_aux(self, arrays, fstate, wait_ticks_left, wait_prev, new_pos_xz, state, flags, work=None,
                          ent_rot=None, target_dir=None, range_in=None, surround=None, vdes_xz=None, hz=20):
