@@ -1124,13 +1124,78 @@ int  navhip_arrival_settle_resident(navhip_ctx *ctx, const navhip_world *world, 
 int  navhip_arrival_settle_dev(navhip_ctx *ctx, const navhip_world *dev_world, const navhip_settle_in *dev_in,
                                const navhip_settle_out *dev_out, void *stream);
 
+/* G_Arrival_DesiredVelocity (arrival.c:862-944) for nq units whose flock's arrival zone is in ARRIVAL_PHASE_FILLING --
+ * the rows with bit 1 of navhip_world.arrival_flags, the one producer of move_work_in.ent_des_v that reads nav data and
+ * was still the host's (ent_desired_velocity, movement.c:1509-1515).  Statement for statement: arrival_near_region
+ * commits the unit (APPROACH -> SEEK, APPROACH_ARMED -> SEEK_ARMED); a committed unit re-targets a blocked sink
+ * (arrival_nearest_open_slot: of equal distance the EARLIEST slot wins, a distance that is not < INFINITY never), beelines
+ * its sink while N_SegmentWithinRegion holds, else heads for arrival_nearest_slot, else (0, 0); an approaching unit takes
+ * N_DesiredGroupArrivalVelocity of the zone's TARGET_ZONE field, else debounces has_dest_los (ARRIVAL_LOS_HYST 12) and
+ * beelines the centre or samples the flock's centre-of-mass point-seek field.  The rule UPDATES the unit's struct
+ * arrival_unit_state: the out arrays receive the state after the call.
+ * Zones as in navhip_settle_in, plus per zone the mapping rows of its two sets of fields: zone_row indexes
+ * world->region_field_slot (the TARGET_ZONE chunk fields, navhip_build_region_fields), com_row indexes
+ * world->flock_field_slot (the fields of arrival_state.com_dest_id); -1 = none cached.  With world->n_field_slots ==
+ * NAVHIP_POOL_RESIDENT both are rows of the resident pool's mapping table.
+ * world: n_ents, pos_xz (the unit's position), map_pos, n_flocks (rows of flock_field_slot), n_region_rows, the two tables
+ * and field_pool / n_field_slots.  Needs the BLOCKERS plane of the zones' layers. */
+#define NAVHIP_AV_COM_MISS  0x01   /* an approaching unit without static LOS whose centre-of-mass field is missing or has
+                                      FD_NONE under it (NAVHIP_ST_FIELD_MISS / _NONE of the sample): every state output is
+                                      final -- the debounce has counted -- and vdes is (NaN, NaN); the host supplies
+                                      M_NavDesiredPointSeekVelocity(com_dest_id, pos, com) for the row and nothing else   */
+#define NAVHIP_AV_HOST      0x80   /* not decided: the state outputs repeat the inputs, vdes is (NaN, NaN).  A uid outside
+                                      the world, a zone index outside the table, a NaN position or one off the map, a
+                                      substate above 3, a layer without a BLOCKERS plane                                  */
+typedef struct navhip_arrival_vel_in {
+    int32_t  n_zones;
+    int32_t  nq;
+    int32_t  n_slots;                 /* rows of slots_xz / slot_ring                                           */
+    int32_t  n_keys;                  /* rows of region_keys                                                    */
+    const navhip_arrival_zone *zones; /* [n_zones]                                                              */
+    const float    *slots_xz;         /* [..][2]                                                                */
+    const int32_t  *slot_ring;        /* [..]                                                                   */
+    const uint64_t *region_keys;      /* [..] ascending inside a zone, as in navhip_settle_in                   */
+    const int32_t  *zone_row;         /* [n_zones] mapping row of the zone's TARGET_ZONE fields, -1 = none      */
+    const int32_t  *com_row;          /* [n_zones] mapping row of the fields of .com_dest_id, -1 = none         */
+    const int32_t  *uid;              /* [nq] the unit (row of the world's arrays)                              */
+    const int32_t  *zone;             /* [nq] its zone                                                          */
+    const uint8_t  *has_dest_los;     /* [nq] move_work_in.has_dest_los                                         */
+    const uint8_t  *substate;         /* [nq] arrival_unit_state.substate                                       */
+    const uint8_t  *sink_valid;       /* [nq] .sink_valid                                                       */
+    const float    *sink_xz;          /* [nq][2] .sink                                                          */
+    const uint8_t  *los_latched;      /* [nq] .los_latched                                                      */
+    const int32_t  *los_hyst;         /* [nq] .los_hyst                                                         */
+} navhip_arrival_vel_in;
+typedef struct navhip_arrival_vel_out {
+    float    *vdes_xz;                /* [nq][2] *out_vel; (NaN, NaN) for a COM_MISS or HOST row                */
+    uint8_t  *status;                 /* [nq] 0, NAVHIP_AV_COM_MISS or NAVHIP_AV_HOST                           */
+    uint8_t  *substate;               /* [nq] arrival_unit_state after the call                                 */
+    uint8_t  *sink_valid;             /* [nq]                                                                   */
+    float    *sink_xz;                /* [nq][2]                                                                */
+    uint8_t  *los_latched;            /* [nq]                                                                   */
+    int32_t  *los_hyst;               /* [nq]                                                                   */
+    float    *dense_vdes_xz;          /* navhip_arrival_velocity_dev only, or NULL: [n_ents][2], row uid[q] receives
+                                              vdes of query q, rows not listed are left alone (vdes_xz may then be NULL).
+                                              Pre-filled with NaN it is navhip_agent_step_dev's world.vdes_xz as it
+                                              stands: NaN = sample the flock's field on the device                  */
+} navhip_arrival_vel_out;
+/* Host buffers.  NAVHIP_ERR_ARG with the reason in navhip_last_error, before any launch and with the outputs untouched:
+ * a missing array, nq < 0, a zone whose ranges leave the shared arrays (in->n_slots / n_keys rows), keys not ascending
+ * inside a zone, a mapping row outside its table, a layer outside the map's, dense_vdes_xz. */
+int  navhip_arrival_velocity(navhip_ctx *ctx, const navhip_world *world, const navhip_arrival_vel_in *in,
+                             const navhip_arrival_vel_out *out);
+/* Everything resident on the device, asynchronous on `stream`, no allocation: one launch.  What the host form checks in
+ * the arrays is the caller's promise here; a mapping row outside its table makes the unit a NAVHIP_AV_HOST row. */
+int  navhip_arrival_velocity_dev(navhip_ctx *ctx, const navhip_world *dev_world, const navhip_arrival_vel_in *dev_in,
+                                 const navhip_arrival_vel_out *dev_out, void *stream);
+
 /* N_DesiredGroupArrivalVelocity (nav.c:3561) for nq points: the direction under each point in the chunk
  * field of mapping row rows[q] (region_field_slot / field_pool as in navhip_world; resident pool: pass
  * region_field_slot = field_pool = NULL), and whether that tile is a sink inside the zone's disc
  * (out_at_slot; centre_abs = zone centre in absolute nav tiles [nq][2] (row, column), radius[nq] in tiles).
  * out_dir[q]: 0..8 = enum flow_dir, 0xff = no field cached for the point's chunk (the reference returns
  * false).  Host buffers.  The arrival overlay's decisions around it (G_Arrival_DesiredVelocity,
- * arrival.c:862) stay with the host. */
+ * arrival.c:862) are navhip_arrival_velocity's, which makes this lookup itself, per unit, on the device. */
 int  navhip_region_lookup(navhip_ctx *ctx, int nq, const float *pos_xz, const int32_t *rows,
                           const int32_t *region_field_slot, int n_region_rows, const uint8_t *field_pool,
                           int n_field_slots, const int32_t *centre_abs, const int32_t *radius,

@@ -4,7 +4,8 @@
 // STATE_SURROUND_ENTITY (:2423-2437, :2569-2668), adjacent_settled_count (:982) and the arrival overlay's settle rule
 // (G_Arrival_ShouldSettle, arrival.c:946) with what it calls: N_SegmentWithinRegion (nav.c:4326) over
 // M_Tile_LineSupercoverTilesSorted (tile.c:430), arrival_near_region / arrival_near_open_slot
-// (arrival.c:158, :326).  Kernels AND their C entry points (include/navhip.h): this translation unit was
+// (arrival.c:158, :326), and the overlay's desired velocity (G_Arrival_DesiredVelocity, arrival.c:862; k_arrival_velocity).
+// Kernels AND their C entry points (include/navhip.h): this translation unit was
 // added after the round's profiles were taken and touches no other (profiles/README.md, `files`); its
 // device scratch is ONE staging slot of the context, carved up per call.
 //
@@ -611,6 +612,161 @@ __global__ __launch_bounds__(256) void k_arrival_settle(nh_step_params P, const 
 }
 
 // ---------------------------------------------------------------------------------------------
+// G_Arrival_DesiredVelocity (arrival.c:862-944), a row of 16 lanes per unit: the scalar tests on every lane, the pad ring
+// of arrival_near_region and the slot scans shared by the lanes
+// ---------------------------------------------------------------------------------------------
+// arrival_nearest_slot (arrival.c:344) / arrival_nearest_open_slot (:304, with the blockers plane): the slot at or behind
+// the frontier of least dd, the EARLIEST of equal ones (the reference's strict `<` from best = INFINITY: a dd that is not
+// < INFINITY never wins).  dd >= 0, so its float bits order as it does: each lane keeps the least (bits, index) of its
+// stride, the row takes the minimum.  -1 = none.
+__device__ int av_nearest_slot(const nh_step_params &P, const navhip_arrival_zone &Z, const float *slots_xz, const int32_t *slot_ring,
+                               v2 from, const uint16_t *blockers, int gl)
+{
+    uint32_t best = 0xffffffffu;
+    int at = 0x7fffffff;
+    for(int k = Z.slot_begin + gl; k < Z.slot_end; k += 16) {
+        if(slot_ring[k] > Z.active_row) continue;
+        const v2 s = mkv(slots_xz[2 * k], slots_xz[2 * k + 1]);
+        if(blockers) {
+            tiledesc t;
+            if(tile_for_point(P, s.x, s.z, t) && blockers[tile_index(P, t)] > 0) continue;
+        }
+        const v2 d = vsub(s, from);
+        const float dd = vdot(d, d);
+        if(!(dd < INFINITY)) continue;
+        const uint32_t key = nh_f2u(dd);
+        if(key < best) { best = key; at = k; }
+    }
+#pragma unroll
+    for(int d = 8; d >= 1; d >>= 1) {
+        const uint32_t ok = (uint32_t)__shfl_xor((int)best, d);
+        const int      oi = __shfl_xor(at, d);
+        if(ok < best || (ok == best && oi < at)) { best = ok; at = oi; }
+    }
+    return best == 0xffffffffu ? -1 : at;
+}
+
+__device__ __forceinline__ v2 av_heading(v2 v)                              // "if(PFM_Vec2_Len(&v) > EPSILON) PFM_Vec2_Normal(&v, &v)"
+{
+    return vlen(v) > CP_EPS ? vnormal(v) : v;
+}
+
+__global__ __launch_bounds__(256) void k_arrival_velocity(nh_step_params P, int n_com_rows, int n_zone_rows,
+                                                          navhip_arrival_vel_in in, navhip_arrival_vel_out out)
+{
+    const int q = (blockIdx.x * 256 + threadIdx.x) >> 4;
+    const int gl = (int)(threadIdx.x & 15);
+    if(q >= in.nq) return;
+    const int uid = in.uid[q], zi = in.zone[q];
+    int substate = in.substate[q], los_hyst = in.los_hyst[q];
+    bool sink_valid = in.sink_valid[q] != 0, los_latched = in.los_latched[q] != 0;
+    v2 sink = mkv(in.sink_xz[2 * q], in.sink_xz[2 * q + 1]);
+    const float nan = nh_u2f(0x7fc00000u);
+    v2 vdes = mkv(nan, nan);
+    uint32_t status = 0;
+
+    // ---- what the device does not decide: the row goes back as it came
+    const bool listed = uid >= 0 && uid < P.n_ents && zi >= 0 && zi < in.n_zones && substate <= 3;
+    navhip_arrival_zone Z = {};
+    v2 pos = mkv(nan, nan);
+    tiledesc tp = {};
+    bool host = !listed;
+    if(listed) {
+        Z = in.zones[zi];
+        pos = mkv(P.pos_xz[2 * uid], P.pos_xz[2 * uid + 1]);
+        host = !(pos.x == pos.x) || !(pos.z == pos.z) || !tile_for_point(P, pos.x, pos.z, tp)
+            || Z.layer < 0 || Z.layer >= NAVHIP_NAV_LAYER_MAX || !P.map.layers[Z.layer].blockers
+            || in.zone_row[zi] < -1 || in.zone_row[zi] >= n_zone_rows || in.com_row[zi] < -1 || in.com_row[zi] >= n_com_rows;
+    }
+    if(host) {
+        status = NAVHIP_AV_HOST;
+    }else{
+        const uint64_t *keys = in.region_keys + Z.key_begin;
+        const int num_region = Z.key_end - Z.key_begin;
+        const uint16_t *blockers = P.map.layers[Z.layer].blockers;
+        const v2 centre = mkv(Z.centre_x, Z.centre_z);
+
+        // arrival_near_region (arrival.c:158): the tile, then the ring of pad tiles around the position
+        bool near_region = sk_in_region(P, pos, keys, num_region);
+        if(!near_region) {
+            int pad = (int)ceilf(Z.unit_radius / 4.0f);
+            if(pad < 1) pad = 1;
+            const int side = 2 * pad + 1;
+            bool hit = false;
+            for(int k = gl; k < side * side; k += 16) {
+                const int dz = k / side - pad, dx = k % side - pad;
+                if(dx == 0 && dz == 0) continue;
+                hit = hit || sk_in_region(P, mkv(pos.x + (float)dx * 4.0f, pos.z + (float)dz * 4.0f), keys, num_region);
+            }
+            near_region = sk_row_any(hit);
+        }
+        if(near_region && substate < 2) substate += 2;                      // unit_commit, arrival.c:102
+
+        if(substate >= 2) {
+            // ---- SEEK / SEEK_ARMED (:877-908)
+            if(sink_valid) {
+                tiledesc ts;
+                if(tile_for_point(P, sink.x, sink.z, ts) && blockers[tile_index(P, ts)] > 0) {
+                    const int k = av_nearest_slot(P, Z, in.slots_xz, in.slot_ring, pos, blockers, gl);
+                    sink_valid = k >= 0;
+                    if(sink_valid) sink = mkv(in.slots_xz[2 * k], in.slots_xz[2 * k + 1]);
+                }
+            }
+            if(sink_valid && sk_segment_within(P, pos, sink, keys, num_region)) {
+                vdes = av_heading(vsub(sink, pos));
+            }else{
+                const int k = av_nearest_slot(P, Z, in.slots_xz, in.slot_ring, pos, nullptr, gl);
+                vdes = mkv(0.0f, 0.0f);
+                if(k >= 0) vdes = av_heading(vsub(mkv(in.slots_xz[2 * k], in.slots_xz[2 * k + 1]), pos));
+            }
+        }else{
+            // ---- APPROACH / APPROACH_ARMED (:909-941).  N_DesiredGroupArrivalVelocity (nav.c:3561): N_FlowDir of the byte
+            // under the unit in the chunk field of the zone's mapping row; a sink inside the disc is an open slot
+            bool zone_ok = false, at_slot = false;
+            v2 zvel = mkv(0.0f, 0.0f);
+            tiledesc tc;
+            const int zrow = in.zone_row[zi];
+            if(zrow >= 0 && P.region_field_slot && P.field_pool && tile_for_point(P, centre.x, centre.z, tc)) {
+                const int slot = P.region_field_slot[(size_t)zrow * (P.map.w * P.map.h) + tp.chunk_r * P.map.w + tp.chunk_c];
+                if(slot >= 0) {
+                    const int dir = P.field_pool[((size_t)slot << 12) + tp.tile_r * 64 + tp.tile_c] & 0xf;
+                    zone_ok = true;
+                    zvel = flow_dir_vec(dir);
+                    if(dir == NAVHIP_FD_NONE) {
+                        const int dr = (tp.chunk_r * 64 + tp.tile_r) - (tc.chunk_r * 64 + tc.tile_r);     // M_Tile_Distance, tile.c:414
+                        const int dc = (tp.chunk_c * 64 + tp.tile_c) - (tc.chunk_c * 64 + tc.tile_c);
+                        at_slot = dr * dr + dc * dc <= Z.radius * Z.radius;
+                    }
+                }
+            }
+            if(zone_ok && !at_slot && vlen(zvel) > CP_EPS) {
+                vdes = zvel;
+            }else{
+                if((in.has_dest_los[q] != 0) == los_latched) los_hyst = 0;  // the LOS debounce, :925-930
+                else if(++los_hyst >= 12) { los_latched = in.has_dest_los[q] != 0; los_hyst = 0; }   // ARRIVAL_LOS_HYST
+                if(los_latched) {
+                    vdes = av_heading(vsub(centre, pos));
+                }else{
+                    uint32_t st = 0;
+                    vdes = sample_flow(P, in.com_row[zi], pos, st);
+                    if(st) { status = NAVHIP_AV_COM_MISS; vdes = mkv(nan, nan); }
+                }
+            }
+        }
+    }
+    if(gl == 0) {
+        if(out.vdes_xz) { out.vdes_xz[2 * q] = vdes.x; out.vdes_xz[2 * q + 1] = vdes.z; }
+        if(out.dense_vdes_xz && uid >= 0 && uid < P.n_ents) { out.dense_vdes_xz[2 * uid] = vdes.x; out.dense_vdes_xz[2 * uid + 1] = vdes.z; }
+        out.status[q] = (uint8_t)status;
+        out.substate[q] = (uint8_t)substate;
+        out.sink_valid[q] = host ? in.sink_valid[q] : (sink_valid ? 1 : 0);
+        out.sink_xz[2 * q] = sink.x; out.sink_xz[2 * q + 1] = sink.z;
+        out.los_latched[q] = host ? in.los_latched[q] : (los_latched ? 1 : 0);
+        out.los_hyst[q] = los_hyst;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // C entry points
 // ---------------------------------------------------------------------------------------------
 namespace {
@@ -703,7 +859,9 @@ enum sk_len : uint8_t { SK_PER_UNIT, SK_PER_FLOCK, SK_PER_FLOCK_PLUS1, SK_PER_TI
                         SK_PER_QUERY, SK_PER_ZONE, SK_PER_SLOT, SK_PER_KEY,
                         SK_PER_ARM_ROW,       // a row per unit -- with sparse rows, per LISTED unit
                         SK_PER_LISTED, SK_LEN_COUNT };
-enum sk_group : uint8_t { SK_ALWAYS, SK_SKIP, SK_TURN, SK_RANGE, SK_SURROUND, SK_INTERP, SK_SPARSE, SK_AUX, SK_GROUP_COUNT };
+enum sk_group : uint8_t { SK_ALWAYS, SK_SKIP, SK_TURN, SK_RANGE, SK_SURROUND, SK_INTERP, SK_SPARSE, SK_AUX,
+                          SK_DEV_ONLY,          // a member only the _dev form of a call reads: never staged
+                          SK_GROUP_COUNT };
 struct sk_row { size_t off; uint16_t elem; uint8_t len, group, pad; bool out; };
 struct sk_dims {
     size_t len[SK_LEN_COUNT] = {};
@@ -779,6 +937,33 @@ SK_COVERS(sk_pass_out_rows, navhip_state_pass_out, 0);
 SK_COVERS(sk_settle_in_rows, navhip_settle_in, 8);          // n_zones, nq
 SK_COVERS(sk_settle_out_rows, navhip_settle_out, 0);
 #undef SK_COVERS
+
+// the two structs of navhip_arrival_velocity: the same lists, the same guard (under their own macro names: the lists above
+// are the state pass's, counted as such)
+#define AV_ROW(T, member, elem, len) {offsetof(T, member), elem, len, SK_ALWAYS, 0, false}
+#define AV_ROW_OUT(T, member, elem, group) {offsetof(T, member), elem, SK_PER_QUERY, group, 0, true}
+const sk_row av_in_rows[] = {
+    AV_ROW(navhip_arrival_vel_in, zones, sizeof(navhip_arrival_zone), SK_PER_ZONE),
+    AV_ROW(navhip_arrival_vel_in, slots_xz, 8, SK_PER_SLOT),          AV_ROW(navhip_arrival_vel_in, slot_ring, 4, SK_PER_SLOT),
+    AV_ROW(navhip_arrival_vel_in, region_keys, 8, SK_PER_KEY),        AV_ROW(navhip_arrival_vel_in, zone_row, 4, SK_PER_ZONE),
+    AV_ROW(navhip_arrival_vel_in, com_row, 4, SK_PER_ZONE),           AV_ROW(navhip_arrival_vel_in, uid, 4, SK_PER_QUERY),
+    AV_ROW(navhip_arrival_vel_in, zone, 4, SK_PER_QUERY),             AV_ROW(navhip_arrival_vel_in, has_dest_los, 1, SK_PER_QUERY),
+    AV_ROW(navhip_arrival_vel_in, substate, 1, SK_PER_QUERY),         AV_ROW(navhip_arrival_vel_in, sink_valid, 1, SK_PER_QUERY),
+    AV_ROW(navhip_arrival_vel_in, sink_xz, 8, SK_PER_QUERY),          AV_ROW(navhip_arrival_vel_in, los_latched, 1, SK_PER_QUERY),
+    AV_ROW(navhip_arrival_vel_in, los_hyst, 4, SK_PER_QUERY),
+};
+const sk_row av_out_rows[] = {
+    AV_ROW_OUT(navhip_arrival_vel_out, vdes_xz, 8, SK_ALWAYS),        AV_ROW_OUT(navhip_arrival_vel_out, status, 1, SK_ALWAYS),
+    AV_ROW_OUT(navhip_arrival_vel_out, substate, 1, SK_ALWAYS),       AV_ROW_OUT(navhip_arrival_vel_out, sink_valid, 1, SK_ALWAYS),
+    AV_ROW_OUT(navhip_arrival_vel_out, sink_xz, 8, SK_ALWAYS),        AV_ROW_OUT(navhip_arrival_vel_out, los_latched, 1, SK_ALWAYS),
+    AV_ROW_OUT(navhip_arrival_vel_out, los_hyst, 4, SK_ALWAYS),       AV_ROW_OUT(navhip_arrival_vel_out, dense_vdes_xz, 8, SK_DEV_ONLY),
+};
+#undef AV_ROW
+#undef AV_ROW_OUT
+static_assert(sizeof(navhip_arrival_vel_in) == sizeof(av_in_rows) / sizeof(av_in_rows[0]) * sizeof(void*) + 16,
+              "navhip_arrival_vel_in changed: does av_in_rows cover it?");       // n_zones, nq, n_slots, n_keys
+static_assert(sizeof(navhip_arrival_vel_out) == sizeof(av_out_rows) / sizeof(av_out_rows[0]) * sizeof(void*),
+              "navhip_arrival_vel_out changed: does av_out_rows cover it?");
 
 bool sk_listed(std::initializer_list<size_t> members, size_t off)
 {
@@ -930,6 +1115,56 @@ bool sk_check_settle(const navhip_settle_in *in, const navhip_settle_out *out)
     return in->zones && in->n_zones >= 1 && in->uid && in->zone && in->new_pos_xz && in->substate && in->sink_valid && in->sink_xz
         && in->order_pos_xz && in->progress_anchor_xz && in->progress_anchored && in->stuck && out->settle && out->substate
         && out->progress_anchor_xz && out->progress_anchored && out->stuck;
+}
+
+// The one argument check of navhip_arrival_velocity and navhip_arrival_velocity_dev; host_arrays: the arrays can be read
+// here (the host form), so what lies IN them is checked too.  Fills in the two mapping tables, the pool and how many rows
+// each table has.  The reason of a refusal goes to last_error.
+struct av_tables { const int32_t *com_slot, *zone_slot; const uint8_t *pool; int n_com_rows, n_zone_rows; bool resident; };
+int av_check(navhip_ctx *ctx, const navhip_world *w, const navhip_arrival_vel_in *in, const navhip_arrival_vel_out *out,
+             bool host_arrays, av_tables *T)
+{
+    if(!ctx) return NAVHIP_ERR_ARG;
+    const char *name = host_arrays ? "navhip_arrival_velocity: " : "navhip_arrival_velocity_dev: ";
+    auto fail = [&](const std::string &why) { ctx->last_error = name + why; return NAVHIP_ERR_ARG; };
+    if(!w || !in || !out) return fail("a missing argument");
+    if(in->nq < 0) return fail("nq < 0");
+    if(in->n_zones < 0 || in->n_slots < 0 || in->n_keys < 0 || w->n_ents < 0) return fail("a negative count");
+    if(in->nq == 0) return NAVHIP_OK;
+    if(!w->pos_xz) return fail("a missing array: world->pos_xz");
+    if(in->n_zones > 0 && (!in->zones || !in->zone_row || !in->com_row)) return fail("a missing array: zones, zone_row or com_row");
+    if((in->n_slots > 0 && (!in->slots_xz || !in->slot_ring)) || (in->n_keys > 0 && !in->region_keys))
+        return fail("a missing array: slots_xz, slot_ring or region_keys");
+    if(!in->uid || !in->zone || !in->has_dest_los || !in->substate || !in->sink_valid || !in->sink_xz || !in->los_latched || !in->los_hyst)
+        return fail("a missing array of navhip_arrival_vel_in");
+    if(!out->status || !out->substate || !out->sink_valid || !out->sink_xz || !out->los_latched || !out->los_hyst)
+        return fail("a missing array of navhip_arrival_vel_out");
+    if(host_arrays ? (!out->vdes_xz || out->dense_vdes_xz) : (!out->vdes_xz && !out->dense_vdes_xz))
+        return fail(host_arrays ? "vdes_xz missing, or dense_vdes_xz given to the host form" : "neither vdes_xz nor dense_vdes_xz");
+    T->resident = w->n_field_slots == NAVHIP_POOL_RESIDENT;
+    if(T->resident) {
+        if(!ctx->pool) return fail("NAVHIP_POOL_RESIDENT without a resident pool");
+        T->com_slot = T->zone_slot = nh_pool_map(ctx); T->pool = nh_pool_fields(ctx);
+        T->n_com_rows = T->n_zone_rows = nh_pool_dests(ctx);
+    }else{
+        T->com_slot = w->flock_field_slot; T->zone_slot = w->region_field_slot; T->pool = w->field_pool;
+        T->n_com_rows = T->com_slot && w->n_flocks > 0 ? w->n_flocks : 0;
+        T->n_zone_rows = T->zone_slot && w->n_region_rows > 0 ? w->n_region_rows : 0;
+        if((T->n_com_rows || T->n_zone_rows) && (!T->pool || w->n_field_slots < 1)) return fail("a mapping table without field_pool");
+    }
+    if(!host_arrays) return NAVHIP_OK;
+    for(int z = 0; z < in->n_zones; z++) {
+        const navhip_arrival_zone &Z = in->zones[z];
+        const std::string zn = "zone " + std::to_string(z);
+        if(Z.slot_begin < 0 || Z.slot_end < Z.slot_begin || Z.slot_end > in->n_slots) return fail(zn + ": its slot range leaves slots_xz / slot_ring");
+        if(Z.key_begin < 0 || Z.key_end < Z.key_begin || Z.key_end > in->n_keys) return fail(zn + ": its key range leaves region_keys");
+        for(int k = Z.key_begin + 1; k < Z.key_end; k++)
+            if(!(in->region_keys[k] > in->region_keys[k - 1])) return fail(zn + ": region_keys not ascending");
+        if(Z.layer < 0 || Z.layer >= NAVHIP_NAV_LAYER_MAX) return fail(zn + ": layer outside the map's");
+        if(in->zone_row[z] < -1 || in->zone_row[z] >= T->n_zone_rows) return fail(zn + ": zone_row outside region_field_slot");
+        if(in->com_row[z] < -1 || in->com_row[z] >= T->n_com_rows) return fail(zn + ": com_row outside flock_field_slot");
+    }
+    return NAVHIP_OK;
 }
 
 }   // namespace
@@ -1420,6 +1655,56 @@ int navhip_arrival_settle(navhip_ctx *ctx, const navhip_world *w, const navhip_s
 int navhip_arrival_settle_resident(navhip_ctx *ctx, const navhip_world *w, const navhip_settle_in *in, const navhip_settle_out *out)
 {
     return sk_arrival_settle(ctx, w, in, out, true);
+}
+
+int navhip_arrival_velocity_dev(navhip_ctx *ctx, const navhip_world *w, const navhip_arrival_vel_in *in,
+                                const navhip_arrival_vel_out *out, void *stream)
+{
+    av_tables T = {};
+    const int rc = av_check(ctx, w, in, out, false, &T);
+    if(rc || in->nq == 0) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    nh_step_params P;
+    sk_map_view(ctx, w, &P);
+    P.pos_xz = w->pos_xz;
+    P.flock_field_slot = T.com_slot; P.region_field_slot = T.zone_slot; P.field_pool = T.pool;
+    hipLaunchKernelGGL(k_arrival_velocity, dim3((in->nq + 15) / 16), dim3(256), 0, stream ? (hipStream_t)stream : ctx->stream,
+                       P, T.n_com_rows, T.n_zone_rows, *in, *out);
+    HIPCHK(ctx, hipGetLastError());
+    return NAVHIP_OK;
+}
+
+int navhip_arrival_velocity(navhip_ctx *ctx, const navhip_world *w, const navhip_arrival_vel_in *in, const navhip_arrival_vel_out *out)
+{
+    av_tables T = {};
+    int rc = av_check(ctx, w, in, out, true, &T);
+    if(rc || in->nq == 0) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t nchunks = (size_t)ctx->nchunks;
+    sk_dims D = sk_dims_of(w, 0, 0);
+    D.len[SK_PER_ZONE] = (size_t)in->n_zones; D.len[SK_PER_SLOT] = (size_t)in->n_slots; D.len[SK_PER_KEY] = (size_t)in->n_keys;
+    D.len[SK_PER_QUERY] = D.cnt = (size_t)in->nq;
+    D.pad = 16;                                                             // (no array of a zone-less or slot-less call is empty)
+    sk_plan P;
+    navhip_world d = sk_device_world(w);
+    sk_stage_world(P, w, &d, D, {SK_W(pos_xz)});
+    if(!T.resident) {
+        // the world's own tables, as the step stages them (rows of -1 .. : see navhip_world)
+        if(T.n_com_rows) P.in(w->flock_field_slot, (size_t)T.n_com_rows * nchunks * 4, D.pad, (void**)&d.flock_field_slot);
+        if(T.n_zone_rows) P.in(w->region_field_slot, (size_t)T.n_zone_rows * nchunks * 4, D.pad, (void**)&d.region_field_slot);
+        if(T.n_com_rows || T.n_zone_rows) P.in(w->field_pool, (size_t)w->n_field_slots * NH_CELLS, D.pad, (void**)&d.field_pool);
+    }
+    navhip_arrival_vel_in di = *in;
+    navhip_arrival_vel_out dout = {};
+    sk_stage(P, av_in_rows, in, &di, D);
+    sk_stage(P, av_out_rows, out, &dout, D);
+    rc = P.reserve(ctx, NH_STAGE_STATE_ARENA);
+    if(!rc) rc = P.upload(ctx, s);
+    if(rc) return rc;
+    rc = navhip_arrival_velocity_dev(ctx, &d, &di, &dout, s);
+    if(!rc) rc = P.download(ctx, s);
+    return rc;
 }
 
 }   // extern "C"

@@ -191,6 +191,21 @@ class SettleOut(C.Structure):
                 ("progress_anchored", C.c_void_p), ("stuck", C.c_void_p), ("nsettled", C.c_void_p)]
 
 
+class ArrivalVelIn(C.Structure):
+    """navhip_arrival_vel_in, include/navhip.h"""
+    _fields_ = [("n_zones", C.c_int32), ("nq", C.c_int32), ("n_slots", C.c_int32), ("n_keys", C.c_int32),
+                ("zones", C.c_void_p), ("slots_xz", C.c_void_p), ("slot_ring", C.c_void_p), ("region_keys", C.c_void_p),
+                ("zone_row", C.c_void_p), ("com_row", C.c_void_p), ("uid", C.c_void_p), ("zone", C.c_void_p),
+                ("has_dest_los", C.c_void_p), ("substate", C.c_void_p), ("sink_valid", C.c_void_p), ("sink_xz", C.c_void_p),
+                ("los_latched", C.c_void_p), ("los_hyst", C.c_void_p)]
+
+
+class ArrivalVelOut(C.Structure):
+    """navhip_arrival_vel_out, include/navhip.h"""
+    _fields_ = [("vdes_xz", C.c_void_p), ("status", C.c_void_p), ("substate", C.c_void_p), ("sink_valid", C.c_void_p),
+                ("sink_xz", C.c_void_p), ("los_latched", C.c_void_p), ("los_hyst", C.c_void_p), ("dense_vdes_xz", C.c_void_p)]
+
+
 class LosChainStats(C.Structure):
     """navhip_los_chain_stats, include/navhip.h"""
     _fields_ = [("slots", C.c_int32), ("levels", C.c_int32), ("stale", C.c_int32), ("rebuilt", C.c_int32),
@@ -295,6 +310,8 @@ _SIGS = {
     "navhip_arrival_settle": (_I, [_P, _WORLD, C.POINTER(SettleIn), C.POINTER(SettleOut)]),
     "navhip_arrival_settle_dev": (_I, [_P, _WORLD, C.POINTER(SettleIn), C.POINTER(SettleOut), _P]),
     "navhip_arrival_settle_resident": (_I, [_P, _P, _P, _P]),
+    "navhip_arrival_velocity": (_I, [_P, _WORLD, C.POINTER(ArrivalVelIn), C.POINTER(ArrivalVelOut)]),
+    "navhip_arrival_velocity_dev": (_I, [_P, _WORLD, C.POINTER(ArrivalVelIn), C.POINTER(ArrivalVelOut), _P]),
     # dest_query_kernels: the destination queries of arrived()
     "navhip_dest_queries": (_I, [_P, _P, _I, _F, _F, _P, _P, _P, _I, _P]),
     "navhip_dest_queries_dev": (_I, [_P, _P, _I, _F, _F, _P, _P, _P, _I, _P, _P]),
@@ -359,6 +376,7 @@ RECORDS = {
     "navhip_state_in": StateIn, "navhip_state_aux_in": StateAuxIn, "navhip_gate_in": GateIn,
     "navhip_state_pass_in": StatePassIn, "navhip_state_pass_out": StatePassOut,
     "navhip_arrival_zone": ArrivalZone, "navhip_settle_in": SettleIn, "navhip_settle_out": SettleOut,
+    "navhip_arrival_vel_in": ArrivalVelIn, "navhip_arrival_vel_out": ArrivalVelOut,
     "navhip_los_chain_stats": LosChainStats, "navhip_tick_desc": TickDesc, "navhip_tick_info": TickInfo,
 }
 
@@ -506,6 +524,28 @@ def _fill_aux(ai, n, fstate, wait_ticks_left, wait_prev, ent_rot=None, target_di
                        surround_nearest_prev_xz=_arr(surround["nearest_prev_xz"], np.float32, n, 2),
                        surround_dest_xz=_arr(surround["dest_xz"], np.float32, n, 2, 2), out_surround_dest_xz=su_out)
     return keep, su_out
+
+
+def _pack_zones(zones, region_keys):
+    """Zones as dicts (layer, centre_xz, radius, unit_radius, fill_frac, active_row, num_rows, slots_xz, slot_ring) and
+    their sorted u64 key arrays -> (ArrivalZone array, slots_xz, slot_ring, region_keys): the three shared arrays, each
+    with one spare element so that none is empty."""
+    zs = (ArrivalZone * max(1, len(zones)))()
+    slots, rings, keys = [], [], []
+    so = ko = 0
+    for i, z in enumerate(zones):
+        sl = np.asarray(z["slots_xz"], np.float32).reshape(-1, 2)
+        kk = np.asarray(region_keys[i], np.uint64)
+        zs[i] = ArrivalZone(float(z["centre_xz"][0]), float(z["centre_xz"][1]), float(z["unit_radius"]),
+                            float(z["fill_frac"]), int(z["radius"]), int(z["layer"]), int(z["active_row"]),
+                            int(z["num_rows"]), so, so + len(sl), ko, ko + len(kk))
+        so += len(sl)
+        ko += len(kk)
+        slots.append(sl)
+        rings.append(np.asarray(z["slot_ring"], np.int32))
+        keys.append(kk)
+    cat = lambda parts, dt, shape: np.ascontiguousarray(np.concatenate(parts + [np.zeros(shape, dt)]))      # noqa: E731
+    return zs, cat(slots, np.float32, (1, 2)), cat(rings, np.int32, (1,)), cat(keys, np.uint64, (1,))
 
 
 def make_reqs(n):
@@ -999,22 +1039,7 @@ class NavContext(_Handle):
         units: dict of nq-row arrays (uid, zone, new_pos_xz, nsettled, substate, sink_valid, sink_xz, order_pos_xz,
         progress_anchor_xz, progress_anchored, stuck).  Returns (settle [nq], dict of the unit state after)."""
         w, keep = self._world(arrays)
-        zs = (ArrivalZone * len(zones))()
-        slots, rings, keys = [], [], []
-        so = ko = 0
-        for i, z in enumerate(zones):
-            sl = np.asarray(z["slots_xz"], np.float32).reshape(-1, 2)
-            kk = np.asarray(region_keys[i], np.uint64)
-            zs[i] = ArrivalZone(float(z["centre_xz"][0]), float(z["centre_xz"][1]), float(z["unit_radius"]),
-                                float(z["fill_frac"]), int(z["radius"]), int(z["layer"]), int(z["active_row"]),
-                                int(z["num_rows"]), so, so + len(sl), ko, ko + len(kk))
-            so += len(sl)
-            ko += len(kk)
-            slots.append(sl)
-            rings.append(np.asarray(z["slot_ring"], np.int32))
-            keys.append(kk)
-        # (one spare element each, so that no array is empty)
-        cat = lambda parts, dt, shape: np.ascontiguousarray(np.concatenate(parts + [np.zeros(shape, dt)]))      # noqa: E731
+        zs, slots_cat, ring_cat, keys_cat = _pack_zones(zones, region_keys)
         nq = len(units["uid"])
         spec = (("uid", np.int32, 1), ("zone", np.int32, 1), ("new_pos_xz", np.float32, 2), ("nsettled", np.int32, 1),
                 ("substate", np.uint8, 1), ("sink_valid", np.uint8, 1), ("sink_xz", np.float32, 2),
@@ -1023,8 +1048,7 @@ class NavContext(_Handle):
         si = SettleIn()
         si.n_zones, si.nq = len(zones), nq
         si.zones = C.addressof(zs)
-        k = _point(si, slots_xz=cat(slots, np.float32, (1, 2)), slot_ring=cat(rings, np.int32, (1,)),
-                   region_keys=cat(keys, np.uint64, (1,)))
+        k = _point(si, slots_xz=slots_cat, slot_ring=ring_cat, region_keys=keys_cat)
         k += _point(si, **{name: _arr(units[name], dt, *((nq, width) if width > 1 else (nq,))) for name, dt, width in spec})
         res = {"settle": np.zeros(nq, np.uint8), "substate": np.zeros(nq, np.uint8),
                "progress_anchor_xz": np.zeros((nq, 2), np.float32), "progress_anchored": np.zeros(nq, np.uint8),
@@ -1034,6 +1058,45 @@ class NavContext(_Handle):
         self._call("navhip_arrival_settle", C.byref(w), C.byref(si), C.byref(so_))
         settle = res.pop("settle")
         return settle, res
+
+    # the per-unit members of navhip_arrival_vel_in / _out: (name, element type, width)
+    _AV_IN = (("uid", np.int32, 1), ("zone", np.int32, 1), ("has_dest_los", np.uint8, 1), ("substate", np.uint8, 1),
+              ("sink_valid", np.uint8, 1), ("sink_xz", np.float32, 2), ("los_latched", np.uint8, 1), ("los_hyst", np.int32, 1))
+    _AV_OUT = (("vdes_xz", np.float32, 2), ("status", np.uint8, 1), ("substate", np.uint8, 1), ("sink_valid", np.uint8, 1),
+               ("sink_xz", np.float32, 2), ("los_latched", np.uint8, 1), ("los_hyst", np.int32, 1))
+
+    def arrival_velocity(self, arrays, zones, region_keys, units, zone_row=None, com_row=None, patch=None):
+        """G_Arrival_DesiredVelocity (arrival.c:862) for units of filling zones, host buffers.  arrays: the world (pos_xz;
+        flock_field_slot / region_field_slot / field_pool, or use_resident_pool); zones, region_keys: as for
+        arrival_settle; zone_row / com_row: [n_zones] mapping rows (default: none); units: dict of nq-row arrays (uid, zone,
+        has_dest_los, substate, sink_valid, sink_xz, los_latched, los_hyst).  patch: a function of (ArrivalVelIn,
+        ArrivalVelOut, zones array) that may damage the call before it is made (argument-error tests).  Returns the dict
+        of outputs (vdes_xz, status and the unit state after the call)."""
+        w, keep = self._world(arrays)
+        w.n_flocks = 0 if arrays.get("flock_field_slot") is None else len(arrays["flock_field_slot"])
+        if arrays.get("field_pool") is None and arrays.get("use_resident_pool"):
+            w.n_field_slots = POOL_RESIDENT
+        zs, slots, ring, keys = _pack_zones(zones, region_keys)
+        nz, nq = len(zones), len(units["uid"])
+        none = np.full(max(nz, 1), -1, np.int32)
+        vi = ArrivalVelIn()
+        vi.n_zones, vi.nq, vi.n_slots, vi.n_keys = nz, nq, len(ring) - 1, len(keys) - 1
+        vi.zones = C.addressof(zs)
+        k = _point(vi, slots_xz=slots, slot_ring=ring, region_keys=keys,
+                   zone_row=none if zone_row is None else _arr(zone_row, np.int32, nz),
+                   com_row=none if com_row is None else _arr(com_row, np.int32, nz))
+        k += _point(vi, **{name: _arr(units[name], dt, *((nq, width) if width > 1 else (nq,))) for name, dt, width in self._AV_IN})
+        res = {name: np.zeros((nq, width) if width > 1 else (nq,), dt) for name, dt, width in self._AV_OUT}
+        vo = ArrivalVelOut()
+        _point(vo, **res)
+        if patch is not None:
+            patch(vi, vo, zs)
+        self._call("navhip_arrival_velocity", C.byref(w), C.byref(vi), C.byref(vo))
+        return res
+
+    def arrival_velocity_dev(self, world, vel_in, vel_out, stream=None):
+        """navhip_arrival_velocity_dev: a World, an ArrivalVelIn and an ArrivalVelOut of device pointers; asynchronous."""
+        self._call("navhip_arrival_velocity_dev", C.byref(world), C.byref(vel_in), C.byref(vel_out), _stream(stream))
 
     # -- pool_api: the resident field pool --------------------------------------------------------------
     def pool_create(self, n_slots, n_dests):
