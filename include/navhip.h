@@ -1189,6 +1189,78 @@ int  navhip_arrival_velocity(navhip_ctx *ctx, const navhip_world *world, const n
 int  navhip_arrival_velocity_dev(navhip_ctx *ctx, const navhip_world *dev_world, const navhip_arrival_vel_in *dev_in,
                                  const navhip_arrival_vel_out *dev_out, void *stream);
 
+/* The built-zone branch of G_Arrival_UpdateFlock (arrival.c:767-853, everything but the first build at :796-848) for
+ * n_zones zones at once -- what update_flock_arrival_fields (movement.c:900-920) runs serially per flock and nav layer,
+ * and the producer of the zone table the two calls above read.  Per zone, in the reference's order: every member settled
+ * -> phase DONE and nothing else changes; otherwise layer / unit_radius from the call's arguments, radius =
+ * arrival_zone_radius(total_members, unit_radius), ++realloc_counter, and when it reaches ARRIVAL_REALLOC_PERIOD (4)
+ * arrival_realloc_slots (:391-516): while fill_frac < 0.25 the rings are recomputed (arrival_compute_geodesic_rings :257
+ * over N_RegionGeodesicDist nav.c:4389: the entry is the float sum of the unsettled members' positions in member order
+ * times 1.0f / cnt, the source the key whose tile centre is nearest to it, a 4-connected flood through the keys, ring =
+ * (maxd - distance) / ring_w) and active_row = 0; then the occupancy (slots under blockers, and the slot nearest to every
+ * settled member), fill_frac, the frontier with its stall counter, and for every unsettled member inside the footprint
+ * unit_commit and its sink: the nearest slot that is not occupied and lies at or behind the frontier (of equal distance
+ * the EARLIEST slot wins, a distance that is not < INFINITY never).
+ * A zone is a navhip_arrival_zone (as in navhip_settle_in / navhip_arrival_vel_in) plus a navhip_arrival_flock: what
+ * struct arrival_state has and that table lacks, the call's arguments, and the zone's members as a range of the member
+ * arrays, in the reference's member order (members[].pos is world->pos_xz[uid]).
+ * world: n_ents, pos_xz, map_pos.  Needs the BLOCKERS plane of the layers the flocks name. */
+#define NAVHIP_ARRIVAL_PHASE_INACTIVE 0    /* enum arrival_phase, arrival.h:49 */
+#define NAVHIP_ARRIVAL_PHASE_FILLING  1
+#define NAVHIP_ARRIVAL_PHASE_DONE     2
+#define NAVHIP_ARRIVAL_MAX_SLOTS      4096 /* ARRIVAL_MAX_SLOTS, arrival.h:47 */
+#define NAVHIP_AF_HOST      0x80   /* not decided: every output of the zone and of its members repeats its input.  A layer
+                                      without a BLOCKERS plane (or outside the map's), more than NAVHIP_ARRIVAL_MAX_SLOTS
+                                      slots or keys, a uid outside the world, a phase other than FILLING, num_rows above
+                                      NAVHIP_ARRIVAL_MAX_SLOTS or active_row outside [0, num_rows)                        */
+typedef struct navhip_arrival_flock {
+    int32_t  phase;                   /* arrival_state.phase (NAVHIP_ARRIVAL_PHASE_*)                           */
+    int32_t  realloc_counter;         /* .realloc_counter                                                       */
+    int32_t  stall_counter;           /* .stall_counter                                                         */
+    int32_t  prev_occ;                /* .prev_occ                                                              */
+    float    row_height;              /* .row_height                                                            */
+    float    unit_radius;             /* the call's arguments: unit_radius,                                     */
+    int32_t  total_members;           /* ... total_members,                                                     */
+    int32_t  layer;                   /* ... layer                                                              */
+    int32_t  member_begin, member_end;/* members[0, nmembers) as a range of the member arrays                   */
+} navhip_arrival_flock;
+typedef struct navhip_arrival_flock_in {
+    int32_t  n_zones;
+    int32_t  nm;                      /* rows of the member arrays                                              */
+    int32_t  n_slots;                 /* rows of slots_xz / slot_ring                                           */
+    int32_t  n_keys;                  /* rows of region_keys                                                    */
+    const navhip_arrival_zone  *zones;  /* [n_zones]                                                            */
+    const navhip_arrival_flock *flocks; /* [n_zones]                                                            */
+    const float    *slots_xz;         /* [..][2]                                                                */
+    const int32_t  *slot_ring;        /* [..]                                                                   */
+    const uint64_t *region_keys;      /* [..] ascending inside a zone, as in navhip_settle_in                   */
+    const int32_t  *uid;              /* [nm] the member (row of world->pos_xz)                                 */
+    const uint8_t  *settled;          /* [nm] arrival_member.settled                                            */
+    const uint8_t  *substate;         /* [nm] arrival_unit_state.substate                                       */
+    const uint8_t  *sink_valid;       /* [nm] .sink_valid                                                       */
+    const float    *sink_xz;          /* [nm][2] .sink                                                          */
+} navhip_arrival_flock_in;
+typedef struct navhip_arrival_flock_out {
+    navhip_arrival_zone  *zones;      /* [n_zones] the zone table after the call                                */
+    navhip_arrival_flock *flocks;     /* [n_zones] the companion after the call                                 */
+    int32_t  *slot_ring;              /* [n_slots]                                                              */
+    uint8_t  *substate;               /* [nm] arrival_unit_state after the call                                 */
+    uint8_t  *sink_valid;             /* [nm]                                                                   */
+    float    *sink_xz;                /* [nm][2]                                                                */
+    uint8_t  *status;                 /* [n_zones] 0 or NAVHIP_AF_HOST                                          */
+} navhip_arrival_flock_out;
+/* Host buffers.  NAVHIP_ERR_ARG with the reason in navhip_last_error, before any launch and with the outputs untouched:
+ * a missing array, nm < 0, a zone whose slot, key or member range leaves the shared arrays, keys not ascending inside a
+ * zone. */
+int  navhip_arrival_flock_update(navhip_ctx *ctx, const navhip_world *world, const navhip_arrival_flock_in *in,
+                                 const navhip_arrival_flock_out *out);
+/* Everything resident on the device, asynchronous on `stream`, no allocation: one launch, a workgroup per zone.  out may
+ * alias in array by array (in place); what the host form checks in the arrays is the caller's promise here.  Behind it
+ * navhip_arrival_velocity_dev and navhip_arrival_settle_dev on the same device arrays see the new rings, frontier and
+ * sinks. */
+int  navhip_arrival_flock_update_dev(navhip_ctx *ctx, const navhip_world *dev_world, const navhip_arrival_flock_in *dev_in,
+                                     const navhip_arrival_flock_out *dev_out, void *stream);
+
 /* N_DesiredGroupArrivalVelocity (nav.c:3561) for nq points: the direction under each point in the chunk
  * field of mapping row rows[q] (region_field_slot / field_pool as in navhip_world; resident pool: pass
  * region_field_slot = field_pool = NULL), and whether that tile is a sink inside the zone's disc

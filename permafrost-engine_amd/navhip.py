@@ -38,6 +38,9 @@ FD_NONE, FD_NW, FD_N, FD_NE, FD_W, FD_E, FD_SW, FD_S, FD_SE = range(9)
 FFID_ENEMIES, FFID_ENTITY, FFID_ZONE = 2, 4, 5
 COMM_ID_BYTES = 128
 POOL_RESIDENT = -1
+ARRIVAL_PHASE_INACTIVE, ARRIVAL_PHASE_FILLING, ARRIVAL_PHASE_DONE = 0, 1, 2
+ARRIVAL_MAX_SLOTS = 4096
+AF_HOST = 0x80
 LOS_REFRESH_DOWNSTREAM = 1
 
 # per-agent movement step
@@ -206,6 +209,27 @@ class ArrivalVelOut(C.Structure):
                 ("sink_xz", C.c_void_p), ("los_latched", C.c_void_p), ("los_hyst", C.c_void_p), ("dense_vdes_xz", C.c_void_p)]
 
 
+class ArrivalFlock(C.Structure):
+    """navhip_arrival_flock, include/navhip.h"""
+    _fields_ = [("phase", C.c_int32), ("realloc_counter", C.c_int32), ("stall_counter", C.c_int32), ("prev_occ", C.c_int32),
+                ("row_height", C.c_float), ("unit_radius", C.c_float), ("total_members", C.c_int32), ("layer", C.c_int32),
+                ("member_begin", C.c_int32), ("member_end", C.c_int32)]
+
+
+class ArrivalFlockIn(C.Structure):
+    """navhip_arrival_flock_in, include/navhip.h"""
+    _fields_ = [("n_zones", C.c_int32), ("nm", C.c_int32), ("n_slots", C.c_int32), ("n_keys", C.c_int32),
+                ("zones", C.c_void_p), ("flocks", C.c_void_p), ("slots_xz", C.c_void_p), ("slot_ring", C.c_void_p),
+                ("region_keys", C.c_void_p), ("uid", C.c_void_p), ("settled", C.c_void_p), ("substate", C.c_void_p),
+                ("sink_valid", C.c_void_p), ("sink_xz", C.c_void_p)]
+
+
+class ArrivalFlockOut(C.Structure):
+    """navhip_arrival_flock_out, include/navhip.h"""
+    _fields_ = [("zones", C.c_void_p), ("flocks", C.c_void_p), ("slot_ring", C.c_void_p), ("substate", C.c_void_p),
+                ("sink_valid", C.c_void_p), ("sink_xz", C.c_void_p), ("status", C.c_void_p)]
+
+
 class LosChainStats(C.Structure):
     """navhip_los_chain_stats, include/navhip.h"""
     _fields_ = [("slots", C.c_int32), ("levels", C.c_int32), ("stale", C.c_int32), ("rebuilt", C.c_int32),
@@ -312,6 +336,9 @@ _SIGS = {
     "navhip_arrival_settle_resident": (_I, [_P, _P, _P, _P]),
     "navhip_arrival_velocity": (_I, [_P, _WORLD, C.POINTER(ArrivalVelIn), C.POINTER(ArrivalVelOut)]),
     "navhip_arrival_velocity_dev": (_I, [_P, _WORLD, C.POINTER(ArrivalVelIn), C.POINTER(ArrivalVelOut), _P]),
+    # arrival_flock_kernels: the built-zone branch of G_Arrival_UpdateFlock
+    "navhip_arrival_flock_update": (_I, [_P, _WORLD, C.POINTER(ArrivalFlockIn), C.POINTER(ArrivalFlockOut)]),
+    "navhip_arrival_flock_update_dev": (_I, [_P, _WORLD, C.POINTER(ArrivalFlockIn), C.POINTER(ArrivalFlockOut), _P]),
     # dest_query_kernels: the destination queries of arrived()
     "navhip_dest_queries": (_I, [_P, _P, _I, _F, _F, _P, _P, _P, _I, _P]),
     "navhip_dest_queries_dev": (_I, [_P, _P, _I, _F, _F, _P, _P, _P, _I, _P, _P]),
@@ -377,6 +404,7 @@ RECORDS = {
     "navhip_state_pass_in": StatePassIn, "navhip_state_pass_out": StatePassOut,
     "navhip_arrival_zone": ArrivalZone, "navhip_settle_in": SettleIn, "navhip_settle_out": SettleOut,
     "navhip_arrival_vel_in": ArrivalVelIn, "navhip_arrival_vel_out": ArrivalVelOut,
+    "navhip_arrival_flock": ArrivalFlock, "navhip_arrival_flock_in": ArrivalFlockIn, "navhip_arrival_flock_out": ArrivalFlockOut,
     "navhip_los_chain_stats": LosChainStats, "navhip_tick_desc": TickDesc, "navhip_tick_info": TickInfo,
 }
 
@@ -546,6 +574,39 @@ def _pack_zones(zones, region_keys):
         keys.append(kk)
     cat = lambda parts, dt, shape: np.ascontiguousarray(np.concatenate(parts + [np.zeros(shape, dt)]))      # noqa: E731
     return zs, cat(slots, np.float32, (1, 2)), cat(rings, np.int32, (1,)), cat(keys, np.uint64, (1,))
+
+
+def pack_flocks(zones, members):
+    """The per-zone companions of navhip_arrival_flock_update and the member arrays of every zone side by side (one
+    spare row each, so that none is empty): (ArrivalFlock array, dict of arrays)."""
+    fs = (ArrivalFlock * max(1, len(zones)))()
+    parts = {name: [] for name, _, _ in NavContext._AF_IN}
+    mo = 0
+    for i, (z, mem) in enumerate(zip(zones, members)):
+        n = len(mem["uid"])
+        fs[i] = ArrivalFlock(int(z["phase"]), int(z["realloc_counter"]), int(z["stall_counter"]), int(z["prev_occ"]),
+                             float(z["row_height"]), float(z["arg_unit_radius"]), int(z["arg_total_members"]), int(z["arg_layer"]),
+                             mo, mo + n)
+        mo += n
+        for name, dt, width in NavContext._AF_IN:
+            parts[name].append(np.asarray(mem[name], dt).reshape((n, width) if width > 1 else (n,)))
+    cat = {name: np.ascontiguousarray(np.concatenate(parts[name] + [np.zeros((1, width) if width > 1 else (1,), dt)]))
+           for name, dt, width in NavContext._AF_IN}
+    return fs, cat
+
+
+def unpack_flocks(zs, fs, res, nz):
+    """What navhip_arrival_flock_update left: (per zone a dict of the zone's and the companion's members and its
+    slot_ring, per zone a dict of the member outputs, status [nz])."""
+    zones, members = [], []
+    for i in range(nz):
+        z, f = zs[i], fs[i]
+        d = {name: getattr(z, name) for name in ("unit_radius", "fill_frac", "radius", "layer", "active_row", "num_rows")}
+        d.update({name: getattr(f, name) for name in ("phase", "realloc_counter", "stall_counter", "prev_occ")})
+        d["slot_ring"] = np.array(res["slot_ring"][z.slot_begin:z.slot_end])
+        zones.append(d)
+        members.append({name: np.array(res[name][f.member_begin:f.member_end]) for name, _, _ in NavContext._AF_OUT})
+    return zones, members, np.array(res["status"][:nz])
 
 
 def make_reqs(n):
@@ -1097,6 +1158,43 @@ class NavContext(_Handle):
     def arrival_velocity_dev(self, world, vel_in, vel_out, stream=None):
         """navhip_arrival_velocity_dev: a World, an ArrivalVelIn and an ArrivalVelOut of device pointers; asynchronous."""
         self._call("navhip_arrival_velocity_dev", C.byref(world), C.byref(vel_in), C.byref(vel_out), _stream(stream))
+
+    # the members of navhip_arrival_flock a caller gives per zone, and the per-member arrays: (name, element type, width)
+    _AF_FLOCK = ("phase", "realloc_counter", "stall_counter", "prev_occ", "row_height", "unit_radius", "total_members", "layer")
+    _AF_IN = (("uid", np.int32, 1), ("settled", np.uint8, 1), ("substate", np.uint8, 1), ("sink_valid", np.uint8, 1),
+              ("sink_xz", np.float32, 2))
+    _AF_OUT = (("substate", np.uint8, 1), ("sink_valid", np.uint8, 1), ("sink_xz", np.float32, 2))
+
+    def arrival_flock_update(self, arrays, zones, region_keys, members, patch=None):
+        """The built-zone branch of G_Arrival_UpdateFlock (arrival.c:767) for a batch of zones, host buffers.  arrays: the
+        world (pos_xz); zones: dicts as for arrival_settle plus phase, realloc_counter, stall_counter, prev_occ, row_height,
+        and the call's arguments as arg_unit_radius, arg_total_members, arg_layer; region_keys: per zone a sorted u64
+        array; members: per zone a dict of its member rows in the reference's order (uid, settled, substate, sink_valid,
+        sink_xz).  patch: a function of (ArrivalFlockIn, ArrivalFlockOut, zones array, flocks array) that may damage the
+        call before it is made.  Returns (zones after the call as dicts of the members that can change, per-zone lists of
+        the member outputs, status [n_zones])."""
+        w, keep = self._world(arrays)
+        zs, slots, ring, keys = _pack_zones(zones, region_keys)
+        fs, cat = pack_flocks(zones, members)
+        nz, nm = len(zones), len(cat["uid"]) - 1
+        fi = ArrivalFlockIn()
+        fi.n_zones, fi.nm, fi.n_slots, fi.n_keys = nz, nm, len(ring) - 1, len(keys) - 1
+        fi.zones, fi.flocks = C.addressof(zs), C.addressof(fs)
+        k = _point(fi, slots_xz=slots, slot_ring=ring, region_keys=keys, **cat)
+        zs_out, fs_out = (ArrivalZone * max(1, nz))(), (ArrivalFlock * max(1, nz))()
+        res = {name: np.zeros((nm + 1, width) if width > 1 else (nm + 1,), dt) for name, dt, width in self._AF_OUT}
+        res["slot_ring"], res["status"] = np.zeros(len(ring), np.int32), np.zeros(max(1, nz), np.uint8)
+        fo = ArrivalFlockOut()
+        fo.zones, fo.flocks = C.addressof(zs_out), C.addressof(fs_out)
+        _point(fo, **res)
+        if patch is not None:
+            patch(fi, fo, zs, fs)
+        self._call("navhip_arrival_flock_update", C.byref(w), C.byref(fi), C.byref(fo))
+        return unpack_flocks(zs_out, fs_out, res, nz)
+
+    def arrival_flock_update_dev(self, world, flock_in, flock_out, stream=None):
+        """navhip_arrival_flock_update_dev: a World, an ArrivalFlockIn and an ArrivalFlockOut of device pointers; asynchronous."""
+        self._call("navhip_arrival_flock_update_dev", C.byref(world), C.byref(flock_in), C.byref(flock_out), _stream(stream))
 
     # -- pool_api: the resident field pool --------------------------------------------------------------
     def pool_create(self, n_slots, n_dests):
