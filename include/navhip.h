@@ -1261,6 +1261,88 @@ int  navhip_arrival_flock_update(navhip_ctx *ctx, const navhip_world *world, con
 int  navhip_arrival_flock_update_dev(navhip_ctx *ctx, const navhip_world *dev_world, const navhip_arrival_flock_in *dev_in,
                                      const navhip_arrival_flock_out *dev_out, void *stream);
 
+/* The FIRST build of a zone: the `!built` branch of G_Arrival_UpdateFlock (arrival.c:784-848) for n_zones zones at once,
+ * which takes a zone from INACTIVE to FILLING.  Per zone, statement for statement: the gate (:785-788: total_members >=
+ * ARRIVAL_MIN_UNITS 4 and arrival_near_goal :377, a member with PFM_Vec2_Len(target - pos) < 150.0f), arrival_zone_radius
+ * (:363), centre = N_ClosestPathable(target) ? snapped : target (:801, nav.c:4126), arrival_approach_axis (:236: the float
+ * sum of the member positions in member order times 1.0f / n), arrival_build_slots (:181) over
+ * N_ClosestConnectedPathableTiles (nav.c:4192: the best-first 8-connected flood whose ties the heap of pqueue.h:109-208
+ * decides, replayed operation for operation, budget arrival_region_area :147) and N_TileKeysForPositions (nav.c:4304),
+ * arrival_thin_centered_slots (:196), the clear-line filter (:810-817, N_SegmentWithinRegion nav.c:4326), the centre of
+ * mass in slot order with its N_ClosestPathable and N_DestIDForPos (:819-830, nav.c:3367), arrival_order_slots_far_near
+ * (:231, slot_cmp_far_banded :130), and the tail :839-847: row_height, arrival_compute_geodesic_rings, the counters, and
+ * arrival_realloc_slots exactly as navhip_arrival_flock_update runs it for a zone below a quarter full.
+ * The two qsort calls (:210, :233) promise nothing for equal elements; glibc's qsort is a stable merge sort for arrays of
+ * this size, so the engine's behaviour on its platform is "ties keep their order", and that is the contract here: ties of
+ * the near-reference sort keep flood order, ties of the banded sort the order the clear-line filter left.
+ *
+ * In, per zone: a navhip_arrival_flock with phase INACTIVE and the call's arguments (unit_radius, total_members, layer,
+ * the member range), target_xz, and the zone's row of the zone table, of which only the ROOM is read: [slot_begin,
+ * slot_end) of slots_xz / slot_ring and [key_begin, key_end) of region_keys.  A zone needs room for
+ * area = arrival_region_area keys (min((int)(M_PI * radius * radius + 0.5f), 4096), radius = arrival_zone_radius) and for
+ * min(total_members, area) slots; the raw flood lives in the kernel's LDS.  Too little room (or a range that leaves the
+ * shared arrays) is NAVHIP_ERR_ARG in the host form and a NAVHIP_AB_HOST row in the resident form.
+ * Out (may alias in, array by array): the zone row (centre, unit_radius, radius, layer, fill_frac, active_row, num_rows,
+ * slot_end = slot_begin + num_slots, key_end = key_begin + num_region), the companion (phase FILLING, the counters,
+ * row_height), slots_xz / slot_ring / region_keys inside the new ranges, axis_xz, com_xz, com_dest_id (what struct
+ * arrival_state has and the table lacks: com_row and G_Arrival_RequestField need them), the members' state, status.
+ * world: n_ents, pos_xz, map_pos.  Needs the COST_BASE and BLOCKERS planes of the layers the flocks name. */
+#define NAVHIP_AB_WAIT      0x01   /* the gate said not yet: every output repeats its input (axis_xz, com_xz and com_dest_id,
+                                      which have none, are not written), phase stays INACTIVE                               */
+#define NAVHIP_AB_HOST      0x80   /* not decided, never a wrong answer: outputs as for NAVHIP_AB_WAIT.  A layer without cost
+                                      or blockers plane; a member uid outside the world; a phase other than INACTIVE; a
+                                      unit_radius that is not a positive finite number; too little room; a target or a centre
+                                      of mass that is NaN or off the map (the reference asserts; (0, 0) off the map when no
+                                      slot survives included); a NAVHIP_DQ_HOST answer of either N_ClosestPathable; a flood
+                                      that meets an unvisited on-map neighbour outside the WINDOW of
+                                      NAVHIP_AB_WINDOW_R tiles (Chebyshev) around the centre tile; a heap that would hold
+                                      more than NAVHIP_AB_HEAP_NODES nodes                                                  */
+#define NAVHIP_AB_WINDOW_R   127
+#define NAVHIP_AB_HEAP_NODES 4096
+typedef struct navhip_arrival_build_in {
+    int32_t  n_zones;
+    int32_t  nm;                      /* rows of the member arrays                                              */
+    int32_t  n_slots;                 /* rows of slots_xz / slot_ring                                           */
+    int32_t  n_keys;                  /* rows of region_keys                                                    */
+    const navhip_arrival_zone  *zones;  /* [n_zones] slot_begin/slot_end, key_begin/key_end: the zone's room    */
+    const navhip_arrival_flock *flocks; /* [n_zones] phase INACTIVE, the call's arguments, the member range     */
+    const float    *target_xz;        /* [n_zones][2] the call's target_xz                                      */
+    const float    *slots_xz;         /* [n_slots][2] what the rooms hold now: repeated on WAIT / HOST rows     */
+    const int32_t  *slot_ring;        /* [n_slots]                                                              */
+    const uint64_t *region_keys;      /* [n_keys]                                                               */
+    const int32_t  *uid;              /* [nm] the member (row of world->pos_xz), the reference's member order   */
+    const uint8_t  *settled;          /* [nm] arrival_member.settled                                            */
+    const uint8_t  *substate;         /* [nm] arrival_unit_state.substate                                       */
+    const uint8_t  *sink_valid;       /* [nm] .sink_valid                                                       */
+    const float    *sink_xz;          /* [nm][2] .sink                                                          */
+} navhip_arrival_build_in;
+typedef struct navhip_arrival_build_out {
+    navhip_arrival_zone  *zones;      /* [n_zones] the zone table after the call                                */
+    navhip_arrival_flock *flocks;     /* [n_zones] the companion after the call                                 */
+    float    *slots_xz;               /* [n_slots][2] arrival_state.slots, far -> near                          */
+    int32_t  *slot_ring;              /* [n_slots]                                                              */
+    uint64_t *region_keys;            /* [n_keys] ascending inside a zone                                       */
+    float    *axis_xz;                /* [n_zones][2] arrival_state.axis                                        */
+    float    *com_xz;                 /* [n_zones][2] .com                                                      */
+    uint32_t *com_dest_id;            /* [n_zones] .com_dest_id (N_DestIDForPos, nav.c:3367)                    */
+    uint8_t  *substate;               /* [nm] arrival_unit_state after the call                                 */
+    uint8_t  *sink_valid;             /* [nm]                                                                   */
+    float    *sink_xz;                /* [nm][2]                                                                */
+    uint8_t  *status;                 /* [n_zones] 0 = built, NAVHIP_AB_WAIT, NAVHIP_AB_HOST                    */
+} navhip_arrival_build_out;
+/* Host buffers.  NAVHIP_ERR_ARG with the reason in navhip_last_error, before any launch and with the outputs untouched:
+ * a missing array, a negative count, a zone whose slot, key or member range leaves the shared arrays, and -- for a zone
+ * the call would go on to build (phase INACTIVE, a layer with its planes, every uid inside the world, the gate passed)
+ * -- too little room.  A zone that comes back NAVHIP_AB_WAIT needs no room. */
+int  navhip_arrival_zone_build(navhip_ctx *ctx, const navhip_world *world, const navhip_arrival_build_in *in,
+                               const navhip_arrival_build_out *out);
+/* Everything resident on the device, asynchronous on `stream`, no allocation: two launches, a workgroup per zone each
+ * (the build; navhip_arrival_flock_update's kernel for the tail).  out may alias in array by array.  Behind it
+ * navhip_arrival_flock_update_dev, navhip_arrival_velocity_dev and navhip_arrival_settle_dev on the same device arrays
+ * see a FILLING zone. */
+int  navhip_arrival_zone_build_dev(navhip_ctx *ctx, const navhip_world *dev_world, const navhip_arrival_build_in *dev_in,
+                                   const navhip_arrival_build_out *dev_out, void *stream);
+
 /* N_DesiredGroupArrivalVelocity (nav.c:3561) for nq points: the direction under each point in the chunk
  * field of mapping row rows[q] (region_field_slot / field_pool as in navhip_world; resident pool: pass
  * region_field_slot = field_pool = NULL), and whether that tile is a sink inside the zone's disc

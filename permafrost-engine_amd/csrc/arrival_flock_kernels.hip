@@ -1,7 +1,8 @@
 // arrival_flock_kernels.hip -- the built-zone branch of G_Arrival_UpdateFlock (arrival.c:767-853) on the device: the
 // all-settled arm, arrival_zone_radius (:363), the realloc period, and arrival_realloc_slots (:391-516) with
 // arrival_compute_geodesic_rings (:257-302) over N_RegionGeodesicDist (nav.c:4389-4460).  The first build of a zone
-// (:796-848) stays the host's.  Kernel AND its C entry points (include/navhip.h: navhip_arrival_flock_update[_dev]).
+// (:784-848) is arrival_build_kernels.hip's, which launches this kernel for its tail (first_build below).  Kernel AND
+// its C entry points (include/navhip.h: navhip_arrival_flock_update[_dev]).
 //
 // One workgroup of four waves per zone.  The zone's keys, BFS distances, slots, slot rings, occupied bits and per-ring
 // counters live in LDS (the reference caps keys and slots at ARRIVAL_MAX_SLOTS = 4 096 each).  Every part of the rule
@@ -17,6 +18,7 @@
 #include "navhip_internal.h"
 #include "agent_internal.h"
 #include "agent_math.h"
+#include "arrival_region.h"     // af_key, af_key_index, af_zone_radius
 
 #define AF_CAP      4096        /* ARRIVAL_MAX_SLOTS, arrival.h:47: slots, keys and so rows of a zone           */
 #define AF_THREADS  256
@@ -49,23 +51,6 @@ __device__ __forceinline__ void af_wave_min(uint32_t &key, int &at)
     }
 }
 
-__device__ __forceinline__ uint64_t af_key(int chunk_r, int chunk_c, int tile_r, int tile_c)    // td_key, nav.c:207
-{
-    return ((uint64_t)chunk_r << 48) | ((uint64_t)chunk_c << 32) | ((uint64_t)tile_r << 16) | (uint64_t)tile_c;
-}
-
-__device__ int af_key_index(const uint64_t *keys, int num, uint64_t k)     // region_key_index, nav.c:4369
-{
-    int lo = 0, hi = num;
-    while(lo < hi) {
-        const int mid = lo + (hi - lo) / 2;
-        const uint64_t v = keys[mid];
-        if(v == k) return mid;
-        if(v < k) lo = mid + 1; else hi = mid;
-    }
-    return -1;
-}
-
 // index of the key of the point's tile, -1 off the map or off the region (arrival_in_region, arrival.c:153: the walk of
 // N_SegmentWithinRegion from a point to itself is its tile)
 __device__ __forceinline__ int af_point_key(const nh_step_params &P, float x, float z, const uint64_t *keys, int num)
@@ -84,21 +69,15 @@ __device__ __forceinline__ void af_copy_member(const navhip_arrival_flock_in &in
     out.sink_xz[2 * m] = sx; out.sink_xz[2 * m + 1] = sz;
 }
 
-// arrival_zone_radius, arrival.c:363: `ntiles / M_PI` is a double, narrowed for sqrtf
-__device__ __forceinline__ int af_zone_radius(int nunits, float unit_radius)
-{
-    float per_unit = (1.85f * unit_radius) / 4.0f;                           // ARRIVAL_SLOT_SPACING, tile_dim
-    per_unit *= per_unit;
-    if(per_unit < 1.0f) per_unit = 1.0f;
-    const float ntiles = (float)nunits * per_unit;
-    const float root = nh_sqrt_ieee((float)((double)ntiles / 3.14159265358979323846));
-    return (int)(uint16_t)(int)(ceilf(root) + 3.0f);                         // ARRIVAL_ZONE_PAD
-}
-
-__global__ __launch_bounds__(AF_THREADS) void k_arrival_flock(nh_step_params P, navhip_arrival_flock_in in, navhip_arrival_flock_out out)
+// first_build (or null): the status row of navhip_arrival_zone_build behind whose kernel this one runs -- the tail of the
+// `!built` branch (arrival.c:839-847).  A zone that kernel built (status 0, phase FILLING, counters and fill_frac 0) takes
+// the realloc below without the all-settled arm and without the counter; any other zone of that call is not touched.
+__global__ __launch_bounds__(AF_THREADS) void k_arrival_flock(nh_step_params P, navhip_arrival_flock_in in, navhip_arrival_flock_out out,
+                                                              const uint8_t *first_build)
 {
     __shared__ af_lds L;
     const int zi = (int)blockIdx.x;
+    if(first_build && first_build[zi] != 0) return;
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     navhip_arrival_zone Z = in.zones[zi];
     navhip_arrival_flock S = in.flocks[zi];
@@ -123,7 +102,9 @@ __global__ __launch_bounds__(AF_THREADS) void k_arrival_flock(nh_step_params P, 
     const bool all_settled = __syncthreads_or(unsettled) == 0;
 
     bool realloc = false;
-    if(!host && !all_settled) {
+    if(!host && first_build) {
+        realloc = M > 0;                                                    // (:840: num_rows >= 1 with a slot, 0 without)
+    }else if(!host && !all_settled) {
         Z.layer = S.layer;
         Z.radius = af_zone_radius(S.total_members, S.unit_radius);
         Z.unit_radius = S.unit_radius;
@@ -376,6 +357,12 @@ __global__ __launch_bounds__(AF_THREADS) void k_arrival_flock(nh_step_params P, 
 // ---------------------------------------------------------------------------------------------
 // C entry points
 // ---------------------------------------------------------------------------------------------
+void nh_launch_arrival_first_realloc(const nh_step_params &P, const navhip_arrival_flock_in &in, const navhip_arrival_flock_out &out,
+                                     const uint8_t *first_build, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_arrival_flock, dim3(in.n_zones), dim3(AF_THREADS), 0, s, P, in, out, first_build);
+}
+
 namespace {
 
 // The one argument check of both forms; host_arrays: the arrays can be read here, so what lies IN them is checked too.
@@ -429,7 +416,8 @@ int navhip_arrival_flock_update_dev(navhip_ctx *ctx, const navhip_world *w, cons
     P.map_x = w->map_pos_x; P.map_z = w->map_pos_z;
     P.n_ents = w->n_ents; P.hz = w->hz;
     P.pos_xz = w->pos_xz;
-    hipLaunchKernelGGL(k_arrival_flock, dim3(in->n_zones), dim3(AF_THREADS), 0, stream ? (hipStream_t)stream : ctx->stream, P, *in, *out);
+    hipLaunchKernelGGL(k_arrival_flock, dim3(in->n_zones), dim3(AF_THREADS), 0, stream ? (hipStream_t)stream : ctx->stream, P, *in, *out,
+                       (const uint8_t*)nullptr);
     HIPCHK(ctx, hipGetLastError());
     return NAVHIP_OK;
 }

@@ -139,7 +139,9 @@ template <bool ISL> __device__ __forceinline__ dq_cand dq_candidate(const dq_map
 //   ISL = true   n_closest_island_tiles: the hits in the reference's order in tiles[] ((row, column) pairs of int16 as one
 //                word), their number in *n_hits; returns 1.
 // Either returns -1 when the flood leaves the window (NAVHIP_DQ_HOST).
-template <bool ISL> __device__ int dq_flood(const dq_map &M, const dq_layer &L, int sr, int sc, uint32_t giid,
+// (internal linkage, like dq_flood_first below: two units instantiate it, and on the host emulator each copy must use the
+// cross-lane primitives of its own unit)
+template <bool ISL> static __device__ int dq_flood(const dq_map &M, const dq_layer &L, int sr, int sc, uint32_t giid,
                                             uint16_t (*fr)[DQ_FRONTIER], uint32_t *ring,
                                             int *ans_r, int *ans_c, uint32_t *tiles, int *n_hits)
 {
@@ -282,7 +284,7 @@ template <bool ISL> __device__ int dq_flood(const dq_map &M, const dq_layer &L, 
 // in the ISL = false arm, candidates outside the window are tested as well: the reference pops the whole level in front of
 // the hit, and only a NEXT level needs the window.  Returns 1 with the tile in *ans_r / *ans_c, 0 when the flood visited
 // the whole map without a hit, -1 when it has to leave the window (NAVHIP_SQ_HOST).
-__device__ inline int dq_flood_first(const dq_map &M, const dq_layer &L, int sr, int sc, uint32_t giid,
+static __device__ inline int dq_flood_first(const dq_map &M, const dq_layer &L, int sr, int sc, uint32_t giid,
                                      uint16_t (*fr)[DQ_FRONTIER], uint32_t *ring, int *ans_r, int *ans_c)
 {
     const int lane = (int)(threadIdx.x & 63);

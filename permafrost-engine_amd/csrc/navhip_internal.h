@@ -370,6 +370,10 @@ bool nh_async_resident(navhip_ctx *ctx, navhip_world *w, navhip_step_out *o);   
 int  nh_async_slabs(navhip_ctx *ctx, size_t in_bytes, size_t out_bytes, char **h_in, char **h_out);
 bool nh_is_pinned(const void *p);
 int  nh_refresh_derived(navhip_ctx *ctx, hipStream_t s);    // the derived row masks (passmask / probemask / facmask) of dirty chunks, rebuilt
+// arrival_flock_kernels.hip: k_arrival_flock as the tail of a first build (arrival.c:839-847) behind k_arrival_build --
+// zones with first_build[z] == 0 take arrival_realloc_slots, the others are not touched
+void nh_launch_arrival_first_realloc(const struct nh_step_params &P, const navhip_arrival_flock_in &in, const navhip_arrival_flock_out &out,
+                                     const uint8_t *first_build, hipStream_t s);
 int  nh_spatial_query_dev(navhip_ctx *ctx, const navhip_world *dev_w, const float *d_query, int nq, float range, int maxout,
                           int32_t *d_counts, uint32_t *d_ids, hipStream_t s);
 const uint8_t *nh_pool_fields(const navhip_ctx *ctx);

@@ -230,6 +230,21 @@ class ArrivalFlockOut(C.Structure):
                 ("sink_valid", C.c_void_p), ("sink_xz", C.c_void_p), ("status", C.c_void_p)]
 
 
+class ArrivalBuildIn(C.Structure):
+    """navhip_arrival_build_in, include/navhip.h"""
+    _fields_ = [("n_zones", C.c_int32), ("nm", C.c_int32), ("n_slots", C.c_int32), ("n_keys", C.c_int32),
+                ("zones", C.c_void_p), ("flocks", C.c_void_p), ("target_xz", C.c_void_p), ("slots_xz", C.c_void_p),
+                ("slot_ring", C.c_void_p), ("region_keys", C.c_void_p), ("uid", C.c_void_p), ("settled", C.c_void_p),
+                ("substate", C.c_void_p), ("sink_valid", C.c_void_p), ("sink_xz", C.c_void_p)]
+
+
+class ArrivalBuildOut(C.Structure):
+    """navhip_arrival_build_out, include/navhip.h"""
+    _fields_ = [("zones", C.c_void_p), ("flocks", C.c_void_p), ("slots_xz", C.c_void_p), ("slot_ring", C.c_void_p),
+                ("region_keys", C.c_void_p), ("axis_xz", C.c_void_p), ("com_xz", C.c_void_p), ("com_dest_id", C.c_void_p),
+                ("substate", C.c_void_p), ("sink_valid", C.c_void_p), ("sink_xz", C.c_void_p), ("status", C.c_void_p)]
+
+
 class LosChainStats(C.Structure):
     """navhip_los_chain_stats, include/navhip.h"""
     _fields_ = [("slots", C.c_int32), ("levels", C.c_int32), ("stale", C.c_int32), ("rebuilt", C.c_int32),
@@ -339,6 +354,9 @@ _SIGS = {
     # arrival_flock_kernels: the built-zone branch of G_Arrival_UpdateFlock
     "navhip_arrival_flock_update": (_I, [_P, _WORLD, C.POINTER(ArrivalFlockIn), C.POINTER(ArrivalFlockOut)]),
     "navhip_arrival_flock_update_dev": (_I, [_P, _WORLD, C.POINTER(ArrivalFlockIn), C.POINTER(ArrivalFlockOut), _P]),
+    # arrival_build_kernels: the first build of a zone, the `!built` branch of G_Arrival_UpdateFlock
+    "navhip_arrival_zone_build": (_I, [_P, _WORLD, C.POINTER(ArrivalBuildIn), C.POINTER(ArrivalBuildOut)]),
+    "navhip_arrival_zone_build_dev": (_I, [_P, _WORLD, C.POINTER(ArrivalBuildIn), C.POINTER(ArrivalBuildOut), _P]),
     # dest_query_kernels: the destination queries of arrived()
     "navhip_dest_queries": (_I, [_P, _P, _I, _F, _F, _P, _P, _P, _I, _P]),
     "navhip_dest_queries_dev": (_I, [_P, _P, _I, _F, _F, _P, _P, _P, _I, _P, _P]),
@@ -405,6 +423,7 @@ RECORDS = {
     "navhip_arrival_zone": ArrivalZone, "navhip_settle_in": SettleIn, "navhip_settle_out": SettleOut,
     "navhip_arrival_vel_in": ArrivalVelIn, "navhip_arrival_vel_out": ArrivalVelOut,
     "navhip_arrival_flock": ArrivalFlock, "navhip_arrival_flock_in": ArrivalFlockIn, "navhip_arrival_flock_out": ArrivalFlockOut,
+    "navhip_arrival_build_in": ArrivalBuildIn, "navhip_arrival_build_out": ArrivalBuildOut,
     "navhip_los_chain_stats": LosChainStats, "navhip_tick_desc": TickDesc, "navhip_tick_info": TickInfo,
 }
 
@@ -1195,6 +1214,40 @@ class NavContext(_Handle):
     def arrival_flock_update_dev(self, world, flock_in, flock_out, stream=None):
         """navhip_arrival_flock_update_dev: a World, an ArrivalFlockIn and an ArrivalFlockOut of device pointers; asynchronous."""
         self._call("navhip_arrival_flock_update_dev", C.byref(world), C.byref(flock_in), C.byref(flock_out), _stream(stream))
+
+    def arrival_zone_build(self, arrays, zones, members, targets, patch=None):
+        """The first build of G_Arrival_UpdateFlock (arrival.c:784-848) for a batch of INACTIVE zones, host buffers.
+        arrays: the world (pos_xz); zones: dicts as for arrival_flock_update whose slots_xz / slot_ring and whose entry of
+        `keys` (a u64 array under "room_keys") are the zone's ROOM and what it holds now; members: per zone a dict of its
+        member rows; targets: [n_zones][2].  patch: as for arrival_flock_update.  Returns a dict: zs / fs (the two tables
+        after the call), slots_xz, slot_ring, region_keys (the shared arrays), axis_xz, com_xz, com_dest_id, substate,
+        sink_valid, sink_xz, status."""
+        w, keep = self._world(arrays)
+        zs, slots, ring, keys = _pack_zones(zones, [z["room_keys"] for z in zones])
+        fs, cat = pack_flocks(zones, members)
+        nz, nm = len(zones), len(cat["uid"]) - 1
+        bi = ArrivalBuildIn()
+        bi.n_zones, bi.nm, bi.n_slots, bi.n_keys = nz, nm, len(ring) - 1, len(keys) - 1
+        bi.zones, bi.flocks = C.addressof(zs), C.addressof(fs)
+        tgt = np.ascontiguousarray(np.concatenate([np.asarray(targets, np.float32).reshape(-1, 2), np.zeros((1, 2), np.float32)]))
+        k = _point(bi, slots_xz=slots, slot_ring=ring, region_keys=keys, target_xz=tgt, **cat)
+        zs_out, fs_out = (ArrivalZone * max(1, nz))(), (ArrivalFlock * max(1, nz))()
+        res = {name: np.zeros((nm + 1, width) if width > 1 else (nm + 1,), dt) for name, dt, width in self._AF_OUT}
+        res.update(slots_xz=np.full(slots.shape, -7.0, np.float32), slot_ring=np.full(ring.shape, -7, np.int32),
+                   region_keys=np.full(keys.shape, 7, np.uint64), axis_xz=np.full((nz + 1, 2), -7.0, np.float32),
+                   com_xz=np.full((nz + 1, 2), -7.0, np.float32), com_dest_id=np.full(nz + 1, 7, np.uint32),
+                   status=np.full(max(1, nz), 0x55, np.uint8))
+        bo = ArrivalBuildOut()
+        bo.zones, bo.flocks = C.addressof(zs_out), C.addressof(fs_out)
+        _point(bo, **res)
+        if patch is not None:
+            patch(bi, bo, zs, fs)
+        self._call("navhip_arrival_zone_build", C.byref(w), C.byref(bi), C.byref(bo))
+        return dict(res, zs=zs_out, fs=fs_out)
+
+    def arrival_zone_build_dev(self, world, build_in, build_out, stream=None):
+        """navhip_arrival_zone_build_dev: a World, an ArrivalBuildIn and an ArrivalBuildOut of device pointers; asynchronous."""
+        self._call("navhip_arrival_zone_build_dev", C.byref(world), C.byref(build_in), C.byref(build_out), _stream(stream))
 
     # -- pool_api: the resident field pool --------------------------------------------------------------
     def pool_create(self, n_slots, n_dests):
