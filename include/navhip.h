@@ -888,6 +888,49 @@ int  navhip_surround_queries_ex_dev(navhip_ctx *ctx, const navhip_world *dev_wor
                                     const int32_t *dev_units, const int32_t *dev_target, const int32_t *dev_target_set,
                                     int nq, uint8_t *dev_out_query, float *dev_out_dest_xz, void *stream);
 
+/* ---- the nav queries of an order on the device: reachable destination, tile in range ------------------------------------
+ *
+ * When a SET_DEST or SET_ENTER_RANGE command is carried out (move_process_cmds, movement.c:3246) the reference asks, per
+ * unit and on the main thread: M_NavClosestReachableInRange (do_set_enter_range, movement.c:3069-3092; combat.c:491 issues
+ * it for every ranged unit that picks a target), M_NavClosestReachableDest and M_NavDestIDForPos[Attacking] (do_set_dest,
+ * movement.c:2951-2972; make_flock :804, :845-847 once per flock) and M_NavLocationsReachable (combat.c:486).  One row of
+ * these entry points is that chain for one unit, from NAVHIP_PLANE_ISLANDS, bit for bit with the reference:
+ *   t = flags & NAVHIP_OQ_IN_RANGE  ? N_ClosestReachableInRange(src, dst, range, layer)  (nav.c:5067)  : dst
+ *   d = flags & NAVHIP_OQ_REACHABLE ? N_ClosestReachableDest(layer, src, t)              (nav.c:4085)  : t
+ *   out_dest_xz = d;  out_dest_id = faction == 15 (FACTION_ID_NONE) ? N_DestIDForPos(d, layer)
+ *                                                                   : N_DestIDForPosAttacking(d, layer, faction)
+ * Both flags: the nav part of do_set_enter_range.  NAVHIP_OQ_REACHABLE alone: that of do_set_dest / make_flock.  Neither: a
+ * dest id and the reachability bit.  `range` is the value the caller passes to N_ClosestReachableInRange: the arithmetic of
+ * movement.c:3080, :3091 and the already-in-range early-out stay the host's.  It is checked on every row, used or not.
+ * THE QUERIES READ THE ISLANDS PLANE ONLY, no blockers (the flood of N_ClosestReachableDest runs with ignore_blockers =
+ * true): the answers change only when the host uploads a new islands plane.
+ * The in-range tile is the CORNER of the winning tile (nav.c:5109-5112), the reachable destination the CENTRE of the first
+ * tile of the source's island in the flood's queue order (nav.c:4119-4122).  N_ClosestReachableDest's "no tile found:
+ * return xz_src" arm is written, and no world reaches it: the source's own tile is of the source's island, a hit once the
+ * flood gets there.  32 bytes. */
+typedef struct navhip_order_query { float src_x, src_z, dst_x, dst_z, range; int32_t layer; int32_t faction; uint32_t flags; } navhip_order_query;
+#define NAVHIP_OQ_IN_RANGE     0x1u   /* t = N_ClosestReachableInRange(src, dst, range, layer); else t = dst           */
+#define NAVHIP_OQ_REACHABLE    0x2u   /* d = N_ClosestReachableDest(layer, src, t); else d = t                         */
+#define NAVHIP_OQ_SAME_ISLAND  0x01   /* out_status: N_LocationsReachable(layer, src, dst) of the row's original dst (nav.c:4593) */
+#define NAVHIP_OQ_NO_TILE      0x02   /* out_status: the in-range search found no tile of the source's island and returned
+                                         the target (nav.c:5124)                                                       */
+#define NAVHIP_OQ_HOST         0x80   /* out_status: not decided here; the row's other bits are 0, its dest is (NaN, 0) and
+                                         its dest id 0.  Never a wrong answer.  For: a flood of N_ClosestReachableDest whose
+                                         answer lies outside the window of 127 x 127 tiles centred on the tile it starts on
+                                         (the rule of NAVHIP_DQ_HOST; a map that fits the window never does); in the resident
+                                         form, a row the host form refuses                                              */
+/* n rows, host buffers.  out_dest_xz [n][2], out_dest_id [n], out_status [n].
+ * NAVHIP_ERR_ARG, with the reason in navhip_last_error, before anything is launched and with the outputs untouched: a
+ * missing array; n < 0; unknown flag bits; a layer outside [0, NAVHIP_NAV_LAYER_MAX) or without a resident islands plane; a
+ * faction outside [0, 15]; a NaN coordinate or range; src or dst (the in-range search's target) off the map (the reference
+ * asserts there); ceil(range / 4) > 32 (a range above 128). */
+int  navhip_order_queries(navhip_ctx *ctx, const navhip_order_query *q, int n, float map_pos_x, float map_pos_z,
+                          float *out_dest_xz, uint32_t *out_dest_id, uint8_t *out_status);
+/* Everything resident on the device: ONE launch, asynchronous on `stream`, no allocation at all.  The rows are not readable
+ * before the launch: a row the host form would refuse comes back NAVHIP_OQ_HOST. */
+int  navhip_order_queries_dev(navhip_ctx *ctx, const navhip_order_query *dev_q, int n, float map_pos_x, float map_pos_z,
+                              float *dev_out_dest_xz, uint32_t *dev_out_dest_id, uint8_t *dev_out_status, void *stream);
+
 /* ---- more of entity_compute_update: the heading gate, the arms of the state switch that flags, a
  *      counter, an angle or a distance decide, the arrival overlay's settle rule, and all of it but the last in one call ----
  *

@@ -1,8 +1,8 @@
 // nav_flood.h -- the level-by-level replay of the reference's FIFO floods over the nav grid by one wave, device only: the
 // map view (dq_map: probemask rows and islands plane per layer), the tile of a point, the candidates of a level, their
 // ring positions and the floods themselves.  Shared by dest_query_kernels.hip (dq_flood: N_ClosestPathable and the island
-// tile list of N_IsMaximallyClose) and surround_query_kernels.hip (dq_flood_first: the first island tile next to a tile
-// of the target).  How a flood is replayed is described at the top of dest_query_kernels.hip.  Free of device variables,
+// tile list of N_IsMaximallyClose), surround_query_kernels.hip (dq_flood_first: the first island tile next to a tile
+// of the target) and order_query_kernels.hip (dq_flood_first without the blockers test: N_ClosestReachableDest).  How a flood is replayed is described at the top of dest_query_kernels.hip.  Free of device variables,
 // so any unit may include it.
 #pragma once
 #include "navhip_internal.h"
@@ -284,6 +284,9 @@ template <bool ISL> static __device__ int dq_flood(const dq_map &M, const dq_lay
 // in the ISL = false arm, candidates outside the window are tested as well: the reference pops the whole level in front of
 // the hit, and only a NEXT level needs the window.  Returns 1 with the tile in *ans_r / *ans_c, 0 when the flood visited
 // the whole map without a hit, -1 when it has to leave the window (NAVHIP_SQ_HOST).
+// BLK = false is the same flood with ignore_blockers = true (N_ClosestReachableDest, nav.c:4115): the island alone decides,
+// and the probemask rows are not read (order_query_kernels.hip).
+template <bool BLK = true>
 static __device__ inline int dq_flood_first(const dq_map &M, const dq_layer &L, int sr, int sc, uint32_t giid,
                                      uint16_t (*fr)[DQ_FRONTIER], uint32_t *ring, int *ans_r, int *ans_c)
 {
@@ -306,7 +309,7 @@ static __device__ inline int dq_flood_first(const dq_map &M, const dq_layer &L, 
                 const dq_cand k = dq_candidate<true>(M, sr, sc, f, i, j, R);
                 if(k.state == 0) continue;
                 const int r = sr + k.dr, c = sc + k.dc;
-                if((uint32_t)dq_island(M, L, r, c) == giid && !(dq_probe(M, L, r, c) & 2u)) hit_key = min(hit_key, k.key);
+                if((uint32_t)dq_island(M, L, r, c) == giid && (!BLK || !(dq_probe(M, L, r, c) & 2u))) hit_key = min(hit_key, k.key);
                 if(k.state == 2) out_key = min(out_key, k.key);
                 else atomicMin(&ring[dq_ring_pos<true>(k.dr, k.dc, R)], k.key);
             }

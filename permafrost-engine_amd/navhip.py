@@ -65,6 +65,9 @@ SQ_ADJACENT, SQ_HAS_DEST_0, SQ_HAS_DEST_1, SQ_HOST = 0x01, 0x02, 0x04, 0x80
 FS_MEMBER, FS_READY, FS_ASSIGNED, FS_IN_RANGE, FS_ARRIVED = 0x01, 0x02, 0x04, 0x08, 0x10
 DQ_NEAREST, DQ_TILES, DQ_HOST = 0x1, 0x2, 0x80
 DQ_MAX_TILES = 256                                                           # per query: FIELD_RES_R * 2 + FIELD_RES_C * 2
+OQ_IN_RANGE, OQ_REACHABLE = 0x1, 0x2                                         # navhip_order_query.flags
+OQ_SAME_ISLAND, OQ_NO_TILE, OQ_HOST = 0x01, 0x02, 0x80                       # out_status of the order queries
+FACTION_NONE = 15                                                            # FACTION_ID_NONE: a dest id without a faction
 
 # the whole tick behind one call
 TICK_SERIAL, TICK_TIME_FIELDS, TICK_OWNS_SNAPSHOT = 0x2, 0x8, 0x10
@@ -108,6 +111,11 @@ assert REGION_REQ_DTYPE.itemsize == 32
 # navhip_dest_query, include/navhip.h (16 bytes)
 DEST_QUERY_DTYPE = np.dtype([("x", np.float32), ("z", np.float32), ("layer", np.int32), ("flags", np.uint32)])
 assert DEST_QUERY_DTYPE.itemsize == 16
+
+# navhip_order_query, include/navhip.h (32 bytes)
+ORDER_QUERY_DTYPE = np.dtype([("src_x", np.float32), ("src_z", np.float32), ("dst_x", np.float32), ("dst_z", np.float32),
+                              ("range", np.float32), ("layer", np.int32), ("faction", np.int32), ("flags", np.uint32)])
+assert ORDER_QUERY_DTYPE.itemsize == 32
 
 
 class World(C.Structure):
@@ -366,6 +374,9 @@ _SIGS = {
     "navhip_static_targets_set": (_I, [_P, _I, _P, _P]),
     "navhip_surround_queries_ex": (_I, [_P, _WORLD, _P, _P, _P, _P, _I, _P, _P]),
     "navhip_surround_queries_ex_dev": (_I, [_P, _WORLD, _P, _P, _P, _P, _I, _P, _P, _P]),
+    # order_query_kernels: the nav queries of an order
+    "navhip_order_queries": (_I, [_P, _P, _I, _F, _F, _P, _P, _P]),
+    "navhip_order_queries_dev": (_I, [_P, _P, _I, _F, _F, _P, _P, _P, _P]),
     # pool_api: the resident field pool
     "navhip_pool_create": (_I, [_P, _I, _I]),
     "navhip_pool_destroy": (None, [_P]),
@@ -417,7 +428,8 @@ _SIGS = {
 # ---------------------------------------------------------------------------------------------
 RECORDS = {
     "navhip_field_req": FIELD_REQ_DTYPE, "navhip_circle": CIRCLE_DTYPE, "navhip_los_req": LOS_REQ_DTYPE,
-    "navhip_region_req": REGION_REQ_DTYPE, "navhip_dest_query": DEST_QUERY_DTYPE, "navhip_world": World, "navhip_step_out": StepOut,
+    "navhip_region_req": REGION_REQ_DTYPE, "navhip_dest_query": DEST_QUERY_DTYPE, "navhip_order_query": ORDER_QUERY_DTYPE,
+    "navhip_world": World, "navhip_step_out": StepOut,
     "navhip_state_in": StateIn, "navhip_state_aux_in": StateAuxIn, "navhip_gate_in": GateIn,
     "navhip_state_pass_in": StatePassIn, "navhip_state_pass_out": StatePassOut,
     "navhip_arrival_zone": ArrivalZone, "navhip_settle_in": SettleIn, "navhip_settle_out": SettleOut,
@@ -1060,6 +1072,22 @@ class NavContext(_Handle):
         else:
             self._call("navhip_surround_queries_ex_dev", C.byref(world), dev_ptr(d_new_vel_xz), _opt(d_units, dev_ptr),
                        dev_ptr(d_target), dev_ptr(d_target_set), int(nq), dev_ptr(d_query), dev_ptr(d_dest_xz), _stream(stream))
+
+    # -- order_query_kernels: the nav queries of an order ------------------------------------------------
+    def order_queries(self, queries):
+        """N_ClosestReachableInRange (nav.c:5067), N_ClosestReachableDest (nav.c:4085), N_LocationsReachable and
+        N_DestIDForPos[Attacking] for the ORDER_QUERY_DTYPE records `queries` (flags OQ_IN_RANGE | OQ_REACHABLE).  Returns
+        (dest_xz [n][2], dest_id [n] uint32, status [n]: OQ_SAME_ISLAND | OQ_NO_TILE, or OQ_HOST with (NaN, 0) and id 0)."""
+        q = _arr(queries, ORDER_QUERY_DTYPE)
+        n = len(q)
+        dest, ids, status = np.zeros((n, 2), np.float32), np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+        self._call("navhip_order_queries", _hp(q), n, *self.map_pos(), _hp(dest), _hp(ids), _hp(status))
+        return dest, ids, status
+
+    def order_queries_dev(self, d_queries, n, d_dest_xz, d_dest_id, d_status, stream=None):
+        """navhip_order_queries_dev: every buffer a torch CUDA tensor, one launch, asynchronous on `stream`."""
+        self._call("navhip_order_queries_dev", dev_ptr(d_queries), int(n), *self.map_pos(), dev_ptr(d_dest_xz),
+                   dev_ptr(d_dest_id), dev_ptr(d_status), _stream(stream))
 
     def state_update_aux(self, arrays, fstate, wait_ticks_left, wait_prev, new_pos_xz, state, flags, work=None,
                          ent_rot=None, target_dir=None, range_in=None, surround=None, vdes_xz=None, hz=20):
