@@ -42,6 +42,8 @@ SELECTION = [
     "tests/test_field_shapes_gpu.py",  # chunk fields 2 079 levels deep, every depth boundary, the diagonal rule; region and LOS fields on the shapes
     "tests/test_dispatch_gpu.py",      # the work-list dispatch: sparse lists taking turns on one context, an empty slab between them
     "tests/test_cohesion_gpu.py",      # the cohesion launch plan: 1, 63, 64 and 65 flocks with empty ones, a slab that leaves flocks without a member
+    "tests/test_cp_lattice_gpu.py",    # ClearPath inside lattices and equal-distance rings: ties among candidates and at removals (8 + 0.3 + 16 s)
+    "tests/test_line_worlds_gpu.py",   # the step on tile lines, centres, chunk seams and corners, watersheds (15 s); formations on a lattice (44 s)
 ]
 # (agents: the tests that need torch.cuda, and the ones that take more than ~10 s each on the emulator)
 DESELECT = ["test_prefetch_overlap_gives_identical_results", "test_shared_chunk_fields_give_identical_results",
@@ -124,7 +126,7 @@ def test_gpu_parity_tests_pass_on_the_emulated_library(strict):
     assert r.returncode == 0, tail
     last = r.stdout.strip().splitlines()[-1]
     assert " passed" in last and "failed" not in last and "error" not in last, tail
-    assert int(last.split(" passed")[0].split()[-1]) >= (141 if strict else 13), tail          # (the selection really ran)
+    assert int(last.split(" passed")[0].split()[-1]) >= (146 if strict else 13), tail          # (the selection really ran)
 
 
 def test_reference_binding_drives_the_emulated_library():
