@@ -264,6 +264,45 @@ int  navhip_build_region_fields_dev(navhip_ctx *ctx, const navhip_region_req *de
                                     const int16_t *dev_overlay, uint8_t *dev_inout,
                                     size_t out_stride, void *stream);
 
+/* One N_CellArrivalFieldUpdateToNearestPathable(rdim = cdim = dim, layer, start, center, inout, overlay) call
+ * (field.c:2603): the pass of cell_field_fixup_task (formation.c:3160) that leads a unit out of the blocked ground it
+ * stands on.  Tiles are absolute (chunk * 64 + tile).  The library derives what the reference derives: base = centre -
+ * dim / 2 per axis, NOT shifted by a target clamp as N_CellArrivalFieldCreate's is (:2654 against :2483), and the
+ * clamped region of the flood (clamped_region :1892; where its far clamp binds, the map's last row or column is not
+ * part of the flood).  field_passable_frontier (:1441) floods the blocked ground around `start` over the clamped region
+ * and emits the passable tiles beside it -- with the reference's visited index dr * R + dc, which is not injective for a
+ * clamped region of more columns than rows (C > R): the FIFO is then replayed operation for operation --; the emitted
+ * tiles get 0; field_build_integration_nonpass_region (:678) runs over [base, base + dim)^2 into the tiles that are not
+ * passable or lie under the overlay, at the cost_base of the tile entered; every on-map tile with a finite non-zero value
+ * gets field_flow_dir (:355), every other nibble keeps what it held.  `enemies` plays no part.  20 bytes. */
+typedef struct navhip_region_repair_req {
+    uint8_t  layer;
+    uint8_t  reserved;                      /* 0 */
+    uint16_t dim;                           /* even, 2..128 */
+    int16_t  centre_abs_r, centre_abs_c;
+    int16_t  start_abs_r, start_abs_c;      /* the unit's tile: not passable */
+    uint32_t overlay_begin, overlay_count;  /* a range of the call's overlay array of (abs_r, abs_c) int16 pairs */
+} navhip_region_repair_req;
+#define NAVHIP_RR_HOST 0x80   /* out_status: not decided here, the slot is untouched and the host decides.  Never a wrong
+                                 field.  For: a passable start tile (the reference asserts); a start or centre tile off the
+                                 map; a start outside the clamped region (the reference would index its visited array out
+                                 of bounds); a layer without resident cost_base and blockers planes; in the resident form,
+                                 a row the host form refuses */
+/* inout: n slots of `stride` >= dim * dim / 2 bytes, two 4-bit directions per byte as navhip_build_region_fields'
+ * out_mode 0 writes them, changed in place.  out_status [n]: 0 or NAVHIP_RR_HOST.
+ * NAVHIP_ERR_INVALID, with the reason in navhip_last_error, before anything is launched and with the buffers untouched: a
+ * missing array; n < 0; a dim that is odd, 0 or above 128; a layer outside [0, NAVHIP_NAV_LAYER_MAX); a stride below
+ * dim * dim / 2; an overlay range outside [0, n_overlay). */
+int  navhip_repair_region_fields(navhip_ctx *ctx, const navhip_region_repair_req *reqs, int n,
+                                 const int16_t *overlay, size_t n_overlay,
+                                 uint8_t *inout, size_t stride, uint8_t *out_status);
+/* Every buffer resident on the device, ONE launch on `stream`, no synchronisation: behind navhip_build_region_fields_dev
+ * on the same stream and over the same slots this is cell_field_fixup_task.  max_dim: an even bound >= every row's dim
+ * (it sizes the launch); a row the host form would refuse, or whose dim exceeds max_dim, comes back NAVHIP_RR_HOST. */
+int  navhip_repair_region_fields_dev(navhip_ctx *ctx, const navhip_region_repair_req *dev_reqs, int n, int max_dim,
+                                     const int16_t *dev_overlay, uint8_t *dev_inout, size_t stride,
+                                     uint8_t *dev_status, void *stream);
+
 /* ---- line-of-sight fields ------------------------------------------------- */
 
 /* One N_LOSFieldCreate(id, chunk_coord, target, priv, map_pos, ctx, out_los, prev_los) call

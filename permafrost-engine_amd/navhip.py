@@ -67,6 +67,7 @@ DQ_NEAREST, DQ_TILES, DQ_HOST = 0x1, 0x2, 0x80
 DQ_MAX_TILES = 256                                                           # per query: FIELD_RES_R * 2 + FIELD_RES_C * 2
 OQ_IN_RANGE, OQ_REACHABLE = 0x1, 0x2                                         # navhip_order_query.flags
 OQ_SAME_ISLAND, OQ_NO_TILE, OQ_HOST = 0x01, 0x02, 0x80                       # out_status of the order queries
+RR_HOST = 0x80                                                               # out_status of the region-field repair
 FACTION_NONE = 15                                                            # FACTION_ID_NONE: a dest id without a faction
 
 # the whole tick behind one call
@@ -107,6 +108,13 @@ REGION_REQ_DTYPE = np.dtype([("layer", np.uint8), ("out_mode", np.uint8), ("enem
                              ("coff", np.uint16), ("seed_begin", np.uint32), ("seed_count", np.uint32),
                              ("overlay_begin", np.uint32), ("overlay_count", np.uint32)])
 assert REGION_REQ_DTYPE.itemsize == 32
+
+# navhip_region_repair_req, include/navhip.h (20 bytes)
+REGION_REPAIR_REQ_DTYPE = np.dtype([("layer", np.uint8), ("reserved", np.uint8), ("dim", np.uint16),
+                                    ("centre_abs_r", np.int16), ("centre_abs_c", np.int16),
+                                    ("start_abs_r", np.int16), ("start_abs_c", np.int16),
+                                    ("overlay_begin", np.uint32), ("overlay_count", np.uint32)])
+assert REGION_REPAIR_REQ_DTYPE.itemsize == 20
 
 # navhip_dest_query, include/navhip.h (16 bytes)
 DEST_QUERY_DTYPE = np.dtype([("x", np.float32), ("z", np.float32), ("layer", np.int32), ("flags", np.uint32)])
@@ -377,6 +385,9 @@ _SIGS = {
     # order_query_kernels: the nav queries of an order
     "navhip_order_queries": (_I, [_P, _P, _I, _F, _F, _P, _P, _P]),
     "navhip_order_queries_dev": (_I, [_P, _P, _I, _F, _F, _P, _P, _P, _P]),
+    # region_repair_kernels: the nearest-pathable repair of a region field
+    "navhip_repair_region_fields": (_I, [_P, _P, _I, _P, _Z, _P, _Z, _P]),
+    "navhip_repair_region_fields_dev": (_I, [_P, _P, _I, _I, _P, _P, _Z, _P, _P]),
     # pool_api: the resident field pool
     "navhip_pool_create": (_I, [_P, _I, _I]),
     "navhip_pool_destroy": (None, [_P]),
@@ -428,7 +439,8 @@ _SIGS = {
 # ---------------------------------------------------------------------------------------------
 RECORDS = {
     "navhip_field_req": FIELD_REQ_DTYPE, "navhip_circle": CIRCLE_DTYPE, "navhip_los_req": LOS_REQ_DTYPE,
-    "navhip_region_req": REGION_REQ_DTYPE, "navhip_dest_query": DEST_QUERY_DTYPE, "navhip_order_query": ORDER_QUERY_DTYPE,
+    "navhip_region_req": REGION_REQ_DTYPE, "navhip_region_repair_req": REGION_REPAIR_REQ_DTYPE,
+    "navhip_dest_query": DEST_QUERY_DTYPE, "navhip_order_query": ORDER_QUERY_DTYPE,
     "navhip_world": World, "navhip_step_out": StepOut,
     "navhip_state_in": StateIn, "navhip_state_aux_in": StateAuxIn, "navhip_gate_in": GateIn,
     "navhip_state_pass_in": StatePassIn, "navhip_state_pass_out": StatePassOut,
@@ -893,6 +905,35 @@ class NavContext(_Handle):
             buf[:, :a.shape[1]] = a
         self._call("navhip_build_region_fields", _hp(reqs), n, _hp(seeds), len(seeds), _hp(ov), len(ov), _hp(buf), out_stride)
         return buf
+
+    def build_region_fields_dev(self, d_reqs, n, max_dim, d_seeds, d_overlay, d_inout, out_stride, stream=None):
+        """navhip_build_region_fields_dev: every buffer a torch CUDA tensor (d_overlay may be None), asynchronous on
+        `stream`."""
+        self._call("navhip_build_region_fields_dev", dev_ptr(d_reqs), int(n), int(max_dim), _opt(d_seeds, dev_ptr),
+                   _opt(d_overlay, dev_ptr), dev_ptr(d_inout), int(out_stride), _stream(stream))
+
+    def repair_region_fields(self, reqs, overlay=None, inout=None, stride=None):
+        """Batched N_CellArrivalFieldUpdateToNearestPathable (field.c:2603) through host buffers.  reqs:
+        REGION_REPAIR_REQ_DTYPE records; overlay: [k, 2] int16 absolute (row, col) tiles; inout: [n, >= dim * dim / 2] u8
+        packed fields (two directions per byte), copied.  Returns (fields [n, stride] u8, status [n]: 0 or RR_HOST with
+        the field as it came in)."""
+        reqs = _arr(reqs, REGION_REPAIR_REQ_DTYPE)
+        n = len(reqs)
+        ov = np.zeros((0, 2), np.int16) if overlay is None else _arr(overlay, np.int16, -1, 2)
+        a = np.asarray(inout, np.uint8).reshape(n, -1) if n else np.zeros((0, stride or 0), np.uint8)
+        if stride is None:
+            stride = a.shape[1]
+        buf = np.zeros((n, stride), np.uint8)
+        buf[:, :a.shape[1]] = a
+        status = np.zeros(n, np.uint8)
+        self._call("navhip_repair_region_fields", _hp(reqs), n, _hp(ov), len(ov), _hp(buf), stride, _hp(status))
+        return buf, status
+
+    def repair_region_fields_dev(self, d_reqs, n, max_dim, d_overlay, d_inout, stride, d_status, stream=None):
+        """navhip_repair_region_fields_dev: every buffer a torch CUDA tensor (d_overlay may be None), one launch,
+        asynchronous on `stream`; behind build_region_fields_dev on the same stream it is cell_field_fixup_task."""
+        self._call("navhip_repair_region_fields_dev", dev_ptr(d_reqs), int(n), int(max_dim), _opt(d_overlay, dev_ptr),
+                   dev_ptr(d_inout), int(stride), dev_ptr(d_status), _stream(stream))
 
     def N_LOSFieldCreate(self, reqs, prev=None):
         """Batched N_LOSFieldCreate (field.c:2085).  reqs: LOS_REQ_DTYPE; prev: [n,64,64] u8 previous

@@ -14,6 +14,10 @@
                       and the same requests without a faction, with navhip_last_fields_split beside each; and the
                       blocker update of 10 000 circles with a resident factions plane (k_refresh_touched keeps the
                       faction rows current)
+  k_region_repair     64 and 256 nearest-pathable repairs of cell arrival fields (dim 96) on a map with blocked blobs, per
+                      call: the resident form, the host-buffer form, and the round trip of the slots that a host-side
+                      repair would need instead.  The reference's own time for the same requests on one core:
+                      tests/tools/bench_region_repair.py
 Prints one JSON object."""
 import json
 import os
@@ -103,10 +107,52 @@ def field_attacking(torch, dev):
     return res
 
 
+def region_repair(torch, dev):
+    """navhip_repair_region_fields[_dev] per call against the transfers of a repair on the host."""
+    from tests.tools import bench_region_repair as brr
+    res = {"what": "dim %d, %d x %d chunks, 400 blocked blobs; requests of tests/tools/bench_region_repair.py" % (brr.DIM, brr.MAP, brr.MAP)}
+    stride = brr.DIM * brr.DIM // 2
+    for n in (64, 256):
+        cases = brr.world(n)
+        ctx = navhip.NavContext(brr.MAP, brr.MAP)
+        ctx.upload_plane(0, navhip.PLANE_COST_BASE, synth.to_chunks(cases[0]["cost"]))
+        ctx.upload_plane(0, navhip.PLANE_BLOCKERS, synth.to_chunks(cases[0]["blk"]))
+        reqs = np.zeros(n, navhip.REGION_REPAIR_REQ_DTYPE)
+        reqs["dim"] = brr.DIM
+        reqs["centre_abs_r"], reqs["centre_abs_c"] = np.array([c["centre"] for c in cases]).T
+        reqs["start_abs_r"], reqs["start_abs_c"] = np.array([c["start"] for c in cases]).T
+        fields = np.random.RandomState(1).randint(0, 256, (n, stride)).astype(np.uint8)
+        d_reqs = torch.from_numpy(reqs.view(np.uint8).reshape(n, 20)).to(dev)
+        d_io = torch.from_numpy(fields).to(dev)
+        d_st = torch.zeros(n, dtype=torch.uint8, device=dev)
+        st = torch.cuda.Stream(device=dev)
+        pinned = torch.empty((n, stride), dtype=torch.uint8).pin_memory()
+
+        def resident():
+            ctx.repair_region_fields_dev(d_reqs, n, brr.DIM, None, d_io, stride, d_st, stream=st.cuda_stream)
+            st.synchronize()
+
+        def round_trip():
+            with torch.cuda.stream(st):
+                pinned.copy_(d_io, non_blocking=True)
+                st.synchronize()                     # (the host's repair would run here)
+                d_io.copy_(pinned, non_blocking=True)
+            st.synchronize()
+        res["n%d" % n] = {"ms_resident": timed(resident, reps=20) * 1e3,
+                          "ms_host_api": timed(lambda: ctx.repair_region_fields(reqs, None, fields, stride), reps=10) * 1e3,
+                          "ms_round_trip_of_the_slots_pinned": timed(round_trip, reps=20) * 1e3,
+                          "host_rows": int((d_st.cpu().numpy() == navhip.RR_HOST).sum())}
+        ctx.close()
+    return res
+
+
 def main():
     import torch
     torch.cuda.init()
     dev = torch.device("cuda", 0)
+    if "--region-repair-only" in sys.argv:
+        print(json.dumps({"region_repair": region_repair(torch, dev)}, indent=1))
+        return
     if "--attacking-only" in sys.argv:
         print(json.dumps({"field_attacking": field_attacking(torch, dev)}, indent=1))
         return
@@ -198,6 +244,7 @@ def main():
     out["los_fields"] = {"fields": 4096, "ms_host_api": t * 1e3, "fields_per_s": 4096 / t}
     ctx.close()
     out["field_attacking"] = field_attacking(torch, dev)
+    out["region_repair"] = region_repair(torch, dev)
     print(json.dumps(out, indent=1))
 
 
