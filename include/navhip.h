@@ -449,6 +449,8 @@ enum { NAVHIP_STATE_MOVING = 0, NAVHIP_STATE_MOVING_IN_FORMATION, NAVHIP_STATE_A
 
 /* ENTITY_FLAG_* bits the step reads, entity.h:56-82 */
 #define NAVHIP_ENTITY_FLAG_MOVABLE      (1u << 3)
+#define NAVHIP_ENTITY_FLAG_COMBATABLE   (1u << 4)
+#define NAVHIP_ENTITY_FLAG_BUILDING     (1u << 8)
 #define NAVHIP_ENTITY_FLAG_WATER        (1u << 14)
 #define NAVHIP_ENTITY_FLAG_AIR          (1u << 15)
 #define NAVHIP_ENTITY_FLAG_GARRISONED   (1u << 18)
@@ -1424,6 +1426,65 @@ int  navhip_arrival_zone_build(navhip_ctx *ctx, const navhip_world *world, const
  * see a FILLING zone. */
 int  navhip_arrival_zone_build_dev(navhip_ctx *ctx, const navhip_world *dev_world, const navhip_arrival_build_in *dev_in,
                                    const navhip_arrival_build_out *dev_out, void *stream);
+
+/* ---- enemy-seek and surround fields from the snapshot (compute_async_fields, movement.c:4149-4164) ---------------- */
+
+/* The whole job of N_RequestAsyncEnemySeekField / N_RequestAsyncSurroundField: the seed tiles come from the snapshot on the
+ * device (field_enemies_initial_frontier field.c:1209, field_entity_initial_frontier :1317), the field from
+ * navhip_build_region_fields' kernel behind them (out_mode 1, enemies 0, the geometry of field.c:1558-1572, 1596-1597).
+ *   kind 0  the rectangle of the chunk widened by half a chunk + SEARCH_BUFFER (16) per side, in bitmap_grid.h's fixed point
+ *           (bg_ent_inrange_rect, inclusive bounds, the grid of world.grid_*); garrisoned entities dropped (G_Pos_EntsInRect);
+ *           field_enemy_ent :963 + ent_dying; M_Tile_AllUnderCircle + one contour of everything so far per layer step
+ *           (layer >= 3X3, >= 5X5, >= 7X7: every water and air layer three); tds[512] replayed in row-major order
+ *   kind 1  the circle of entity target_uid, contours for layer == 3X3, >= 5X5, >= 7X7; the tiles inside the region */
+#define NAVHIP_SEEK_ENEMIES 0   /* field_update_enemies, field.c:1537 (TARGET_ENEMIES) */
+#define NAVHIP_SEEK_ENTITY  1   /* field_update_entity,  field.c:1612 (TARGET_ENTITY)  */
+#define NAVHIP_SK_HOST   0x80   /* out_status: not decided here, slot and seed row untouched, never a wrong field.  For: a map
+                                   one chunk high or wide (the padded region is not square); a chunk outside the map; a layer
+                                   without resident cost_base and blockers planes; more than 4 096 entities in the rectangle,
+                                   garrisoned ones included (the reference truncates in its grid's cell order); a source entity
+                                   or the kind-1 target with ENTITY_FLAG_BUILDING (its OBB is not here), with ceil(radius / 4)
+                                   plus its contours above 31 (the 64 x 64 window), with a NaN radius or with a position that
+                                   is not finite or at or beyond 2^22 world units (no fixed-point value); target_uid outside
+                                   [0, n_ents); faction_id outside [0, 15] for kind 0; in the resident form, a kind above 1 or
+                                   a layer outside [0, NAVHIP_NAV_LAYER_MAX) */
+
+typedef struct navhip_seek_req {      /* one job of N_RequestAsyncEnemySeekField / ...SurroundField.  12 bytes */
+    uint8_t  kind, layer;
+    int16_t  chunk_r, chunk_c;        /* the chunk of curr_pos (nav.c:3789, :3844) */
+    int16_t  faction_id;              /* kind 0: enemies_desc.faction_id */
+    int32_t  target_uid;              /* kind 1: entity_desc.target */
+} navhip_seek_req;
+
+typedef uint16_t navhip_enemy_masks[16];   /* (a type of its own: a record of this header has no array declarator) */
+
+typedef struct navhip_seek_game {     /* what field.c asks game.c / combat.c / fog_of_war.c per entity */
+    const int32_t *faction;           /* [n_ents] G_GetFactionID */
+    const uint8_t *exclude;           /* [n_ents] or NULL: nonzero = dying (ent_dying) or not player-visible
+                                         (ent_player_visible): fog and death stay the host's, one byte per entity */
+    navhip_enemy_masks enemy_mask;    /* bit g of [f]: G_GetDiplomacyState(f, g) is known and DIPLOMACY_STATE_WAR */
+} navhip_seek_game;
+
+/* Host buffers.  inout: n chunk fields of one direction per byte, stride >= 4096, read-modify-write exactly as
+ * navhip_build_region_fields writes them in out_mode 1 (an unreached tile keeps its byte; a request without any seed
+ * returns status 0 with the slot as it was).  out_status [n]: 0 or NAVHIP_SK_HOST.  out_seed_bits, or NULL: n rows of
+ * 2 048 bytes, the request's has_enemy bitmap over the 128 x 128 region, row-major, bit r * 128 + c in byte (r * 128 + c) / 8
+ * (kind 1: the in-region tiles of the target).  Of `world` the call reads n_ents, pos_xz, radius, flags, map_pos_* and
+ * grid_*.  NAVHIP_ERR_INVALID, with the reason in navhip_last_error, before any launch and with the buffers untouched: a
+ * missing array (world, game, game->faction, pos_xz, radius, flags, reqs, inout, out_status), n < 0, stride < 4096, a
+ * negative n_ents, a kind above 1, a layer outside [0, NAVHIP_NAV_LAYER_MAX). */
+int  navhip_build_seek_fields(navhip_ctx *ctx, const navhip_world *world, const navhip_seek_game *game,
+                              const navhip_seek_req *reqs, int n, uint8_t *inout, size_t stride,
+                              uint8_t *out_status, uint8_t *out_seed_bits);
+/* Every buffer resident, two launches on `stream` (seeds; fields), no synchronisation.  dev_world and dev_game are HOST
+ * structures that cross by value and whose array pointers are DEVICE pointers, as navhip_world is in
+ * navhip_agent_step_dev: the scalars and enemy_mask are read at the call.  The seed lists and the navhip_region_req table
+ * between the two kernels live in the context (64 KB per request, grown on demand: a call with more requests than any
+ * before it allocates); one such call of a context in flight at a time, or all of them on one stream.  dev_seed_bits may be
+ * NULL.  A row the host form refuses comes back NAVHIP_SK_HOST. */
+int  navhip_build_seek_fields_dev(navhip_ctx *ctx, const navhip_world *dev_world, const navhip_seek_game *dev_game,
+                                  const navhip_seek_req *dev_reqs, int n, uint8_t *dev_inout, size_t stride,
+                                  uint8_t *dev_status, uint8_t *dev_seed_bits, void *stream);
 
 /* N_DesiredGroupArrivalVelocity (nav.c:3561) for nq points: the direction under each point in the chunk
  * field of mapping row rows[q] (region_field_slot / field_pool as in navhip_world; resident pool: pass

@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libnavhip.so")
-SOURCES = ["navhip_api.hip", "step_api.hip", "pool_api.hip", "submit_api.hip", "field_kernels.hip", "spatial_kernels.hip", "cohesion_kernels.hip", "agent_kernels.hip", "blocker_kernels.hip", "los_kernels.hip", "los_chain_api.hip", "region_kernels.hip", "region_repair_kernels.hip", "comm_api.hip", "state_kernels.hip", "dest_query_kernels.hip", "surround_query_kernels.hip", "order_query_kernels.hip", "arrival_flock_kernels.hip", "arrival_build_kernels.hip", "tick_api.hip", "stream_set.hip"]
+SOURCES = ["navhip_api.hip", "step_api.hip", "pool_api.hip", "submit_api.hip", "field_kernels.hip", "spatial_kernels.hip", "cohesion_kernels.hip", "agent_kernels.hip", "blocker_kernels.hip", "los_kernels.hip", "los_chain_api.hip", "region_kernels.hip", "region_repair_kernels.hip", "seek_seed_kernels.hip", "comm_api.hip", "state_kernels.hip", "dest_query_kernels.hip", "surround_query_kernels.hip", "order_query_kernels.hip", "arrival_flock_kernels.hip", "arrival_build_kernels.hip", "tick_api.hip", "stream_set.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
          # the agent kernels mirror the reference's C arithmetic operation by operation:

@@ -271,6 +271,7 @@ struct navhip_ctx {
     nh_buf       dest_query_scratch;    // dest_query_kernels.hip, navhip_dest_queries_dev: the counts and the unpacked tile lists of its queries
     nh_buf       surround_query_scratch; // surround_query_kernels.hip, navhip_surround_queries_dev: the rows' records, the work items, the tile answers
     nh_buf       static_sets;           // surround_query_kernels.hip, navhip_static_targets_set: CSR offsets [n + 1], then the tiles (row << 16 | column)
+    nh_buf       seek_scratch;          // seek_seed_kernels.hip, navhip_build_seek_fields_dev: the navhip_region_req table, then 64 KB of seed pairs per request
     int          static_sets_n = 0, static_sets_longest = 0;   // ... its sets, the entries of its longest list (first occurrences)
     nh_step_state step;                 // the agent step: its scratch and what it remembers between calls (step_api.hip)
     std::string  last_error;
@@ -296,7 +297,7 @@ static inline void nh_fill_map_view(const navhip_ctx *ctx, nh_map_view *mv)
 template<class F> static inline void nh_ctx_each_buf(navhip_ctx *ctx, F f)
 {
     nh_buf *one[] = {&ctx->d_dirty_list, &ctx->gen_list, &ctx->field_classes, &ctx->state_arrived, &ctx->state_arrived_n, &ctx->dest_query_scratch,
-                      &ctx->surround_query_scratch, &ctx->static_sets};
+                      &ctx->surround_query_scratch, &ctx->static_sets, &ctx->seek_scratch};
     for(nh_buf *b : one) f(*b);
     for(auto &b : ctx->step.buf) f(b);
     for(auto &b : ctx->stage) f(b);

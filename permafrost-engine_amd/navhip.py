@@ -68,6 +68,8 @@ DQ_MAX_TILES = 256                                                           # p
 OQ_IN_RANGE, OQ_REACHABLE = 0x1, 0x2                                         # navhip_order_query.flags
 OQ_SAME_ISLAND, OQ_NO_TILE, OQ_HOST = 0x01, 0x02, 0x80                       # out_status of the order queries
 RR_HOST = 0x80                                                               # out_status of the region-field repair
+SEEK_ENEMIES, SEEK_ENTITY, SK_HOST = 0, 1, 0x80                              # navhip_seek_req.kind; out_status of the seek fields
+ENTITY_FLAG_COMBATABLE, ENTITY_FLAG_BUILDING, ENTITY_FLAG_GARRISONED = 1 << 4, 1 << 8, 1 << 18   # entity.h, as the seed pass reads them
 FACTION_NONE = 15                                                            # FACTION_ID_NONE: a dest id without a faction
 
 # the whole tick behind one call
@@ -116,6 +118,11 @@ REGION_REPAIR_REQ_DTYPE = np.dtype([("layer", np.uint8), ("reserved", np.uint8),
                                     ("overlay_begin", np.uint32), ("overlay_count", np.uint32)])
 assert REGION_REPAIR_REQ_DTYPE.itemsize == 20
 
+# navhip_seek_req, include/navhip.h (12 bytes)
+SEEK_REQ_DTYPE = np.dtype([("kind", np.uint8), ("layer", np.uint8), ("chunk_r", np.int16), ("chunk_c", np.int16),
+                           ("faction_id", np.int16), ("target_uid", np.int32)])
+assert SEEK_REQ_DTYPE.itemsize == 12
+
 # navhip_dest_query, include/navhip.h (16 bytes)
 DEST_QUERY_DTYPE = np.dtype([("x", np.float32), ("z", np.float32), ("layer", np.int32), ("flags", np.uint32)])
 assert DEST_QUERY_DTYPE.itemsize == 16
@@ -145,6 +152,11 @@ class World(C.Structure):
         ("los_pool", C.c_void_p), ("flock_los_slot", C.c_void_p), ("los_pos_xz", C.c_void_p),
         ("n_los_slots", C.c_int32), ("static_epoch", C.c_uint32),
         ("region_row", C.c_void_p), ("region_field_slot", C.c_void_p), ("n_region_rows", C.c_int32)]
+
+
+class SeekGame(C.Structure):
+    """navhip_seek_game, include/navhip.h"""
+    _fields_ = [("faction", C.c_void_p), ("exclude", C.c_void_p), ("enemy_mask", C.c_uint16 * 16)]
 
 
 class StepOut(C.Structure):
@@ -388,6 +400,9 @@ _SIGS = {
     # region_repair_kernels: the nearest-pathable repair of a region field
     "navhip_repair_region_fields": (_I, [_P, _P, _I, _P, _Z, _P, _Z, _P]),
     "navhip_repair_region_fields_dev": (_I, [_P, _P, _I, _I, _P, _P, _Z, _P, _P]),
+    # seek_seed_kernels: enemy-seek and surround fields from the snapshot
+    "navhip_build_seek_fields": (_I, [_P, _WORLD, C.POINTER(SeekGame), _P, _I, _P, _Z, _P, _P]),
+    "navhip_build_seek_fields_dev": (_I, [_P, _WORLD, C.POINTER(SeekGame), _P, _I, _P, _Z, _P, _P, _P]),
     # pool_api: the resident field pool
     "navhip_pool_create": (_I, [_P, _I, _I]),
     "navhip_pool_destroy": (None, [_P]),
@@ -441,6 +456,7 @@ RECORDS = {
     "navhip_field_req": FIELD_REQ_DTYPE, "navhip_circle": CIRCLE_DTYPE, "navhip_los_req": LOS_REQ_DTYPE,
     "navhip_region_req": REGION_REQ_DTYPE, "navhip_region_repair_req": REGION_REPAIR_REQ_DTYPE,
     "navhip_dest_query": DEST_QUERY_DTYPE, "navhip_order_query": ORDER_QUERY_DTYPE,
+    "navhip_seek_req": SEEK_REQ_DTYPE, "navhip_seek_game": SeekGame,
     "navhip_world": World, "navhip_step_out": StepOut,
     "navhip_state_in": StateIn, "navhip_state_aux_in": StateAuxIn, "navhip_gate_in": GateIn,
     "navhip_state_pass_in": StatePassIn, "navhip_state_pass_out": StatePassOut,
@@ -709,6 +725,25 @@ def make_world(chunk_w, chunk_h, arrays, hz=20, xp=None):
     return w, keep
 
 
+def make_seek_game(faction, enemy_mask, exclude=None):
+    """A navhip_seek_game of numpy arrays (host form) or torch CUDA tensors (device form).  Returns (SeekGame, keepalive)."""
+    g = SeekGame()
+    keep = []
+    for name, a, dt in (("faction", faction, np.int32), ("exclude", exclude, np.uint8)):
+        if a is None:
+            setattr(g, name, None)
+        elif hasattr(a, "data_ptr"):
+            keep.append(a)
+            setattr(g, name, a.data_ptr())
+        else:
+            a = np.ascontiguousarray(a, dtype=dt)
+            keep.append(a)
+            setattr(g, name, a.ctypes.data)
+    for f, m in enumerate(enemy_mask):
+        g.enemy_mask[f] = int(m)
+    return g, keep
+
+
 def N_FlowFieldID(req):
     """N_FlowFieldID (field.c:1952) for one navhip_field_req record."""
     r = np.ascontiguousarray(np.asarray(req, dtype=FIELD_REQ_DTYPE).reshape(1))
@@ -934,6 +969,30 @@ class NavContext(_Handle):
         asynchronous on `stream`; behind build_region_fields_dev on the same stream it is cell_field_fixup_task."""
         self._call("navhip_repair_region_fields_dev", dev_ptr(d_reqs), int(n), int(max_dim), _opt(d_overlay, dev_ptr),
                    dev_ptr(d_inout), int(stride), dev_ptr(d_status), _stream(stream))
+
+    def build_seek_fields(self, world, faction, enemy_mask, reqs, inout, exclude=None, seed_bits=None):
+        """Enemy-seek (kind SEEK_ENEMIES) and surround (SEEK_ENTITY) chunk fields, seeds taken from the snapshot on the
+        device, through host buffers.  world: a host World (make_world) of which n_ents, pos_xz, radius, flags, map_pos_*
+        and grid_* are read; faction: [n_ents] i32; enemy_mask: 16 u16 (bit g of [f]: f is at war with g); exclude:
+        [n_ents] u8 or None; reqs: SEEK_REQ_DTYPE records; inout: [n, >= 4096] u8 chunk fields, copied; seed_bits:
+        [n, 2048] u8 to start from (rows of SK_HOST requests keep it) or None for zeros.
+        Returns (fields [n, stride] u8, status [n]: 0 or SK_HOST with the field as it came in, seed bits [n, 2048] u8)."""
+        reqs = _arr(reqs, SEEK_REQ_DTYPE)
+        n = len(reqs)
+        buf = np.array(np.asarray(inout, np.uint8).reshape(n, -1) if n else np.zeros((0, 4096), np.uint8), order="C")
+        status = np.zeros(n, np.uint8)
+        bits = np.zeros((n, 2048), np.uint8) if seed_bits is None else np.array(np.asarray(seed_bits, np.uint8).reshape(n, 2048), order="C")
+        g, keep = make_seek_game(faction, enemy_mask, exclude)
+        self._call("navhip_build_seek_fields", C.byref(world), C.byref(g), _hp(reqs), n, _hp(buf), buf.shape[1] if n else 4096,
+                   _hp(status), _hp(bits))
+        return buf, status, bits
+
+    def build_seek_fields_dev(self, dev_world, dev_game, d_reqs, n, d_inout, stride, d_status, d_seed_bits=None, stream=None):
+        """navhip_build_seek_fields_dev: dev_world (make_world of CUDA tensors) and dev_game (make_seek_game of CUDA
+        tensors) are host structures of device pointers; every other buffer a torch CUDA tensor; two launches,
+        asynchronous on `stream`."""
+        self._call("navhip_build_seek_fields_dev", C.byref(dev_world), C.byref(dev_game), dev_ptr(d_reqs), int(n), dev_ptr(d_inout),
+                   int(stride), dev_ptr(d_status), _opt(d_seed_bits, dev_ptr), _stream(stream))
 
     def N_LOSFieldCreate(self, reqs, prev=None):
         """Batched N_LOSFieldCreate (field.c:2085).  reqs: LOS_REQ_DTYPE; prev: [n,64,64] u8 previous

@@ -18,6 +18,13 @@
                       call: the resident form, the host-buffer form, and the round trip of the slots that a host-side
                       repair would need instead.  The reference's own time for the same requests on one core:
                       tests/tools/bench_region_repair.py
+  seek_fields         256 enemy-seek jobs (kind 0) on the configs[2] map with 100 000 entities of 3 factions, per call:
+                      navhip_build_seek_fields_dev with events round the call; its field part as navhip_build_region_fields_dev
+                      replayed on the very seed lists (uploaded once, events round it), the seed part as the difference; the
+                      parent's route for the grid half, navhip_build_region_fields fed by uploaded seeds (host buffers); and,
+                      where oracle/_ref is present, the reference's async batch of the same jobs all on the CPU and with the
+                      binding on (N_HIP_RegionRequest: the frontier extraction on the host, then one region build on the
+                      device) -- the binding's batch less the parent's region call is the host's seed extraction
 Prints one JSON object."""
 import json
 import os
@@ -146,10 +153,114 @@ def region_repair(torch, dev):
     return res
 
 
+def seek_fields(torch, dev):
+    """navhip_build_seek_fields_dev against the host's seed extraction and the parent's region build."""
+    W, n, nj = 16, 100_000, 256
+    rng = np.random.RandomState(7)
+    grid = synth.cost_grid(W, W, seed=1234)
+    cells = synth.passable_cells(grid)
+    pick = cells[rng.choice(len(cells), size=n, replace=False)]
+    pos = (synth.cell_centre(W, W, pick[:, 0], pick[:, 1]) + rng.uniform(-1.5, 1.5, (n, 2))).astype(np.float32)
+    radius = rng.choice([1.0, 1.0, 2.5, 4.0], size=n).astype(np.float32)
+    faction = rng.randint(0, 3, n).astype(np.int32)
+    flags = np.full(n, navhip.ENTITY_FLAG_MOVABLE | navhip.ENTITY_FLAG_COMBATABLE, np.uint32)
+    flags[rng.rand(n) < 0.1] &= ~np.uint32(navhip.ENTITY_FLAG_COMBATABLE)
+    masks = np.zeros(16, np.uint16)
+    masks[:3] = (0b110, 0b001, 0b010)
+    jobs = [(cr, cc, f) for cr in range(W) for cc in range(W) for f in range(3)]
+    jobs = [jobs[i] for i in rng.choice(len(jobs), nj, replace=False)]                  # distinct: the reference builds a job once
+    reqs = np.zeros(nj, navhip.SEEK_REQ_DTYPE)
+    reqs["chunk_r"], reqs["chunk_c"], reqs["faction_id"] = np.array(jobs).T
+    ctx = navhip.NavContext(W, W)
+    ctx.upload_plane(0, navhip.PLANE_COST_BASE, synth.to_chunks(grid))
+    ctx.upload_plane(0, navhip.PLANE_BLOCKERS, np.zeros((W, W, 64, 64), np.uint16))
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a).copy()).to(dev)
+    world, keep = navhip.make_world(W, W, {"pos_xz": t(pos), "radius": t(radius), "flags": t(flags.view(np.int32))})
+    game, keep2 = navhip.make_seek_game(t(faction), masks)
+    d_reqs = t(reqs.view(np.uint8).reshape(nj, 12))
+    d_io = torch.zeros((nj, 4096), dtype=torch.uint8, device=dev)
+    d_st = torch.zeros(nj, dtype=torch.uint8, device=dev)
+    d_bits = torch.zeros((nj, 2048), dtype=torch.uint8, device=dev)
+    st = torch.cuda.Stream(device=dev)
+
+    def by_events(fn, reps=20):
+        fn(); st.synchronize()
+        ms = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(st); fn(); b.record(st); st.synchronize()
+            ms.append(a.elapsed_time(b))
+        return {"ms_mean": float(np.mean(ms)), "ms_min": float(np.min(ms)), "ms_max": float(np.max(ms))}
+
+    total = by_events(lambda: ctx.build_seek_fields_dev(world, game, d_reqs, nj, d_io, 4096, d_st, d_bits, stream=st.cuda_stream))
+    status, fields = d_st.cpu().numpy(), d_io.cpu().numpy()
+    bits = np.unpackbits(d_bits.cpu().numpy(), axis=1, bitorder="little").reshape(nj, 128, 128)
+    # the same seed lists as the host would upload them
+    rr = np.zeros(nj, navhip.REGION_REQ_DTYPE)
+    seeds = []
+    for j, (cr, cc, f) in enumerate(jobs):
+        br, bc = ((cr - 1) * 64 + 32 if cr else 0), ((cc - 1) * 64 + 32 if cc else 0)
+        sd = np.argwhere(bits[j]) + (br, bc)
+        rr[j] = (0, 1, 0, br, bc, 128, 128, 32 if cr else 0, 32 if cc else 0, sum(len(x) for x in seeds), len(sd), 0, 0)
+        seeds.append(sd.astype(np.int16))
+    seeds = np.concatenate(seeds)
+    d_rr, d_seeds = t(rr.view(np.uint8).reshape(nj, 32)), t(seeds)
+    d_io2 = torch.zeros((nj, 4096), dtype=torch.uint8, device=dev)
+    part = by_events(lambda: ctx.build_region_fields_dev(d_rr, nj, 128, d_seeds, None, d_io2, 4096, stream=st.cuda_stream))
+    assert np.array_equal(d_io2.cpu().numpy(), fields)
+    zeros = np.zeros((nj, 4096), np.uint8)
+    parent = timed(lambda: ctx.build_region_fields(rr, seeds, inout=zeros, out_stride=4096), reps=10) * 1e3
+    res = {"what": "256 distinct kind-0 jobs, layer 0, 1024x1024 map (configs[2]), 100 000 entities, 3 factions, radii 1 / 2.5 / 4",
+           "host_rows": int((status != 0).sum()), "seeds_per_job_mean": float(bits.reshape(nj, -1).sum(1).mean()),
+           "fields_not_trivial": int(fields.any(1).sum()),
+           "seek_fields_dev_events": total, "field_part_events": part,
+           "seed_part_ms_mean_by_difference": total["ms_mean"] - part["ms_mean"],
+           "parent_region_fields_host_api_ms": parent, "seed_upload_bytes": int(seeds.nbytes)}
+    ctx.close()
+    from oracle import pfref
+    if pfref.available():
+        nav = pfref.RefNav(synth.to_chunks(grid))
+        nav.game_load(pos, radius, faction, flags)
+        for f in range(16):
+            pfref.set_enemy_factions(f, int(masks[f]))
+        centre = synth.cell_centre(W, W, np.array([j[0] for j in jobs]) * 64 + 32, np.array([j[1] for j in jobs]) * 64 + 32)
+        batch = np.array([(pfref.ASYNC_ENEMY_SEEK, 0, f, c[0], c[1], 0, 0) for (cr, cc, f), c in zip(jobs, centre)],
+                         dtype=pfref.ASYNC_REQ_DTYPE)
+        assert nav.hip_init()
+        try:
+            def ref_batch(binding):
+                ms, got = [], None
+                for _ in range(4):
+                    nav.cache_clear()
+                    pfref.RefNav.hip_mode(binding, 1)
+                    t0 = time.perf_counter()
+                    got = nav.async_batch(batch)
+                    ms.append((time.perf_counter() - t0) * 1e3)
+                return min(ms[1:]), got
+            cpu_ms, ref = ref_batch(False)
+            bind_ms, _ = ref_batch(True)
+            same = sum(np.array_equal(ref[navhip.N_RegionFieldID(navhip.FFID_ENEMIES, 0, cr, cc, f)].reshape(4096), fields[j])
+                       for j, (cr, cc, f) in enumerate(jobs) if status[j] == 0)
+            res.update({"reference_async_batch_all_cpu_ms": cpu_ms, "reference_async_batch_binding_on_ms": bind_ms,
+                        "host_seed_extraction_ms_binding_less_parent_region_call": bind_ms - parent,
+                        "device_fields_equal_to_reference": int(same), "jobs_decided": int((status == 0).sum())})
+        finally:
+            pfref.RefNav.hip_mode(False)
+            pfref.RefNav.hip_shutdown()
+            pfref.RefNav.game_unload()
+            for f in range(16):
+                pfref.set_enemy_factions(f, 0)
+            nav.close()
+    return res
+
+
 def main():
     import torch
     torch.cuda.init()
     dev = torch.device("cuda", 0)
+    if "--seek-only" in sys.argv:
+        print(json.dumps({"seek_fields": seek_fields(torch, dev)}, indent=1))
+        return
     if "--region-repair-only" in sys.argv:
         print(json.dumps({"region_repair": region_repair(torch, dev)}, indent=1))
         return
@@ -245,6 +356,7 @@ def main():
     ctx.close()
     out["field_attacking"] = field_attacking(torch, dev)
     out["region_repair"] = region_repair(torch, dev)
+    out["seek_fields"] = seek_fields(torch, dev)
     print(json.dumps(out, indent=1))
 
 
