@@ -30,6 +30,7 @@
 #include "nav_flood.h"          // dq_map, dq_probe, dq_tile_for_point, dq_delta, dq_flood: N_ClosestPathable
 #include "arrival_region.h"     // af_key, af_zone_radius, af_region_area, sk_segment_within
 #include "pq_heap.h"
+#include "stage_plan.h"
 
 #define AB_CAP      NAVHIP_ARRIVAL_MAX_SLOTS
 #define AB_THREADS  256
@@ -378,34 +379,32 @@ __global__ __launch_bounds__(AB_THREADS) void k_arrival_build(nh_step_params P, 
 // ---------------------------------------------------------------------------------------------
 namespace {
 
+#define AB_FAIL(why) nh_fail(ctx, NAVHIP_ERR_ARG, name, why)     /* inside the check below: `name` is the form's */
 // The one argument check of both forms; host_arrays: the arrays can be read here, so what lies IN them is checked too.
 int ab_check(navhip_ctx *ctx, const navhip_world *w, const navhip_arrival_build_in *in, const navhip_arrival_build_out *out, bool host_arrays)
 {
     if(!ctx) return NAVHIP_ERR_ARG;
     const char *name = host_arrays ? "navhip_arrival_zone_build: " : "navhip_arrival_zone_build_dev: ";
-    auto fail = [&](const std::string &why) { ctx->last_error = name + why; return NAVHIP_ERR_ARG; };
-    if(!w || !in || !out) return fail("a missing argument");
-    if(in->nm < 0) return fail("nm < 0");
-    if(in->n_zones < 0 || in->n_slots < 0 || in->n_keys < 0 || w->n_ents < 0) return fail("a negative count");
+    if(!w || !in || !out) return AB_FAIL("a missing argument");
+    if(in->nm < 0) return AB_FAIL("nm < 0");
+    if(in->n_zones < 0 || in->n_slots < 0 || in->n_keys < 0 || w->n_ents < 0) return AB_FAIL("a negative count");
     if(in->n_zones == 0) return NAVHIP_OK;
-    if(!in->zones || !in->flocks || !in->target_xz) return fail("a missing array: zones, flocks or target_xz");
+    if(!in->zones || !in->flocks || !in->target_xz) return AB_FAIL("a missing array: zones, flocks or target_xz");
     if(!out->zones || !out->flocks || !out->status || !out->axis_xz || !out->com_xz || !out->com_dest_id)
-        return fail("a missing array: zones, flocks, status, axis_xz, com_xz or com_dest_id of navhip_arrival_build_out");
-    if(in->n_slots > 0 && (!in->slots_xz || !in->slot_ring || !out->slots_xz || !out->slot_ring)) return fail("a missing array: slots_xz or slot_ring");
-    if(in->n_keys > 0 && (!in->region_keys || !out->region_keys)) return fail("a missing array: region_keys");
+        return AB_FAIL("a missing array: zones, flocks, status, axis_xz, com_xz or com_dest_id of navhip_arrival_build_out");
+    if(in->n_slots > 0 && (!in->slots_xz || !in->slot_ring || !out->slots_xz || !out->slot_ring)) return AB_FAIL("a missing array: slots_xz or slot_ring");
+    if(in->n_keys > 0 && (!in->region_keys || !out->region_keys)) return AB_FAIL("a missing array: region_keys");
     if(in->nm > 0) {
-        if(!w->pos_xz) return fail("a missing array: world->pos_xz");
-        if(!in->uid || !in->settled || !in->substate || !in->sink_valid || !in->sink_xz) return fail("a missing array of the members");
-        if(!out->substate || !out->sink_valid || !out->sink_xz) return fail("a missing array of the members of navhip_arrival_build_out");
+        if(!w->pos_xz) return AB_FAIL("a missing array: world->pos_xz");
+        if(!in->uid || !in->settled || !in->substate || !in->sink_valid || !in->sink_xz) return AB_FAIL("a missing array of the members");
+        if(!out->substate || !out->sink_valid || !out->sink_xz) return AB_FAIL("a missing array of the members of navhip_arrival_build_out");
     }
     if(!host_arrays) return NAVHIP_OK;
     for(int z = 0; z < in->n_zones; z++) {
         const navhip_arrival_zone &Z = in->zones[z];
         const navhip_arrival_flock &S = in->flocks[z];
         const std::string zn = "zone " + std::to_string(z);
-        if(Z.slot_begin < 0 || Z.slot_end < Z.slot_begin || Z.slot_end > in->n_slots) return fail(zn + ": its slot range leaves slots_xz / slot_ring");
-        if(Z.key_begin < 0 || Z.key_end < Z.key_begin || Z.key_end > in->n_keys) return fail(zn + ": its key range leaves region_keys");
-        if(S.member_begin < 0 || S.member_end < S.member_begin || S.member_end > in->nm) return fail(zn + ": its member range leaves the member arrays");
+        if(const char *fault = nh_zone_fault(Z, &S, in->n_slots, in->n_keys, in->nm, nullptr)) return AB_FAIL(zn + fault);
         // room is asked of a zone the kernel would go on to build: one it answers NAVHIP_AB_HOST or NAVHIP_AB_WAIT in front
         // of its own room test (a layer without planes, a uid outside the world, nobody near the goal) needs none
         if(S.phase != NAVHIP_ARRIVAL_PHASE_INACTIVE || S.total_members < 4 || !(S.unit_radius > 0.0f && S.unit_radius < INFINITY)) continue;
@@ -421,12 +420,33 @@ int ab_check(navhip_ctx *ctx, const navhip_world *w, const navhip_arrival_build_
         const int area = af_region_area(af_zone_radius(S.total_members, S.unit_radius));
         const int slots = S.total_members < area ? S.total_members : area;
         if(Z.key_end - Z.key_begin < area || Z.slot_end - Z.slot_begin < slots)
-            return fail(zn + ": too little room: it needs " + std::to_string(area) + " keys and " + std::to_string(slots) + " slots");
+            return AB_FAIL(zn + ": too little room: it needs " + std::to_string(area) + " keys and " + std::to_string(slots) + " slots");
     }
     return NAVHIP_OK;
 }
 
-struct ab_copy { void *dst; const void *src; size_t bytes; };
+// the two structs of the host form, row by row (stage_plan.h)
+const nh_row ab_in_rows[] = {
+    NH_ROW(navhip_arrival_build_in, zones, sizeof(navhip_arrival_zone), NH_LEN_ZONE, NH_ON_ALWAYS),
+    NH_ROW(navhip_arrival_build_in, flocks, sizeof(navhip_arrival_flock), NH_LEN_ZONE, NH_ON_ALWAYS),
+    NH_ROW(navhip_arrival_build_in, target_xz, 8, NH_LEN_ZONE, NH_ON_ALWAYS),  NH_ROW(navhip_arrival_build_in, slots_xz, 8, NH_LEN_SLOT, NH_ON_ALWAYS),
+    NH_ROW(navhip_arrival_build_in, slot_ring, 4, NH_LEN_SLOT, NH_ON_ALWAYS),  NH_ROW(navhip_arrival_build_in, region_keys, 8, NH_LEN_KEY, NH_ON_ALWAYS),
+    NH_ROW(navhip_arrival_build_in, uid, 4, NH_LEN_MEMBER, NH_ON_ALWAYS),  NH_ROW(navhip_arrival_build_in, settled, 1, NH_LEN_MEMBER, NH_ON_ALWAYS),
+    NH_ROW(navhip_arrival_build_in, substate, 1, NH_LEN_MEMBER, NH_ON_ALWAYS),  NH_ROW(navhip_arrival_build_in, sink_valid, 1, NH_LEN_MEMBER, NH_ON_ALWAYS),
+    NH_ROW(navhip_arrival_build_in, sink_xz, 8, NH_LEN_MEMBER, NH_ON_ALWAYS),
+};
+// (axis, com and dest id of a row that is not built are not written: they go up, and back as they came)
+const nh_row ab_out_rows[] = {
+    NH_ROW_OUT_PAD(navhip_arrival_build_out, zones, sizeof(navhip_arrival_zone), NH_LEN_ZONE, NH_ON_ALWAYS, 16),
+    NH_ROW_OUT_PAD(navhip_arrival_build_out, flocks, sizeof(navhip_arrival_flock), NH_LEN_ZONE, NH_ON_ALWAYS, 16),
+    NH_ROW_OUT_PAD(navhip_arrival_build_out, slots_xz, 8, NH_LEN_SLOT, NH_ON_ALWAYS, 16),  NH_ROW_OUT_PAD(navhip_arrival_build_out, slot_ring, 4, NH_LEN_SLOT, NH_ON_ALWAYS, 16),
+    NH_ROW_OUT_PAD(navhip_arrival_build_out, region_keys, 8, NH_LEN_KEY, NH_ON_ALWAYS, 16),  NH_ROW_IO(navhip_arrival_build_out, axis_xz, 8, NH_LEN_ZONE, NH_ON_ALWAYS, 16),
+    NH_ROW_IO(navhip_arrival_build_out, com_xz, 8, NH_LEN_ZONE, NH_ON_ALWAYS, 16),  NH_ROW_IO(navhip_arrival_build_out, com_dest_id, 4, NH_LEN_ZONE, NH_ON_ALWAYS, 16),
+    NH_ROW_OUT_PAD(navhip_arrival_build_out, substate, 1, NH_LEN_MEMBER, NH_ON_ALWAYS, 16),  NH_ROW_OUT_PAD(navhip_arrival_build_out, sink_valid, 1, NH_LEN_MEMBER, NH_ON_ALWAYS, 16),
+    NH_ROW_OUT_PAD(navhip_arrival_build_out, sink_xz, 8, NH_LEN_MEMBER, NH_ON_ALWAYS, 16),  NH_ROW_OUT_PAD(navhip_arrival_build_out, status, 1, NH_LEN_ZONE, NH_ON_ALWAYS, 16),
+};
+NH_COVERS(ab_in_rows, navhip_arrival_build_in, 16);         // n_zones, nm, n_slots, n_keys
+NH_COVERS(ab_out_rows, navhip_arrival_build_out, 0);
 
 }   // namespace
 
@@ -442,10 +462,7 @@ int navhip_arrival_zone_build_dev(navhip_ctx *ctx, const navhip_world *w, const 
     rc = nh_refresh_derived(ctx, s);              // the probemask rows of uploads since the last build
     if(rc) return rc;
     nh_step_params P;
-    memset(&P, 0, sizeof(P));
-    nh_fill_map_view(ctx, &P.map);
-    P.map_x = w->map_pos_x; P.map_z = w->map_pos_z;
-    P.n_ents = w->n_ents; P.hz = w->hz;
+    nh_step_params_init(ctx, w, &P);
     P.pos_xz = w->pos_xz;
     const dq_map M = dq_map_of(ctx, w->map_pos_x, w->map_pos_z);
     hipLaunchKernelGGL(k_arrival_build, dim3(in->n_zones), dim3(AB_THREADS), 0, s, P, M, *in, *out);
@@ -471,62 +488,28 @@ int navhip_arrival_zone_build(navhip_ctx *ctx, const navhip_world *w, const navh
     if(rc || in->n_zones == 0) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const size_t nz = (size_t)in->n_zones, nm = (size_t)in->nm, ns = (size_t)in->n_slots, nkeys = (size_t)in->n_keys;
-    const size_t n_ents = (size_t)w->n_ents;
-    const size_t zb = sizeof(navhip_arrival_zone), fb = sizeof(navhip_arrival_flock);
-    // one arena: the inputs, then the outputs (a spare row behind every array, so that none is empty)
-    size_t total = 0;
-    auto row = [&](size_t bytes) { const size_t off = total; total += nh_up256(bytes + 16); return off; };
-    const size_t o_pos = row(n_ents * 8), o_zones = row(nz * zb), o_flocks = row(nz * fb), o_target = row(nz * 8),
-                 o_slots = row(ns * 8), o_ring = row(ns * 4), o_keys = row(nkeys * 8), o_uid = row(nm * 4), o_settled = row(nm),
-                 o_sub = row(nm), o_valid = row(nm), o_sink = row(nm * 8);
-    const size_t r_zones = row(nz * zb), r_flocks = row(nz * fb), r_slots = row(ns * 8), r_ring = row(ns * 4), r_keys = row(nkeys * 8),
-                 r_axis = row(nz * 8), r_com = row(nz * 8), r_dest = row(nz * 4), r_sub = row(nm), r_valid = row(nm), r_sink = row(nm * 8),
-                 r_status = row(nz);
-    char *base = nullptr;
-    rc = nh_stage_reserve(ctx, NH_STAGE_STATE_ARENA, total, (void**)&base);
-    if(rc) return rc;
-    const ab_copy up[] = {
-        {base + o_pos, nm ? w->pos_xz : nullptr, n_ents * 8}, {base + o_zones, in->zones, nz * zb}, {base + o_flocks, in->flocks, nz * fb},
-        {base + o_target, in->target_xz, nz * 8}, {base + o_slots, in->slots_xz, ns * 8}, {base + o_ring, in->slot_ring, ns * 4},
-        {base + o_keys, in->region_keys, nkeys * 8}, {base + o_uid, in->uid, nm * 4}, {base + o_settled, in->settled, nm},
-        {base + o_sub, in->substate, nm}, {base + o_valid, in->sink_valid, nm}, {base + o_sink, in->sink_xz, nm * 8},
-        // (axis, com and dest id of a row that is not built are not written: they go back as they came)
-        {base + r_axis, out->axis_xz, nz * 8}, {base + r_com, out->com_xz, nz * 8}, {base + r_dest, out->com_dest_id, nz * 4},
-    };
-    for(const ab_copy &c : up)
-        if(c.src && c.bytes) HIPCHK(ctx, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyHostToDevice, s));
+    nh_dims D;
+    D.len[NH_LEN_UNIT] = (size_t)w->n_ents; D.len[NH_LEN_ZONE] = (size_t)in->n_zones; D.len[NH_LEN_MEMBER] = (size_t)in->nm;
+    D.len[NH_LEN_SLOT] = (size_t)in->n_slots; D.len[NH_LEN_KEY] = (size_t)in->n_keys;
+    D.pad = 16;                                                             // (no input array of a slot-less or member-less call is empty; the result rows pad themselves)
+    nh_plan P;
     navhip_world d = *w;
-    d.pos_xz = (const float*)(base + o_pos);
     navhip_arrival_build_in di = *in;
-    di.zones = (const navhip_arrival_zone*)(base + o_zones); di.flocks = (const navhip_arrival_flock*)(base + o_flocks);
-    di.target_xz = (const float*)(base + o_target);
-    di.slots_xz = (const float*)(base + o_slots); di.slot_ring = (const int32_t*)(base + o_ring);
-    di.region_keys = (const uint64_t*)(base + o_keys); di.uid = (const int32_t*)(base + o_uid);
-    di.settled = (const uint8_t*)(base + o_settled); di.substate = (const uint8_t*)(base + o_sub);
-    di.sink_valid = (const uint8_t*)(base + o_valid); di.sink_xz = (const float*)(base + o_sink);
     navhip_arrival_build_out dout = {};
-    dout.zones = (navhip_arrival_zone*)(base + r_zones); dout.flocks = (navhip_arrival_flock*)(base + r_flocks);
-    dout.slots_xz = (float*)(base + r_slots); dout.slot_ring = (int32_t*)(base + r_ring); dout.region_keys = (uint64_t*)(base + r_keys);
-    dout.axis_xz = (float*)(base + r_axis); dout.com_xz = (float*)(base + r_com); dout.com_dest_id = (uint32_t*)(base + r_dest);
-    dout.substate = (uint8_t*)(base + r_sub); dout.sink_valid = (uint8_t*)(base + r_valid);
-    dout.sink_xz = (float*)(base + r_sink); dout.status = (uint8_t*)(base + r_status);
-    // (a built zone writes its new ranges only: what the rooms hold behind them goes back as it came)
-    if(ns) HIPCHK(ctx, hipMemcpyAsync(base + r_slots, base + o_slots, ns * 8, hipMemcpyDeviceToDevice, s));
-    if(ns) HIPCHK(ctx, hipMemcpyAsync(base + r_ring, base + o_ring, ns * 4, hipMemcpyDeviceToDevice, s));
-    if(nkeys) HIPCHK(ctx, hipMemcpyAsync(base + r_keys, base + o_keys, nkeys * 8, hipMemcpyDeviceToDevice, s));
-    rc = navhip_arrival_zone_build_dev(ctx, &d, &di, &dout, s);
+    P.in(in->nm ? w->pos_xz : nullptr, D.len[NH_LEN_UNIT] * 8, D.pad, (void**)&d.pos_xz);    // (no members: the positions do not travel)
+    nh_plan_rows(P, ab_in_rows, in, &di, D);
+    nh_plan_rows(P, ab_out_rows, out, &dout, D);
+    rc = P.reserve(ctx, NH_STAGE_CALL0);
+    if(!rc) rc = P.upload(ctx, s);
     if(rc) return rc;
-    const ab_copy down[] = {
-        {out->zones, base + r_zones, nz * zb}, {out->flocks, base + r_flocks, nz * fb}, {out->slots_xz, base + r_slots, ns * 8},
-        {out->slot_ring, base + r_ring, ns * 4}, {out->region_keys, base + r_keys, nkeys * 8}, {out->axis_xz, base + r_axis, nz * 8},
-        {out->com_xz, base + r_com, nz * 8}, {out->com_dest_id, base + r_dest, nz * 4}, {out->substate, base + r_sub, nm},
-        {out->sink_valid, base + r_valid, nm}, {out->sink_xz, base + r_sink, nm * 8}, {out->status, base + r_status, nz},
-    };
-    for(const ab_copy &c : down)
-        if(c.dst && c.bytes) HIPCHK(ctx, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return NAVHIP_OK;
+    // (a built zone writes its new ranges only: what the rooms hold behind them goes back as it came)
+    const size_t ns = D.len[NH_LEN_SLOT], nkeys = D.len[NH_LEN_KEY];
+    if(ns) HIPCHK(ctx, hipMemcpyAsync(dout.slots_xz, di.slots_xz, ns * 8, hipMemcpyDeviceToDevice, s));
+    if(ns) HIPCHK(ctx, hipMemcpyAsync(dout.slot_ring, di.slot_ring, ns * 4, hipMemcpyDeviceToDevice, s));
+    if(nkeys) HIPCHK(ctx, hipMemcpyAsync(dout.region_keys, di.region_keys, nkeys * 8, hipMemcpyDeviceToDevice, s));
+    rc = navhip_arrival_zone_build_dev(ctx, &d, &di, &dout, s);
+    if(!rc) rc = P.download(ctx, s);
+    return rc;
 }
 
 }   // extern "C"

@@ -19,6 +19,7 @@
 #include "agent_internal.h"
 #include "agent_math.h"
 #include "arrival_region.h"     // af_key, af_key_index, af_zone_radius
+#include "stage_plan.h"
 
 #define AF_CAP      4096        /* ARRIVAL_MAX_SLOTS, arrival.h:47: slots, keys and so rows of a zone           */
 #define AF_THREADS  256
@@ -365,40 +366,50 @@ void nh_launch_arrival_first_realloc(const nh_step_params &P, const navhip_arriv
 
 namespace {
 
+#define AF_FAIL(why) nh_fail(ctx, NAVHIP_ERR_ARG, name, why)     /* inside the check below: `name` is the form's */
 // The one argument check of both forms; host_arrays: the arrays can be read here, so what lies IN them is checked too.
 int af_check(navhip_ctx *ctx, const navhip_world *w, const navhip_arrival_flock_in *in, const navhip_arrival_flock_out *out, bool host_arrays)
 {
     if(!ctx) return NAVHIP_ERR_ARG;
     const char *name = host_arrays ? "navhip_arrival_flock_update: " : "navhip_arrival_flock_update_dev: ";
-    auto fail = [&](const std::string &why) { ctx->last_error = name + why; return NAVHIP_ERR_ARG; };
-    if(!w || !in || !out) return fail("a missing argument");
-    if(in->nm < 0) return fail("nm < 0");
-    if(in->n_zones < 0 || in->n_slots < 0 || in->n_keys < 0 || w->n_ents < 0) return fail("a negative count");
+    if(!w || !in || !out) return AF_FAIL("a missing argument");
+    if(in->nm < 0) return AF_FAIL("nm < 0");
+    if(in->n_zones < 0 || in->n_slots < 0 || in->n_keys < 0 || w->n_ents < 0) return AF_FAIL("a negative count");
     if(in->n_zones == 0) return NAVHIP_OK;
-    if(!in->zones || !in->flocks) return fail("a missing array: zones or flocks");
-    if(!out->zones || !out->flocks || !out->status) return fail("a missing array: zones, flocks or status of navhip_arrival_flock_out");
-    if(in->n_slots > 0 && (!in->slots_xz || !in->slot_ring || !out->slot_ring)) return fail("a missing array: slots_xz or slot_ring");
-    if(in->n_keys > 0 && !in->region_keys) return fail("a missing array: region_keys");
+    if(!in->zones || !in->flocks) return AF_FAIL("a missing array: zones or flocks");
+    if(!out->zones || !out->flocks || !out->status) return AF_FAIL("a missing array: zones, flocks or status of navhip_arrival_flock_out");
+    if(in->n_slots > 0 && (!in->slots_xz || !in->slot_ring || !out->slot_ring)) return AF_FAIL("a missing array: slots_xz or slot_ring");
+    if(in->n_keys > 0 && !in->region_keys) return AF_FAIL("a missing array: region_keys");
     if(in->nm > 0) {
-        if(!w->pos_xz) return fail("a missing array: world->pos_xz");
-        if(!in->uid || !in->settled || !in->substate || !in->sink_valid || !in->sink_xz) return fail("a missing array of the members");
-        if(!out->substate || !out->sink_valid || !out->sink_xz) return fail("a missing array of the members of navhip_arrival_flock_out");
+        if(!w->pos_xz) return AF_FAIL("a missing array: world->pos_xz");
+        if(!in->uid || !in->settled || !in->substate || !in->sink_valid || !in->sink_xz) return AF_FAIL("a missing array of the members");
+        if(!out->substate || !out->sink_valid || !out->sink_xz) return AF_FAIL("a missing array of the members of navhip_arrival_flock_out");
     }
     if(!host_arrays) return NAVHIP_OK;
-    for(int z = 0; z < in->n_zones; z++) {
-        const navhip_arrival_zone &Z = in->zones[z];
-        const navhip_arrival_flock &S = in->flocks[z];
-        const std::string zn = "zone " + std::to_string(z);
-        if(Z.slot_begin < 0 || Z.slot_end < Z.slot_begin || Z.slot_end > in->n_slots) return fail(zn + ": its slot range leaves slots_xz / slot_ring");
-        if(Z.key_begin < 0 || Z.key_end < Z.key_begin || Z.key_end > in->n_keys) return fail(zn + ": its key range leaves region_keys");
-        if(S.member_begin < 0 || S.member_end < S.member_begin || S.member_end > in->nm) return fail(zn + ": its member range leaves the member arrays");
-        for(int k = Z.key_begin + 1; k < Z.key_end; k++)
-            if(!(in->region_keys[k] > in->region_keys[k - 1])) return fail(zn + ": region_keys not ascending");
-    }
+    for(int z = 0; z < in->n_zones; z++)
+        if(const char *fault = nh_zone_fault(in->zones[z], &in->flocks[z], in->n_slots, in->n_keys, in->nm, in->region_keys))
+            return AF_FAIL("zone " + std::to_string(z) + fault);
     return NAVHIP_OK;
 }
 
-struct af_copy { void *dst; const void *src; size_t bytes; };
+// the two structs of the host form, row by row (stage_plan.h)
+const nh_row af_in_rows[] = {
+    NH_ROW(navhip_arrival_flock_in, zones, sizeof(navhip_arrival_zone), NH_LEN_ZONE, NH_ON_ALWAYS),
+    NH_ROW(navhip_arrival_flock_in, flocks, sizeof(navhip_arrival_flock), NH_LEN_ZONE, NH_ON_ALWAYS),
+    NH_ROW(navhip_arrival_flock_in, slots_xz, 8, NH_LEN_SLOT, NH_ON_ALWAYS),  NH_ROW(navhip_arrival_flock_in, slot_ring, 4, NH_LEN_SLOT, NH_ON_ALWAYS),
+    NH_ROW(navhip_arrival_flock_in, region_keys, 8, NH_LEN_KEY, NH_ON_ALWAYS),  NH_ROW(navhip_arrival_flock_in, uid, 4, NH_LEN_MEMBER, NH_ON_ALWAYS),
+    NH_ROW(navhip_arrival_flock_in, settled, 1, NH_LEN_MEMBER, NH_ON_ALWAYS),  NH_ROW(navhip_arrival_flock_in, substate, 1, NH_LEN_MEMBER, NH_ON_ALWAYS),
+    NH_ROW(navhip_arrival_flock_in, sink_valid, 1, NH_LEN_MEMBER, NH_ON_ALWAYS),  NH_ROW(navhip_arrival_flock_in, sink_xz, 8, NH_LEN_MEMBER, NH_ON_ALWAYS),
+};
+const nh_row af_out_rows[] = {
+    NH_ROW_OUT_PAD(navhip_arrival_flock_out, zones, sizeof(navhip_arrival_zone), NH_LEN_ZONE, NH_ON_ALWAYS, 16),
+    NH_ROW_OUT_PAD(navhip_arrival_flock_out, flocks, sizeof(navhip_arrival_flock), NH_LEN_ZONE, NH_ON_ALWAYS, 16),
+    NH_ROW_OUT_PAD(navhip_arrival_flock_out, slot_ring, 4, NH_LEN_SLOT, NH_ON_ALWAYS, 16),  NH_ROW_OUT_PAD(navhip_arrival_flock_out, substate, 1, NH_LEN_MEMBER, NH_ON_ALWAYS, 16),
+    NH_ROW_OUT_PAD(navhip_arrival_flock_out, sink_valid, 1, NH_LEN_MEMBER, NH_ON_ALWAYS, 16),  NH_ROW_OUT_PAD(navhip_arrival_flock_out, sink_xz, 8, NH_LEN_MEMBER, NH_ON_ALWAYS, 16),
+    NH_ROW_OUT_PAD(navhip_arrival_flock_out, status, 1, NH_LEN_ZONE, NH_ON_ALWAYS, 16),
+};
+NH_COVERS(af_in_rows, navhip_arrival_flock_in, 16);         // n_zones, nm, n_slots, n_keys
+NH_COVERS(af_out_rows, navhip_arrival_flock_out, 0);
 
 }   // namespace
 
@@ -411,10 +422,7 @@ int navhip_arrival_flock_update_dev(navhip_ctx *ctx, const navhip_world *w, cons
     if(rc || in->n_zones == 0) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     nh_step_params P;
-    memset(&P, 0, sizeof(P));
-    nh_fill_map_view(ctx, &P.map);
-    P.map_x = w->map_pos_x; P.map_z = w->map_pos_z;
-    P.n_ents = w->n_ents; P.hz = w->hz;
+    nh_step_params_init(ctx, w, &P);
     P.pos_xz = w->pos_xz;
     hipLaunchKernelGGL(k_arrival_flock, dim3(in->n_zones), dim3(AF_THREADS), 0, stream ? (hipStream_t)stream : ctx->stream, P, *in, *out,
                        (const uint8_t*)nullptr);
@@ -428,51 +436,22 @@ int navhip_arrival_flock_update(navhip_ctx *ctx, const navhip_world *w, const na
     if(rc || in->n_zones == 0) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const size_t nz = (size_t)in->n_zones, nm = (size_t)in->nm, ns = (size_t)in->n_slots, nkeys = (size_t)in->n_keys;
-    const size_t n_ents = (size_t)w->n_ents;
-    // one arena: the inputs, then the outputs (a spare row behind every array, so that none is empty)
-    size_t total = 0;
-    auto row = [&](size_t bytes) { const size_t off = total; total += nh_up256(bytes + 16); return off; };
-    const size_t o_pos = row(n_ents * 8), o_zones = row(nz * sizeof(navhip_arrival_zone)), o_flocks = row(nz * sizeof(navhip_arrival_flock)),
-                 o_slots = row(ns * 8), o_ring = row(ns * 4), o_keys = row(nkeys * 8), o_uid = row(nm * 4), o_settled = row(nm),
-                 o_sub = row(nm), o_valid = row(nm), o_sink = row(nm * 8);
-    const size_t r_zones = row(nz * sizeof(navhip_arrival_zone)), r_flocks = row(nz * sizeof(navhip_arrival_flock)), r_ring = row(ns * 4),
-                 r_sub = row(nm), r_valid = row(nm), r_sink = row(nm * 8), r_status = row(nz);
-    char *base = nullptr;
-    rc = nh_stage_reserve(ctx, NH_STAGE_STATE_ARENA, total, (void**)&base);
-    if(rc) return rc;
-    const af_copy up[] = {
-        {base + o_pos, nm ? w->pos_xz : nullptr, n_ents * 8}, {base + o_zones, in->zones, nz * sizeof(navhip_arrival_zone)},
-        {base + o_flocks, in->flocks, nz * sizeof(navhip_arrival_flock)}, {base + o_slots, in->slots_xz, ns * 8},
-        {base + o_ring, in->slot_ring, ns * 4}, {base + o_keys, in->region_keys, nkeys * 8}, {base + o_uid, in->uid, nm * 4},
-        {base + o_settled, in->settled, nm}, {base + o_sub, in->substate, nm}, {base + o_valid, in->sink_valid, nm},
-        {base + o_sink, in->sink_xz, nm * 8},
-    };
-    for(const af_copy &c : up)
-        if(c.src && c.bytes) HIPCHK(ctx, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyHostToDevice, s));
+    nh_dims D;
+    D.len[NH_LEN_UNIT] = (size_t)w->n_ents; D.len[NH_LEN_ZONE] = (size_t)in->n_zones; D.len[NH_LEN_MEMBER] = (size_t)in->nm;
+    D.len[NH_LEN_SLOT] = (size_t)in->n_slots; D.len[NH_LEN_KEY] = (size_t)in->n_keys;
+    D.pad = 16;                                                             // (no input array of a slot-less or member-less call is empty; the result rows pad themselves)
+    nh_plan P;
     navhip_world d = *w;
-    d.pos_xz = (const float*)(base + o_pos);
     navhip_arrival_flock_in di = *in;
-    di.zones = (const navhip_arrival_zone*)(base + o_zones); di.flocks = (const navhip_arrival_flock*)(base + o_flocks);
-    di.slots_xz = (const float*)(base + o_slots); di.slot_ring = (const int32_t*)(base + o_ring);
-    di.region_keys = (const uint64_t*)(base + o_keys); di.uid = (const int32_t*)(base + o_uid);
-    di.settled = (const uint8_t*)(base + o_settled); di.substate = (const uint8_t*)(base + o_sub);
-    di.sink_valid = (const uint8_t*)(base + o_valid); di.sink_xz = (const float*)(base + o_sink);
     navhip_arrival_flock_out dout = {};
-    dout.zones = (navhip_arrival_zone*)(base + r_zones); dout.flocks = (navhip_arrival_flock*)(base + r_flocks);
-    dout.slot_ring = (int32_t*)(base + r_ring); dout.substate = (uint8_t*)(base + r_sub); dout.sink_valid = (uint8_t*)(base + r_valid);
-    dout.sink_xz = (float*)(base + r_sink); dout.status = (uint8_t*)(base + r_status);
-    rc = navhip_arrival_flock_update_dev(ctx, &d, &di, &dout, s);
-    if(rc) return rc;
-    const af_copy down[] = {
-        {out->zones, base + r_zones, nz * sizeof(navhip_arrival_zone)}, {out->flocks, base + r_flocks, nz * sizeof(navhip_arrival_flock)},
-        {out->slot_ring, base + r_ring, ns * 4}, {out->substate, base + r_sub, nm}, {out->sink_valid, base + r_valid, nm},
-        {out->sink_xz, base + r_sink, nm * 8}, {out->status, base + r_status, nz},
-    };
-    for(const af_copy &c : down)
-        if(c.dst && c.bytes) HIPCHK(ctx, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return NAVHIP_OK;
+    P.in(in->nm ? w->pos_xz : nullptr, D.len[NH_LEN_UNIT] * 8, D.pad, (void**)&d.pos_xz);    // (no members: the positions do not travel)
+    nh_plan_rows(P, af_in_rows, in, &di, D);
+    nh_plan_rows(P, af_out_rows, out, &dout, D);
+    rc = P.reserve(ctx, NH_STAGE_CALL0);
+    if(!rc) rc = P.upload(ctx, s);
+    if(!rc) rc = navhip_arrival_flock_update_dev(ctx, &d, &di, &dout, s);
+    if(!rc) rc = P.download(ctx, s);
+    return rc;
 }
 
 }   // extern "C"

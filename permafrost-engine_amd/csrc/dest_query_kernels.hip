@@ -18,6 +18,7 @@
 // The window is the 127 x 127 tiles centred on the start (Chebyshev radius DQ_R): a flood that has to push an on-map tile
 // outside it in front of its answer ends with NAVHIP_DQ_HOST, never with a wrong answer.
 #include "navhip_internal.h"
+#include "stage_plan.h"
 #include "lane_group.h"
 #include "nav_flood.h"        // the floods themselves: dq_map, dq_candidate, dq_flood
 #include <cmath>
@@ -107,11 +108,7 @@ __global__ __launch_bounds__(64) void k_dest_query_pack(const int32_t *count, co
         if(o + k < tiles_cap) out_tiles[o + k] = tiles[(size_t)qi * DQ_MAX_TILES + k];
 }
 
-static int dq_fail(navhip_ctx *ctx, const std::string &why)
-{
-    ctx->last_error = "navhip_dest_queries: " + why;
-    return NAVHIP_ERR_ARG;
-}
+#define DQ_FAIL(why) nh_fail(ctx, NAVHIP_ERR_ARG, "navhip_dest_queries: ", why)
 
 extern "C" {
 
@@ -120,9 +117,9 @@ int navhip_dest_queries_dev(navhip_ctx *ctx, const navhip_dest_query *q, int n, 
                             uint8_t *out_status, void *stream)
 {
     if(!ctx) return NAVHIP_ERR_ARG;
-    if(n < 0 || tiles_cap < 0) return dq_fail(ctx, "a negative count");
+    if(n < 0 || tiles_cap < 0) return DQ_FAIL("a negative count");
     if(!out_tiles_off || (n > 0 && (!q || !out_nearest_xz || !out_status)) || (tiles_cap > 0 && !out_tiles))
-        return dq_fail(ctx, "a missing array");
+        return DQ_FAIL("a missing array");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     int rc = nh_refresh_derived(ctx, s);          // the row masks of uploads since the last build
@@ -146,41 +143,43 @@ int navhip_dest_queries(navhip_ctx *ctx, const navhip_dest_query *q, int n, floa
                         float *out_nearest_xz, int32_t *out_tiles_off, int16_t *out_tiles, int tiles_cap, uint8_t *out_status)
 {
     if(!ctx) return NAVHIP_ERR_ARG;
-    if(n < 0 || tiles_cap < 0) return dq_fail(ctx, "a negative count");
+    if(n < 0 || tiles_cap < 0) return DQ_FAIL("a negative count");
     if(!out_tiles_off || (n > 0 && (!q || !out_nearest_xz || !out_status)) || (tiles_cap > 0 && !out_tiles))
-        return dq_fail(ctx, "a missing array");
+        return DQ_FAIL("a missing array");
     // every record, before anything is launched
     for(int i = 0; i < n; i++) {
         const std::string row = "query " + std::to_string(i);
         const uint32_t known = NAVHIP_DQ_NEAREST | NAVHIP_DQ_TILES;
-        if(!(q[i].flags & known) || (q[i].flags & ~known)) return dq_fail(ctx, row + ": flags name no query or an unknown one");
-        if(q[i].layer < 0 || q[i].layer >= NAVHIP_NAV_LAYER_MAX) return dq_fail(ctx, row + ": no such layer");
+        if(!(q[i].flags & known) || (q[i].flags & ~known)) return DQ_FAIL(row + ": flags name no query or an unknown one");
+        if(q[i].layer < 0 || q[i].layer >= NAVHIP_NAV_LAYER_MAX) return DQ_FAIL(row + ": no such layer");
         const navhip_layer &L = ctx->layers[q[i].layer];
-        if(!L.cost || !L.blockers) return dq_fail(ctx, row + ": its layer has no resident cost / blockers planes");
-        if((q[i].flags & NAVHIP_DQ_TILES) && !L.islands) return dq_fail(ctx, row + ": its layer has no resident islands plane");
+        if(!L.cost || !L.blockers) return DQ_FAIL(row + ": its layer has no resident cost / blockers planes");
+        if((q[i].flags & NAVHIP_DQ_TILES) && !L.islands) return DQ_FAIL(row + ": its layer has no resident islands plane");
         int r, c;
         if(!dq_tile_for_point(ctx->w, ctx->h, map_pos_x, map_pos_z, q[i].x, q[i].z, &r, &c))
-            return dq_fail(ctx, row + ": the position is outside the map");
+            return DQ_FAIL(row + ": the position is outside the map");
     }
     if(n == 0) { out_tiles_off[0] = 0; return NAVHIP_OK; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     // the lists come back through a device array of the full size: the caller's cap is tested against the real total
+    // (the plan lays the arena out and uploads; the answers come down by hand, in the two steps below)
     const navhip_dest_query *d_q;
     float *d_nearest; int32_t *d_off; int16_t *d_tiles; uint8_t *d_status;
     const size_t full = (size_t)DQ_MAX_TILES * (size_t)n;
-    int rc = nh_stage_in(ctx, NH_STAGE_CALL0, q, sizeof(navhip_dest_query) * (size_t)n, (const void**)&d_q, s);
-    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_CALL1, 8 * (size_t)n, (void**)&d_nearest);
-    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_CALL2, 4 * ((size_t)n + 1), (void**)&d_off);
-    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_CALL3, 4 * full, (void**)&d_tiles);
-    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_CALL4, (size_t)n, (void**)&d_status);
+    nh_plan P;
+    P.in(q, sizeof(navhip_dest_query) * (size_t)n, 0, (void**)&d_q);
+    P.scratch(8 * (size_t)n, (void**)&d_nearest); P.scratch(4 * ((size_t)n + 1), (void**)&d_off);
+    P.scratch(4 * full, (void**)&d_tiles); P.scratch((size_t)n, (void**)&d_status);
+    int rc = P.reserve(ctx, NH_STAGE_CALL0);
+    if(!rc) rc = P.upload(ctx, s);
     if(!rc) rc = navhip_dest_queries_dev(ctx, d_q, n, map_pos_x, map_pos_z, d_nearest, d_off, d_tiles, (int)full, d_status, s);
     if(rc) return rc;
     std::vector<int32_t> off((size_t)n + 1);
     HIPCHK(ctx, hipMemcpyAsync(off.data(), d_off, 4 * ((size_t)n + 1), hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     if(off[n] > tiles_cap)
-        return dq_fail(ctx, "tiles_cap " + std::to_string(tiles_cap) + " is below the " + std::to_string(off[n]) + " tiles of the answer");
+        return DQ_FAIL("tiles_cap " + std::to_string(tiles_cap) + " is below the " + std::to_string(off[n]) + " tiles of the answer");
     HIPCHK(ctx, hipMemcpyAsync(out_nearest_xz, d_nearest, 8 * (size_t)n, hipMemcpyDeviceToHost, s));
     if(off[n] > 0) HIPCHK(ctx, hipMemcpyAsync(out_tiles, d_tiles, 4 * (size_t)off[n], hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipMemcpyAsync(out_status, d_status, (size_t)n, hipMemcpyDeviceToHost, s));

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <string>
 #include <vector>
+#include <mutex>
 #include <initializer_list>
 #include <stddef.h>
 #include "navhip.h"
@@ -45,12 +46,14 @@ enum nh_stage_slot {
     NH_STAGE_OUT_VEL, NH_STAGE_OUT_NEW_POS, NH_STAGE_OUT_VDES, NH_STAGE_OUT_VPREF, NH_STAGE_OUT_STATUS,
     // navhip_agent_step_submit: the device slabs of its pageable inputs and outputs
     NH_STAGE_SUBMIT_IN, NH_STAGE_SUBMIT_OUT,
-    // state_kernels.hip: the arena its host-buffer entry points carve up; the two slabs of the resident state pass
+    // state_kernels.hip: the arena its host-buffer entry points carve up (nh_plan); the two slabs of the resident state pass
     NH_STAGE_STATE_ARENA, NH_STAGE_PASS_IN, NH_STAGE_PASS_OUT,
     // navhip_build_los_dev: the per-request overlay (the launch may still run when the call returns)
     NH_STAGE_LOS_OVERLAY,
-    // call-local scratch of the host-pointer utilities that synchronise before they return and leave nothing behind:
-    // the ClearPath batches, navhip_region_lookup, navhip_spatial_query, navhip_build_los, navhip_build_fields,
+    // call-local scratch of the host-pointer utilities that synchronise before they return and leave nothing behind.
+    // NH_STAGE_CALL0 is also the ONE arena (nh_plan, stage_plan.h) of the host forms of the arrival flock update and zone
+    // build, the dest, order and surround queries, the region repair and the seek fields; slot by slot: the ClearPath
+    // batches, navhip_region_lookup, navhip_spatial_query, navhip_build_los, navhip_build_fields,
     // navhip_build_region_fields, navhip_blockers_circles
     NH_STAGE_CALL0, NH_STAGE_CALL1, NH_STAGE_CALL2, NH_STAGE_CALL3, NH_STAGE_CALL4, NH_STAGE_CALL5, NH_STAGE_CALL6,
     NH_STAGE_COUNT
@@ -280,6 +283,40 @@ struct navhip_ctx {
     struct nh_async *async = nullptr;    // state of navhip_agent_step_submit / _poll (submit_api.hip) or NULL
     struct nh_comm  *comm = nullptr;     // RCCL communicator of navhip_comm_* (comm_api.hip) or NULL
 };
+
+// a refused call: the reason to last_error under the call's name ("navhip_xxx: "), the call's code back
+static inline int nh_fail(navhip_ctx *ctx, int code, const char *call, const std::string &why)
+{
+    ctx->last_error = call + why;
+    return code;
+}
+
+// What the host forms check of a zone's ranges in the shared arrays (S: its companion, or NULL where the call has no
+// members; region_keys: NULL where the keys are room to be filled, in no order yet): NULL, or what is wrong with it, to
+// follow "zone <z>" in last_error.
+static inline const char *nh_zone_fault(const navhip_arrival_zone &Z, const navhip_arrival_flock *S, int n_slots, int n_keys, int nm,
+                                        const uint64_t *region_keys)
+{
+    if(Z.slot_begin < 0 || Z.slot_end < Z.slot_begin || Z.slot_end > n_slots) return ": its slot range leaves slots_xz / slot_ring";
+    if(Z.key_begin < 0 || Z.key_end < Z.key_begin || Z.key_end > n_keys) return ": its key range leaves region_keys";
+    if(S && (S->member_begin < 0 || S->member_end < S->member_begin || S->member_end > nm)) return ": its member range leaves the member arrays";
+    for(int k = Z.key_begin + 1; region_keys && k < Z.key_end; k++)
+        if(!(region_keys[k] > region_keys[k - 1])) return ": region_keys not ascending";
+    return nullptr;
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize of a kernel, once per device (not per process: every context's device
+// needs it); the flag is set only behind a call that succeeded.  `once`: a static of the kernel's launcher.
+struct nh_lds_once { std::mutex mu; bool set[64] = {}; };
+static inline hipError_t nh_allow_dynamic_lds(nh_lds_once &once, int device, const void *kernel, int bytes)
+{
+    std::lock_guard<std::mutex> lock(once.mu);
+    const int devi = device >= 0 && device < 64 ? device : 0;
+    if(once.set[devi]) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    once.set[devi] = e == hipSuccess;
+    return e;
+}
 
 // the resident planes of every layer, as the kernels take them
 static inline void nh_fill_map_view(const navhip_ctx *ctx, nh_map_view *mv)

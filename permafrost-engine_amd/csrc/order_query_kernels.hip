@@ -24,6 +24,7 @@
 //              as include/navhip.h states it for every flood (a search that has to visit a tile outside it).
 //   dest id    n_dest_id of the tile of the answer.
 #include "navhip_internal.h"
+#include "stage_plan.h"
 #include "lane_group.h"
 #include "nav_flood.h"        // dq_map, dq_tile_for_point, dq_island, dq_flood_first
 #include "circle_tiles.h"     // circle_hits_tile, len2f
@@ -153,11 +154,7 @@ __global__ __launch_bounds__(64) void k_order_query(dq_map M, uint32_t island_la
     }
 }
 
-static int oq_fail(navhip_ctx *ctx, const std::string &why)
-{
-    ctx->last_error = "navhip_order_queries: " + why;
-    return NAVHIP_ERR_ARG;
-}
+#define OQ_FAIL(why) nh_fail(ctx, NAVHIP_ERR_ARG, "navhip_order_queries: ", why)
 
 static uint32_t oq_island_layers(const navhip_ctx *ctx)
 {
@@ -172,8 +169,8 @@ int navhip_order_queries_dev(navhip_ctx *ctx, const navhip_order_query *q, int n
                              float *out_dest_xz, uint32_t *out_dest_id, uint8_t *out_status, void *stream)
 {
     if(!ctx) return NAVHIP_ERR_ARG;
-    if(n < 0) return oq_fail(ctx, "a negative count");
-    if(n > 0 && (!q || !out_dest_xz || !out_dest_id || !out_status)) return oq_fail(ctx, "a missing array");
+    if(n < 0) return OQ_FAIL("a negative count");
+    if(n > 0 && (!q || !out_dest_xz || !out_dest_id || !out_status)) return OQ_FAIL("a missing array");
     if(n == 0) return NAVHIP_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
@@ -188,8 +185,8 @@ int navhip_order_queries(navhip_ctx *ctx, const navhip_order_query *q, int n, fl
                          float *out_dest_xz, uint32_t *out_dest_id, uint8_t *out_status)
 {
     if(!ctx) return NAVHIP_ERR_ARG;
-    if(n < 0) return oq_fail(ctx, "a negative count");
-    if(n > 0 && (!q || !out_dest_xz || !out_dest_id || !out_status)) return oq_fail(ctx, "a missing array");
+    if(n < 0) return OQ_FAIL("a negative count");
+    if(n > 0 && (!q || !out_dest_xz || !out_dest_id || !out_status)) return OQ_FAIL("a missing array");
     // every row, before anything is launched
     static const char *const why[] = {"", "flags name an unknown query", "no such layer", "its layer has no resident islands plane",
                                       "no such faction (0..14, or 15 for none)", "a NaN coordinate or range",
@@ -198,24 +195,24 @@ int navhip_order_queries(navhip_ctx *ctx, const navhip_order_query *q, int n, fl
     const uint32_t island_layers = oq_island_layers(ctx);
     for(int i = 0; i < n; i++) {
         const int bad = oq_row_refusal(ctx->w, ctx->h, map_pos_x, map_pos_z, island_layers, q[i]);
-        if(bad != OQ_ROW_OK) return oq_fail(ctx, "query " + std::to_string(i) + ": " + why[bad]);
+        if(bad != OQ_ROW_OK) return OQ_FAIL("query " + std::to_string(i) + ": " + why[bad]);
     }
     if(n == 0) return NAVHIP_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const navhip_order_query *d_q;
     float *d_dest; uint32_t *d_id; uint8_t *d_status;
-    int rc = nh_stage_in(ctx, NH_STAGE_CALL0, q, sizeof(navhip_order_query) * (size_t)n, (const void**)&d_q, s);
-    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_CALL1, 8 * (size_t)n, (void**)&d_dest);
-    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_CALL2, 4 * (size_t)n, (void**)&d_id);
-    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_CALL3, (size_t)n, (void**)&d_status);
+    const size_t rows = (size_t)n;
+    nh_plan P;
+    P.in(q, sizeof(navhip_order_query) * rows, 0, (void**)&d_q);
+    P.out(P.scratch(8 * rows, (void**)&d_dest), out_dest_xz, 8, 0, rows);
+    P.out(P.scratch(4 * rows, (void**)&d_id), out_dest_id, 4, 0, rows);
+    P.out(P.scratch(rows, (void**)&d_status), out_status, 1, 0, rows);
+    int rc = P.reserve(ctx, NH_STAGE_CALL0);
+    if(!rc) rc = P.upload(ctx, s);
     if(!rc) rc = navhip_order_queries_dev(ctx, d_q, n, map_pos_x, map_pos_z, d_dest, d_id, d_status, s);
-    if(rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(out_dest_xz, d_dest, 8 * (size_t)n, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(out_dest_id, d_id, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(out_status, d_status, (size_t)n, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return NAVHIP_OK;
+    if(!rc) rc = P.download(ctx, s);
+    return rc;
 }
 
 }   // extern "C"

@@ -114,14 +114,8 @@ void nh_launch_region_fields(navhip_ctx *ctx, const navhip_region_req *d_reqs, i
     nh_map_view mv;
     nh_fill_map_view(ctx, &mv);
     const size_t lds = (size_t)max_dim * max_dim * 5;
-    // (per device, not per process: every context's device needs the attribute)
-    static bool attr_set[64] = {false};
-    const int devi = ctx->device >= 0 && ctx->device < 64 ? ctx->device : 0;
-    if(!attr_set[devi]) {
-        hipFuncSetAttribute((const void*)k_region_field, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            128 * 128 * 5);
-        attr_set[devi] = true;
-    }
+    static nh_lds_once lds_allowed;                 // (a failure is not looked at here: the launch then fails)
+    nh_allow_dynamic_lds(lds_allowed, ctx->device, (const void*)k_region_field, 128 * 128 * 5);
     if(n > 0)
         hipLaunchKernelGGL(k_region_field, dim3(n), dim3(256), lds, s, mv, d_reqs, n, d_seeds,
                            d_overlay, d_out, out_stride);

@@ -25,8 +25,8 @@
 // anything, so the serial arm's ring (16-bit entries, at most max(R, C)^2 <= dim^2 of them: every push sets a fresh flag)
 // and visited flags live in it.
 #include "navhip_internal.h"
+#include "stage_plan.h"
 #include "field_cells.h"
-#include <mutex>
 
 static_assert(sizeof(navhip_region_repair_req) == 20, "navhip_region_repair_req must stay 20 bytes");
 
@@ -205,29 +205,15 @@ static int nh_launch_region_repair(navhip_ctx *ctx, const navhip_region_repair_r
     nh_map_view mv;
     nh_fill_map_view(ctx, &mv);
     const size_t lds = (size_t)max_dim * max_dim * 6;
-    // (per device; the flag is set only behind a call that succeeded, and a failure is the call's error)
-    {
-        static std::mutex mu;
-        static bool attr_set[64] = {false};
-        std::lock_guard<std::mutex> lock(mu);
-        const int devi = ctx->device >= 0 && ctx->device < 64 ? ctx->device : 0;
-        if(!attr_set[devi]) {
-            HIPCHK(ctx, hipFuncSetAttribute((const void*)k_region_repair, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            RR_MAX_DIM * RR_MAX_DIM * 6));
-            attr_set[devi] = true;
-        }
-    }
+    static nh_lds_once lds_allowed;                 // (a failure is the call's error)
+    HIPCHK(ctx, nh_allow_dynamic_lds(lds_allowed, ctx->device, (const void*)k_region_repair, RR_MAX_DIM * RR_MAX_DIM * 6));
     hipLaunchKernelGGL(k_region_repair, dim3(n), dim3(256), lds, s, mv, d_reqs, n, max_dim, d_overlay, d_inout, stride,
                        d_status);
     HIPCHK(ctx, hipGetLastError());
     return NAVHIP_OK;
 }
 
-static int rr_fail(navhip_ctx *ctx, const std::string &why)
-{
-    ctx->last_error = "navhip_repair_region_fields: " + why;
-    return NAVHIP_ERR_INVALID;
-}
+#define RR_FAIL(why) nh_fail(ctx, NAVHIP_ERR_INVALID, "navhip_repair_region_fields: ", why)
 
 extern "C" {
 
@@ -236,9 +222,9 @@ int navhip_repair_region_fields_dev(navhip_ctx *ctx, const navhip_region_repair_
                                     void *stream)
 {
     if(!ctx) return NAVHIP_ERR_INVALID;
-    if(n < 0) return rr_fail(ctx, "a negative count");
-    if(n > 0 && (!dev_reqs || !dev_inout || !dev_status)) return rr_fail(ctx, "a missing array");
-    if(max_dim < 2 || max_dim > RR_MAX_DIM || (max_dim % 2) != 0) return rr_fail(ctx, "max_dim is odd or outside 2..128");
+    if(n < 0) return RR_FAIL("a negative count");
+    if(n > 0 && (!dev_reqs || !dev_inout || !dev_status)) return RR_FAIL("a missing array");
+    if(max_dim < 2 || max_dim > RR_MAX_DIM || (max_dim % 2) != 0) return RR_FAIL("max_dim is odd or outside 2..128");
     if(n == 0) return NAVHIP_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
@@ -250,14 +236,14 @@ int navhip_repair_region_fields(navhip_ctx *ctx, const navhip_region_repair_req 
                                 uint8_t *out_status)
 {
     if(!ctx) return NAVHIP_ERR_INVALID;
-    if(n < 0) return rr_fail(ctx, "a negative count");
-    if(n > 0 && (!reqs || !inout || !out_status)) return rr_fail(ctx, "a missing array");
+    if(n < 0) return RR_FAIL("a negative count");
+    if(n > 0 && (!reqs || !inout || !out_status)) return RR_FAIL("a missing array");
     // every row, before anything is launched
     int max_dim = 2;
     for(int i = 0; i < n; i++) {
         const navhip_region_repair_req &r = reqs[i];
         if(!rr_row_ok(r, stride, overlay != nullptr) || (size_t)r.overlay_begin + r.overlay_count > n_overlay)
-            return rr_fail(ctx, "malformed request " + std::to_string(i) + " (dim odd, 0 or above 128; no such layer; a stride"
+            return RR_FAIL("malformed request " + std::to_string(i) + " (dim odd, 0 or above 128; no such layer; a stride"
                                 " below dim * dim / 2; an overlay range outside the array)");
         max_dim = r.dim > max_dim ? r.dim : max_dim;
     }
@@ -265,18 +251,18 @@ int navhip_repair_region_fields(navhip_ctx *ctx, const navhip_region_repair_req 
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const size_t bytes = (size_t)n * stride;
-    const navhip_region_repair_req *d_reqs; const int16_t *d_overlay;
+    const navhip_region_repair_req *d_reqs; const int16_t *d_overlay = nullptr;
     uint8_t *d_inout, *d_status;
-    int rc = nh_stage_in(ctx, NH_STAGE_CALL0, reqs, (size_t)n * sizeof(navhip_region_repair_req), (const void**)&d_reqs, s);
-    if(!rc) rc = nh_stage_in(ctx, NH_STAGE_CALL1, overlay, n_overlay * 4, (const void**)&d_overlay, s);
-    if(!rc) rc = nh_stage_in(ctx, NH_STAGE_CALL2, inout, bytes, (const void**)&d_inout, s);      // the slots travel with what they hold
-    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_CALL3, (size_t)n, (void**)&d_status);
+    nh_plan P;
+    P.in(reqs, (size_t)n * sizeof(navhip_region_repair_req), 0, (void**)&d_reqs);
+    if(overlay) P.in(overlay, n_overlay * 4, 16, (void**)&d_overlay);
+    P.out(P.in(inout, bytes, 0, (void**)&d_inout), inout, 1, 0, bytes);       // the slots travel with what they hold
+    P.out(P.scratch((size_t)n, (void**)&d_status), out_status, 1, 0, (size_t)n);
+    int rc = P.reserve(ctx, NH_STAGE_CALL0);
+    if(!rc) rc = P.upload(ctx, s);
     if(!rc) rc = navhip_repair_region_fields_dev(ctx, d_reqs, n, max_dim, d_overlay, d_inout, stride, d_status, s);
-    if(rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(inout, d_inout, bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(out_status, d_status, (size_t)n, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return NAVHIP_OK;
+    if(!rc) rc = P.download(ctx, s);
+    return rc;
 }
 
 }   // extern "C"

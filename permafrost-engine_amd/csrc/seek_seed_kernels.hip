@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "navhip_internal.h"
+#include "stage_plan.h"
 #include "agent_types.h"
 #include "agent_math.h"         // bg_scale
 #include "wave_bits.h"
@@ -262,23 +263,19 @@ __global__ __launch_bounds__(256) void k_seek_seeds(sk_params P, const navhip_se
     }
 }
 
-static int sk_fail(navhip_ctx *ctx, const std::string &why)
-{
-    ctx->last_error = "navhip_build_seek_fields: " + why;
-    return NAVHIP_ERR_INVALID;
-}
+#define SK_FAIL(why) nh_fail(ctx, NAVHIP_ERR_INVALID, "navhip_build_seek_fields: ", why)
 
 // the checks both forms make before anything is launched
 static int sk_check(navhip_ctx *ctx, const navhip_world *w, const navhip_seek_game *g, const void *reqs, int n,
                     const void *inout, size_t stride, const void *status)
 {
-    if(n < 0) return sk_fail(ctx, "a negative count");
-    if(!w || !g) return sk_fail(ctx, "a missing array (world or game)");
-    if(w->n_ents < 0) return sk_fail(ctx, "a negative n_ents");
-    if(stride < NH_CELLS) return sk_fail(ctx, "a stride below 4096");
-    if(n > 0 && (!reqs || !inout || !status)) return sk_fail(ctx, "a missing array (reqs, inout or out_status)");
+    if(n < 0) return SK_FAIL("a negative count");
+    if(!w || !g) return SK_FAIL("a missing array (world or game)");
+    if(w->n_ents < 0) return SK_FAIL("a negative n_ents");
+    if(stride < NH_CELLS) return SK_FAIL("a stride below 4096");
+    if(n > 0 && (!reqs || !inout || !status)) return SK_FAIL("a missing array (reqs, inout or out_status)");
     if(w->n_ents > 0 && (!w->pos_xz || !w->radius || !w->flags || !g->faction))
-        return sk_fail(ctx, "a missing array (pos_xz, radius, flags or faction)");
+        return SK_FAIL("a missing array (pos_xz, radius, flags or faction)");
     return NAVHIP_OK;
 }
 
@@ -300,7 +297,7 @@ int navhip_build_seek_fields_dev(navhip_ctx *ctx, const navhip_world *w, const n
     // bg_ent_init, bitmap_grid.h:968-990
     P.origin_x = (int32_t)lrintf(w->grid_xmin * 256.0f); P.origin_y = (int32_t)lrintf(w->grid_zmin * 256.0f);
     const int32_t span_x = (int32_t)lrintf(w->grid_xmax * 256.0f) - P.origin_x, span_y = (int32_t)lrintf(w->grid_zmax * 256.0f) - P.origin_y;
-    if(span_x < 0 || span_y < 0) return sk_fail(ctx, "grid bounds with max below min");
+    if(span_x < 0 || span_y < 0) return SK_FAIL("grid bounds with max below min");
     P.grid_w = (int)(((uint32_t)span_x + 4095u) >> 12); P.grid_h = (int)(((uint32_t)span_y + 4095u) >> 12);
     if(P.grid_w < 1) P.grid_w = 1;
     if(P.grid_h < 1) P.grid_h = 1;
@@ -331,7 +328,7 @@ int navhip_build_seek_fields(navhip_ctx *ctx, const navhip_world *w, const navhi
     if(rc) return rc;
     for(int i = 0; i < n; i++)
         if(reqs[i].kind > NAVHIP_SEEK_ENTITY || reqs[i].layer >= NAVHIP_NAV_LAYER_MAX)
-            return sk_fail(ctx, "malformed request " + std::to_string(i) + " (a kind above 1 or no such layer)");
+            return SK_FAIL("malformed request " + std::to_string(i) + " (a kind above 1 or no such layer)");
     if(n == 0) return NAVHIP_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
@@ -340,22 +337,22 @@ int navhip_build_seek_fields(navhip_ctx *ctx, const navhip_world *w, const navhi
     navhip_seek_game dg = *g;
     const navhip_seek_req *d_reqs;
     uint8_t *d_inout, *d_status, *d_bits = nullptr;
+    // the three arrays of the snapshot in the world's own slots (which drops a resident snapshot), the rest in one arena
     rc = nh_stage_world(ctx, w, &d, s, {offsetof(navhip_world, pos_xz), offsetof(navhip_world, radius), offsetof(navhip_world, flags)});
-    if(!rc) rc = nh_stage_in(ctx, NH_STAGE_CALL0, reqs, (size_t)n * sizeof(navhip_seek_req), (const void**)&d_reqs, s);
-    if(!rc) rc = nh_stage_in(ctx, NH_STAGE_CALL1, g->faction, ne * 4, (const void**)&dg.faction, s);
-    if(!rc) rc = nh_stage_in(ctx, NH_STAGE_CALL2, g->exclude, g->exclude ? ne : 0, (const void**)&dg.exclude, s);
-    if(!rc) rc = nh_stage_in(ctx, NH_STAGE_CALL3, inout, bytes, (const void**)&d_inout, s);       // the slots travel with what they hold
-    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_CALL4, (size_t)n, (void**)&d_status);
-    // (rows that come back NAVHIP_SK_HOST keep what the caller's seed rows hold: they travel too)
-    if(!rc && out_seed_bits) rc = nh_stage_in(ctx, NH_STAGE_CALL5, out_seed_bits, sb_bytes, (const void**)&d_bits, s);
-    if(!g->exclude) dg.exclude = nullptr;
-    if(!rc) rc = navhip_build_seek_fields_dev(ctx, &d, &dg, d_reqs, n, d_inout, stride, d_status, d_bits, s);
     if(rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(inout, d_inout, bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(out_status, d_status, (size_t)n, hipMemcpyDeviceToHost, s));
-    if(out_seed_bits) HIPCHK(ctx, hipMemcpyAsync(out_seed_bits, d_bits, sb_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return NAVHIP_OK;
+    nh_plan P;
+    P.in(reqs, (size_t)n * sizeof(navhip_seek_req), 0, (void**)&d_reqs);
+    if(g->faction) P.in(g->faction, ne * 4, 16, (void**)&dg.faction);
+    if(g->exclude) P.in(g->exclude, ne, 16, (void**)&dg.exclude);
+    P.out(P.in(inout, bytes, 0, (void**)&d_inout), inout, 1, 0, bytes);       // the slots travel with what they hold
+    P.out(P.scratch((size_t)n, (void**)&d_status), out_status, 1, 0, (size_t)n);
+    // (rows that come back NAVHIP_SK_HOST keep what the caller's seed rows hold: they travel too)
+    if(out_seed_bits) P.out(P.in(out_seed_bits, sb_bytes, 0, (void**)&d_bits), out_seed_bits, 1, 0, sb_bytes);
+    rc = P.reserve(ctx, NH_STAGE_CALL0);
+    if(!rc) rc = P.upload(ctx, s);
+    if(!rc) rc = navhip_build_seek_fields_dev(ctx, &d, &dg, d_reqs, n, d_inout, stride, d_status, d_bits, s);
+    if(!rc) rc = P.download(ctx, s);
+    return rc;
 }
 
 }   // extern "C"

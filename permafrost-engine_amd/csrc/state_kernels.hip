@@ -20,6 +20,7 @@
 #include "agent_math.h"
 #include "lane_group.h"
 #include "arrival_region.h"
+#include "stage_plan.h"
 
 #define SK_QUERY_R   30.0f       /* SEPARATION_NEIGHB_RADIUS, movement.c:428                            */
 #define SK_QUERY_MAX 128         /* near_ents[128], movement.c:997                                      */
@@ -712,247 +713,92 @@ __global__ __launch_bounds__(256) void k_arrival_velocity(nh_step_params P, int 
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-// One staging slot, planned before it is reserved: input rows (a host source), scratch rows, and the rows of a scratch
-// row that go back to the host.  Rows are 256-byte aligned; reserve() gives every row its device address and writes it
-// to the member of the device-side struct the row was staged for (`twin`).  How the rows cross the bus is a policy:
-//   per row   (default)  one copy per row: the gate, the aux pass, the state pass, the settled count
-//   region()             rows that lie side by side travel as ONE region, mirrored in the page-locked slabs: the settle calls
-//   pack()               page-locked arrays travel in place, pageable ones as ONE block behind the rows: the resident pass
-struct sk_plan {
-    struct row { size_t off, bytes; const void *src; void **twin; char *dev; bool direct; size_t h_off; };
-    struct ret { int row; void *dst; size_t elem, lo, cnt, h_off; bool direct; };   // rows [lo, lo + cnt) of `row` -> dst
-    std::vector<row> rows;
-    std::vector<ret> rets;
-    size_t total = 0;
-    size_t in_blk = 0, in_bytes = 0, out_blk = 0, out_bytes = 0;    // the block of each direction: offset in the slot, bytes
-    bool gather = false;                                            // pack(): the blocks lie behind the rows
-    char *base = nullptr, *h_in = nullptr, *h_out = nullptr;
+// the lengths and groups of this unit's structs beside the shared ones (stage_plan.h)
+enum { SK_PER_TILE = NH_LEN_OWN, SK_PER_RANGE_ROW_PLUS1, SK_PER_RANGE_TILE,
+       SK_PER_ARM_ROW,          // a row per unit -- with sparse rows, per LISTED unit
+       SK_PER_LISTED, SK_LEN_END };
+enum { SK_SKIP = NH_ON_OWN, SK_TURN, SK_RANGE, SK_SURROUND, SK_INTERP, SK_SPARSE, SK_AUX, SK_ON_END };
+static_assert(SK_LEN_END <= NH_LEN_COUNT && SK_ON_END <= NH_ON_COUNT, "nh_dims has no room for this unit's own lengths and groups");
 
-    static size_t up(size_t bytes) { return nh_up256(bytes); }
-    // pad: tail bytes of a row whose array may be empty, so that a kernel is never handed the next row's address as its own
-    int in(const void *src, size_t bytes, size_t pad = 0, void **twin = nullptr)
-    {
-        rows.push_back({total, src ? bytes : 0, src, twin, nullptr, true, 0});
-        total += up(bytes + pad);
-        return (int)rows.size() - 1;
-    }
-    int scratch(size_t bytes, void **twin = nullptr) { return in(nullptr, bytes, 0, twin); }
-    void out(int row, void *dst, size_t elem, size_t lo, size_t cnt) { if(dst && cnt) rets.push_back({row, dst, elem, lo, cnt, 0, true}); }
-    template<class T> T *dev(int r) const { return (T*)rows[r].dev; }
+// the structs of the state pass and of the settle calls: one list each (stage_plan.h)
+const nh_row sk_gate_rows[] = {
+    NH_ROW(navhip_gate_in, next_rot, 16, NH_LEN_UNIT, NH_ON_ALWAYS),  NH_ROW(navhip_gate_in, new_vel_xz, 8, NH_LEN_UNIT, NH_ON_ALWAYS),
+    NH_ROW(navhip_gate_in, vdes_xz, 8, NH_LEN_UNIT, NH_ON_ALWAYS),  NH_ROW(navhip_gate_in, interp_from_xz, 8, NH_LEN_UNIT, SK_INTERP),
+    NH_ROW(navhip_gate_in, interp_step, 4, NH_LEN_UNIT, SK_INTERP),
+};
+const nh_row sk_state_rows[] = {
+    NH_ROW(navhip_state_in, new_pos_xz, 8, NH_LEN_UNIT, NH_ON_ALWAYS),  NH_ROW(navhip_state_in, vdes_xz, 8, NH_LEN_UNIT, NH_ON_ALWAYS),
+    NH_ROW(navhip_state_in, skip, 1, NH_LEN_UNIT, SK_SKIP),  NH_ROW(navhip_state_in, flock_layer, 1, NH_LEN_FLOCK, NH_ON_ALWAYS),
+    NH_ROW(navhip_state_in, flock_nearest_xz, 8, NH_LEN_FLOCK, NH_ON_ALWAYS),
+    NH_ROW(navhip_state_in, flock_tiles_off, 4, NH_LEN_FLOCK_PLUS1, NH_ON_ALWAYS),
+    NH_ROW(navhip_state_in, flock_tiles, 4, SK_PER_TILE, NH_ON_ALWAYS),
+};
+const nh_row sk_aux_rows[] = {
+    NH_ROW(navhip_state_aux_in, fstate, 1, NH_LEN_UNIT, NH_ON_ALWAYS),  NH_ROW(navhip_state_aux_in, wait_ticks_left, 4, NH_LEN_UNIT, NH_ON_ALWAYS),
+    NH_ROW(navhip_state_aux_in, wait_prev, 1, NH_LEN_UNIT, NH_ON_ALWAYS),  NH_ROW(navhip_state_aux_in, new_pos_xz, 8, NH_LEN_UNIT, NH_ON_ALWAYS),
+    NH_ROW(navhip_state_aux_in, ent_rot, 16, SK_PER_ARM_ROW, SK_TURN),  NH_ROW(navhip_state_aux_in, target_dir, 16, SK_PER_ARM_ROW, SK_TURN),
+    NH_ROW(navhip_state_aux_in, range_target, 4, SK_PER_ARM_ROW, SK_RANGE),
+    NH_ROW(navhip_state_aux_in, target_range, 4, SK_PER_ARM_ROW, SK_RANGE),
+    NH_ROW(navhip_state_aux_in, target_prev_xz, 8, SK_PER_ARM_ROW, SK_RANGE),
+    NH_ROW(navhip_state_aux_in, range_tiles_row, 4, SK_PER_ARM_ROW, SK_RANGE),
+    NH_ROW(navhip_state_aux_in, range_tiles_off, 4, SK_PER_RANGE_ROW_PLUS1, SK_RANGE),
+    NH_ROW_PAD(navhip_state_aux_in, range_tiles, 4, SK_PER_RANGE_TILE, SK_RANGE, 4),
+    NH_ROW(navhip_state_aux_in, surround_target, 4, SK_PER_ARM_ROW, SK_SURROUND),
+    NH_ROW(navhip_state_aux_in, surround_query, 1, SK_PER_ARM_ROW, SK_SURROUND),
+    NH_ROW(navhip_state_aux_in, surround_target_prev_xz, 8, SK_PER_ARM_ROW, SK_SURROUND),
+    NH_ROW(navhip_state_aux_in, surround_nearest_prev_xz, 8, SK_PER_ARM_ROW, SK_SURROUND),
+    NH_ROW(navhip_state_aux_in, surround_dest_xz, 16, SK_PER_ARM_ROW, SK_SURROUND),
+    NH_ROW(navhip_state_aux_in, vdes_xz, 8, NH_LEN_UNIT, SK_SURROUND),
+    NH_ROW_OUT_RANGE(navhip_state_aux_in, out_surround_dest_xz, 8, NH_LEN_UNIT, SK_SURROUND),
+    NH_ROW(navhip_state_aux_in, sparse_units, 4, SK_PER_LISTED, SK_SPARSE),
+};
+const nh_row sk_pass_out_rows[] = {
+    NH_ROW_OUT_RANGE(navhip_state_pass_out, state, 1, NH_LEN_UNIT, NH_ON_ALWAYS),  NH_ROW_OUT_RANGE(navhip_state_pass_out, flags, 1, NH_LEN_UNIT, NH_ON_ALWAYS),
+    NH_ROW_OUT_RANGE(navhip_state_pass_out, gate, 1, NH_LEN_UNIT, NH_ON_ALWAYS),  NH_ROW_OUT_RANGE(navhip_state_pass_out, new_pos_xz, 8, NH_LEN_UNIT, NH_ON_ALWAYS),
+    NH_ROW_OUT_RANGE(navhip_state_pass_out, vel_xz, 8, NH_LEN_UNIT, NH_ON_ALWAYS),  NH_ROW_OUT_RANGE(navhip_state_pass_out, wait_ticks_left, 4, NH_LEN_UNIT, SK_AUX),
+};
+const nh_row sk_settle_in_rows[] = {
+    NH_ROW(navhip_settle_in, zones, sizeof(navhip_arrival_zone), NH_LEN_ZONE, NH_ON_ALWAYS),
+    NH_ROW_PAD(navhip_settle_in, slots_xz, 8, NH_LEN_SLOT, NH_ON_ALWAYS, 8),  NH_ROW_PAD(navhip_settle_in, slot_ring, 4, NH_LEN_SLOT, NH_ON_ALWAYS, 4),
+    NH_ROW_PAD(navhip_settle_in, region_keys, 8, NH_LEN_KEY, NH_ON_ALWAYS, 8),  NH_ROW(navhip_settle_in, uid, 4, NH_LEN_QUERY, NH_ON_ALWAYS),
+    NH_ROW(navhip_settle_in, zone, 4, NH_LEN_QUERY, NH_ON_ALWAYS),  NH_ROW(navhip_settle_in, new_pos_xz, 8, NH_LEN_QUERY, NH_ON_ALWAYS),
+    NH_ROW(navhip_settle_in, nsettled, 4, NH_LEN_QUERY, NH_ON_ALWAYS),  NH_ROW(navhip_settle_in, substate, 1, NH_LEN_QUERY, NH_ON_ALWAYS),
+    NH_ROW(navhip_settle_in, sink_valid, 1, NH_LEN_QUERY, NH_ON_ALWAYS),  NH_ROW(navhip_settle_in, sink_xz, 8, NH_LEN_QUERY, NH_ON_ALWAYS),
+    NH_ROW(navhip_settle_in, order_pos_xz, 8, NH_LEN_QUERY, NH_ON_ALWAYS),  NH_ROW(navhip_settle_in, progress_anchor_xz, 8, NH_LEN_QUERY, NH_ON_ALWAYS),
+    NH_ROW(navhip_settle_in, progress_anchored, 1, NH_LEN_QUERY, NH_ON_ALWAYS),  NH_ROW(navhip_settle_in, stuck, 4, NH_LEN_QUERY, NH_ON_ALWAYS),
+};
+const nh_row sk_settle_out_rows[] = {
+    NH_ROW_OUT(navhip_settle_out, settle, 1, NH_LEN_QUERY, NH_ON_ALWAYS),  NH_ROW_OUT(navhip_settle_out, substate, 1, NH_LEN_QUERY, NH_ON_ALWAYS),
+    NH_ROW_OUT(navhip_settle_out, progress_anchor_xz, 8, NH_LEN_QUERY, NH_ON_ALWAYS),
+    NH_ROW_OUT(navhip_settle_out, progress_anchored, 1, NH_LEN_QUERY, NH_ON_ALWAYS),
+    NH_ROW_OUT(navhip_settle_out, stuck, 4, NH_LEN_QUERY, NH_ON_ALWAYS),  NH_ROW_OUT(navhip_settle_out, nsettled, 4, NH_LEN_QUERY, NH_ON_ALWAYS),
+};
+NH_COVERS(sk_gate_rows, navhip_gate_in, 0);
+NH_COVERS(sk_state_rows, navhip_state_in, 0);
+NH_COVERS(sk_aux_rows, navhip_state_aux_in, 16);            // n_range_rows, n_sparse: 4 bytes and 4 of padding each
+NH_COVERS(sk_pass_out_rows, navhip_state_pass_out, 0);
+NH_COVERS(sk_settle_in_rows, navhip_settle_in, 8);          // n_zones, nq
+NH_COVERS(sk_settle_out_rows, navhip_settle_out, 0);
 
-    // input rows [first, end) go up as one region, everything from row first_out on comes down as one -- when the
-    // context owns page-locked slabs (an asynchronous step path); per row otherwise
-    void region(navhip_ctx *ctx, int first, int end, int first_out)
-    {
-        const size_t i0 = rows[first].off, o0 = rows[first_out].off;
-        if(nh_async_slabs(ctx, rows[end].off - i0, total - o0, &h_in, &h_out) != NAVHIP_OK) return;
-        in_blk = i0; in_bytes = rows[end].off - i0; out_blk = o0; out_bytes = total - o0;
-        for(int i = first; i < end; i++) { rows[i].direct = false; rows[i].h_off = rows[i].off - i0; }
-        for(ret &o : rets) { o.direct = false; o.h_off = rows[o.row].off + o.lo * o.elem - o0; }
-    }
-    // in_bytes / out_bytes: what the caller asks nh_async_slabs for (h_in, h_out)
-    void pack()
-    {
-        gather = true;
-        for(row &r : rows) if(r.bytes && !(r.direct = nh_is_pinned(r.src))) { r.h_off = in_bytes; in_bytes += up(r.bytes); }
-        for(ret &o : rets) if(!(o.direct = nh_is_pinned(o.dst))) { o.h_off = out_bytes; out_bytes += up(o.cnt * o.elem); }
-        in_blk = total; out_blk = total + in_bytes;
-    }
-    int reserve(navhip_ctx *ctx, nh_stage_slot slot)
-    {
-        int rc = nh_stage_reserve(ctx, slot, total + (gather ? in_bytes + out_bytes + 256 : 0), (void**)&base);
-        if(rc) return rc;
-        for(row &r : rows) {
-            r.dev = base + (gather && !r.direct ? in_blk + r.h_off : r.off);
-            if(r.twin) *r.twin = r.dev;
-        }
-        return NAVHIP_OK;
-    }
-    int upload(navhip_ctx *ctx, hipStream_t s)
-    {
-        for(const row &r : rows) {
-            if(!r.bytes) continue;
-            if(r.direct) HIPCHK(ctx, hipMemcpyAsync(r.dev, r.src, r.bytes, hipMemcpyHostToDevice, s));
-            else         memcpy(h_in + r.h_off, r.src, r.bytes);
-        }
-        if(in_bytes) HIPCHK(ctx, hipMemcpyAsync(base + in_blk, h_in, in_bytes, hipMemcpyHostToDevice, s));
-        return NAVHIP_OK;
-    }
-    // the results, and the wait for them
-    int download(navhip_ctx *ctx, hipStream_t s)
-    {
-        for(const ret &o : rets) {
-            const char *d = rows[o.row].dev + o.lo * o.elem;
-            if(o.direct)    HIPCHK(ctx, hipMemcpyAsync((char*)o.dst + o.lo * o.elem, d, o.cnt * o.elem, hipMemcpyDeviceToHost, s));
-            else if(gather) HIPCHK(ctx, hipMemcpyAsync(base + out_blk + o.h_off, d, o.cnt * o.elem, hipMemcpyDeviceToDevice, s));
-        }
-        if(out_bytes) HIPCHK(ctx, hipMemcpyAsync(h_out, base + out_blk, out_bytes, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipStreamSynchronize(s));
-        for(const ret &o : rets) if(!o.direct) memcpy((char*)o.dst + o.lo * o.elem, h_out + o.h_off, o.cnt * o.elem);
-        return NAVHIP_OK;
-    }
+// the two structs of navhip_arrival_velocity
+const nh_row av_in_rows[] = {
+    NH_ROW(navhip_arrival_vel_in, zones, sizeof(navhip_arrival_zone), NH_LEN_ZONE, NH_ON_ALWAYS),
+    NH_ROW(navhip_arrival_vel_in, slots_xz, 8, NH_LEN_SLOT, NH_ON_ALWAYS),  NH_ROW(navhip_arrival_vel_in, slot_ring, 4, NH_LEN_SLOT, NH_ON_ALWAYS),
+    NH_ROW(navhip_arrival_vel_in, region_keys, 8, NH_LEN_KEY, NH_ON_ALWAYS),  NH_ROW(navhip_arrival_vel_in, zone_row, 4, NH_LEN_ZONE, NH_ON_ALWAYS),
+    NH_ROW(navhip_arrival_vel_in, com_row, 4, NH_LEN_ZONE, NH_ON_ALWAYS),  NH_ROW(navhip_arrival_vel_in, uid, 4, NH_LEN_QUERY, NH_ON_ALWAYS),
+    NH_ROW(navhip_arrival_vel_in, zone, 4, NH_LEN_QUERY, NH_ON_ALWAYS),  NH_ROW(navhip_arrival_vel_in, has_dest_los, 1, NH_LEN_QUERY, NH_ON_ALWAYS),
+    NH_ROW(navhip_arrival_vel_in, substate, 1, NH_LEN_QUERY, NH_ON_ALWAYS),  NH_ROW(navhip_arrival_vel_in, sink_valid, 1, NH_LEN_QUERY, NH_ON_ALWAYS),
+    NH_ROW(navhip_arrival_vel_in, sink_xz, 8, NH_LEN_QUERY, NH_ON_ALWAYS),  NH_ROW(navhip_arrival_vel_in, los_latched, 1, NH_LEN_QUERY, NH_ON_ALWAYS),
+    NH_ROW(navhip_arrival_vel_in, los_hyst, 4, NH_LEN_QUERY, NH_ON_ALWAYS),
 };
-
-// Which pointer member of an input / output struct is how large and when it travels: ONE list per struct for every
-// host-buffer path here (as nh_world_rows is for navhip_world).  sk_stage walks a list: staging a struct and building
-// its device twin is one loop.
-enum sk_len : uint8_t { SK_PER_UNIT, SK_PER_FLOCK, SK_PER_FLOCK_PLUS1, SK_PER_TILE, SK_PER_RANGE_ROW_PLUS1, SK_PER_RANGE_TILE,
-                        SK_PER_QUERY, SK_PER_ZONE, SK_PER_SLOT, SK_PER_KEY,
-                        SK_PER_ARM_ROW,       // a row per unit -- with sparse rows, per LISTED unit
-                        SK_PER_LISTED, SK_LEN_COUNT };
-enum sk_group : uint8_t { SK_ALWAYS, SK_SKIP, SK_TURN, SK_RANGE, SK_SURROUND, SK_INTERP, SK_SPARSE, SK_AUX,
-                          SK_DEV_ONLY,          // a member only the _dev form of a call reads: never staged
-                          SK_GROUP_COUNT };
-struct sk_row { size_t off; uint16_t elem; uint8_t len, group, pad; bool out; };
-struct sk_dims {
-    size_t len[SK_LEN_COUNT] = {};
-    bool   on[SK_GROUP_COUNT] = {true};     // SK_ALWAYS
-    size_t pad = 0;                         // at least this much tail padding on every row
-    size_t lo = 0, cnt = 0;                 // the rows of a per-unit / per-query result that go back
+const nh_row av_out_rows[] = {
+    NH_ROW_OUT(navhip_arrival_vel_out, vdes_xz, 8, NH_LEN_QUERY, NH_ON_ALWAYS),  NH_ROW_OUT(navhip_arrival_vel_out, status, 1, NH_LEN_QUERY, NH_ON_ALWAYS),
+    NH_ROW_OUT(navhip_arrival_vel_out, substate, 1, NH_LEN_QUERY, NH_ON_ALWAYS),  NH_ROW_OUT(navhip_arrival_vel_out, sink_valid, 1, NH_LEN_QUERY, NH_ON_ALWAYS),
+    NH_ROW_OUT(navhip_arrival_vel_out, sink_xz, 8, NH_LEN_QUERY, NH_ON_ALWAYS),  NH_ROW_OUT(navhip_arrival_vel_out, los_latched, 1, NH_LEN_QUERY, NH_ON_ALWAYS),
+    NH_ROW_OUT(navhip_arrival_vel_out, los_hyst, 4, NH_LEN_QUERY, NH_ON_ALWAYS),  NH_ROW_OUT(navhip_arrival_vel_out, dense_vdes_xz, 8, NH_LEN_QUERY, NH_ON_DEV_ONLY),
 };
-#define SK_ROW(T, member, elem, len, group) {offsetof(T, member), elem, len, group, 0, false}
-#define SK_ROW_PAD(T, member, elem, len, group, pad) {offsetof(T, member), elem, len, group, pad, false}
-#define SK_ROW_OUT(T, member, elem, len, group) {offsetof(T, member), elem, len, group, 0, true}
-const sk_row sk_gate_rows[] = {
-    SK_ROW(navhip_gate_in, next_rot, 16, SK_PER_UNIT, SK_ALWAYS),       SK_ROW(navhip_gate_in, new_vel_xz, 8, SK_PER_UNIT, SK_ALWAYS),
-    SK_ROW(navhip_gate_in, vdes_xz, 8, SK_PER_UNIT, SK_ALWAYS),         SK_ROW(navhip_gate_in, interp_from_xz, 8, SK_PER_UNIT, SK_INTERP),
-    SK_ROW(navhip_gate_in, interp_step, 4, SK_PER_UNIT, SK_INTERP),
-};
-const sk_row sk_state_rows[] = {
-    SK_ROW(navhip_state_in, new_pos_xz, 8, SK_PER_UNIT, SK_ALWAYS),     SK_ROW(navhip_state_in, vdes_xz, 8, SK_PER_UNIT, SK_ALWAYS),
-    SK_ROW(navhip_state_in, skip, 1, SK_PER_UNIT, SK_SKIP),             SK_ROW(navhip_state_in, flock_layer, 1, SK_PER_FLOCK, SK_ALWAYS),
-    SK_ROW(navhip_state_in, flock_nearest_xz, 8, SK_PER_FLOCK, SK_ALWAYS),
-    SK_ROW(navhip_state_in, flock_tiles_off, 4, SK_PER_FLOCK_PLUS1, SK_ALWAYS),
-    SK_ROW(navhip_state_in, flock_tiles, 4, SK_PER_TILE, SK_ALWAYS),
-};
-const sk_row sk_aux_rows[] = {
-    SK_ROW(navhip_state_aux_in, fstate, 1, SK_PER_UNIT, SK_ALWAYS),     SK_ROW(navhip_state_aux_in, wait_ticks_left, 4, SK_PER_UNIT, SK_ALWAYS),
-    SK_ROW(navhip_state_aux_in, wait_prev, 1, SK_PER_UNIT, SK_ALWAYS),  SK_ROW(navhip_state_aux_in, new_pos_xz, 8, SK_PER_UNIT, SK_ALWAYS),
-    SK_ROW(navhip_state_aux_in, ent_rot, 16, SK_PER_ARM_ROW, SK_TURN),  SK_ROW(navhip_state_aux_in, target_dir, 16, SK_PER_ARM_ROW, SK_TURN),
-    SK_ROW(navhip_state_aux_in, range_target, 4, SK_PER_ARM_ROW, SK_RANGE),
-    SK_ROW(navhip_state_aux_in, target_range, 4, SK_PER_ARM_ROW, SK_RANGE),
-    SK_ROW(navhip_state_aux_in, target_prev_xz, 8, SK_PER_ARM_ROW, SK_RANGE),
-    SK_ROW(navhip_state_aux_in, range_tiles_row, 4, SK_PER_ARM_ROW, SK_RANGE),
-    SK_ROW(navhip_state_aux_in, range_tiles_off, 4, SK_PER_RANGE_ROW_PLUS1, SK_RANGE),
-    SK_ROW_PAD(navhip_state_aux_in, range_tiles, 4, SK_PER_RANGE_TILE, SK_RANGE, 4),
-    SK_ROW(navhip_state_aux_in, surround_target, 4, SK_PER_ARM_ROW, SK_SURROUND),
-    SK_ROW(navhip_state_aux_in, surround_query, 1, SK_PER_ARM_ROW, SK_SURROUND),
-    SK_ROW(navhip_state_aux_in, surround_target_prev_xz, 8, SK_PER_ARM_ROW, SK_SURROUND),
-    SK_ROW(navhip_state_aux_in, surround_nearest_prev_xz, 8, SK_PER_ARM_ROW, SK_SURROUND),
-    SK_ROW(navhip_state_aux_in, surround_dest_xz, 16, SK_PER_ARM_ROW, SK_SURROUND),
-    SK_ROW(navhip_state_aux_in, vdes_xz, 8, SK_PER_UNIT, SK_SURROUND),
-    SK_ROW_OUT(navhip_state_aux_in, out_surround_dest_xz, 8, SK_PER_UNIT, SK_SURROUND),
-    SK_ROW(navhip_state_aux_in, sparse_units, 4, SK_PER_LISTED, SK_SPARSE),
-};
-const sk_row sk_pass_out_rows[] = {
-    SK_ROW_OUT(navhip_state_pass_out, state, 1, SK_PER_UNIT, SK_ALWAYS),      SK_ROW_OUT(navhip_state_pass_out, flags, 1, SK_PER_UNIT, SK_ALWAYS),
-    SK_ROW_OUT(navhip_state_pass_out, gate, 1, SK_PER_UNIT, SK_ALWAYS),       SK_ROW_OUT(navhip_state_pass_out, new_pos_xz, 8, SK_PER_UNIT, SK_ALWAYS),
-    SK_ROW_OUT(navhip_state_pass_out, vel_xz, 8, SK_PER_UNIT, SK_ALWAYS),     SK_ROW_OUT(navhip_state_pass_out, wait_ticks_left, 4, SK_PER_UNIT, SK_AUX),
-};
-const sk_row sk_settle_in_rows[] = {
-    SK_ROW(navhip_settle_in, zones, sizeof(navhip_arrival_zone), SK_PER_ZONE, SK_ALWAYS),
-    SK_ROW_PAD(navhip_settle_in, slots_xz, 8, SK_PER_SLOT, SK_ALWAYS, 8),     SK_ROW_PAD(navhip_settle_in, slot_ring, 4, SK_PER_SLOT, SK_ALWAYS, 4),
-    SK_ROW_PAD(navhip_settle_in, region_keys, 8, SK_PER_KEY, SK_ALWAYS, 8),   SK_ROW(navhip_settle_in, uid, 4, SK_PER_QUERY, SK_ALWAYS),
-    SK_ROW(navhip_settle_in, zone, 4, SK_PER_QUERY, SK_ALWAYS),               SK_ROW(navhip_settle_in, new_pos_xz, 8, SK_PER_QUERY, SK_ALWAYS),
-    SK_ROW(navhip_settle_in, nsettled, 4, SK_PER_QUERY, SK_ALWAYS),           SK_ROW(navhip_settle_in, substate, 1, SK_PER_QUERY, SK_ALWAYS),
-    SK_ROW(navhip_settle_in, sink_valid, 1, SK_PER_QUERY, SK_ALWAYS),         SK_ROW(navhip_settle_in, sink_xz, 8, SK_PER_QUERY, SK_ALWAYS),
-    SK_ROW(navhip_settle_in, order_pos_xz, 8, SK_PER_QUERY, SK_ALWAYS),       SK_ROW(navhip_settle_in, progress_anchor_xz, 8, SK_PER_QUERY, SK_ALWAYS),
-    SK_ROW(navhip_settle_in, progress_anchored, 1, SK_PER_QUERY, SK_ALWAYS),  SK_ROW(navhip_settle_in, stuck, 4, SK_PER_QUERY, SK_ALWAYS),
-};
-const sk_row sk_settle_out_rows[] = {
-    SK_ROW_OUT(navhip_settle_out, settle, 1, SK_PER_QUERY, SK_ALWAYS),        SK_ROW_OUT(navhip_settle_out, substate, 1, SK_PER_QUERY, SK_ALWAYS),
-    SK_ROW_OUT(navhip_settle_out, progress_anchor_xz, 8, SK_PER_QUERY, SK_ALWAYS),
-    SK_ROW_OUT(navhip_settle_out, progress_anchored, 1, SK_PER_QUERY, SK_ALWAYS),
-    SK_ROW_OUT(navhip_settle_out, stuck, 4, SK_PER_QUERY, SK_ALWAYS),         SK_ROW_OUT(navhip_settle_out, nsettled, 4, SK_PER_QUERY, SK_ALWAYS),
-};
-#undef SK_ROW
-#undef SK_ROW_PAD
-#undef SK_ROW_OUT
-// a new pointer member breaks the build here until its list has a row for it
-#define SK_COVERS(tab, T, scalar_bytes) \
-    static_assert(sizeof(T) == sizeof(tab) / sizeof(tab[0]) * sizeof(void*) + (scalar_bytes), #T " changed: does " #tab " cover it?")
-SK_COVERS(sk_gate_rows, navhip_gate_in, 0);
-SK_COVERS(sk_state_rows, navhip_state_in, 0);
-SK_COVERS(sk_aux_rows, navhip_state_aux_in, 16);            // n_range_rows, n_sparse: 4 bytes and 4 of padding each
-SK_COVERS(sk_pass_out_rows, navhip_state_pass_out, 0);
-SK_COVERS(sk_settle_in_rows, navhip_settle_in, 8);          // n_zones, nq
-SK_COVERS(sk_settle_out_rows, navhip_settle_out, 0);
-#undef SK_COVERS
-
-// the two structs of navhip_arrival_velocity: the same lists, the same guard (under their own macro names: the lists above
-// are the state pass's, counted as such)
-#define AV_ROW(T, member, elem, len) {offsetof(T, member), elem, len, SK_ALWAYS, 0, false}
-#define AV_ROW_OUT(T, member, elem, group) {offsetof(T, member), elem, SK_PER_QUERY, group, 0, true}
-const sk_row av_in_rows[] = {
-    AV_ROW(navhip_arrival_vel_in, zones, sizeof(navhip_arrival_zone), SK_PER_ZONE),
-    AV_ROW(navhip_arrival_vel_in, slots_xz, 8, SK_PER_SLOT),          AV_ROW(navhip_arrival_vel_in, slot_ring, 4, SK_PER_SLOT),
-    AV_ROW(navhip_arrival_vel_in, region_keys, 8, SK_PER_KEY),        AV_ROW(navhip_arrival_vel_in, zone_row, 4, SK_PER_ZONE),
-    AV_ROW(navhip_arrival_vel_in, com_row, 4, SK_PER_ZONE),           AV_ROW(navhip_arrival_vel_in, uid, 4, SK_PER_QUERY),
-    AV_ROW(navhip_arrival_vel_in, zone, 4, SK_PER_QUERY),             AV_ROW(navhip_arrival_vel_in, has_dest_los, 1, SK_PER_QUERY),
-    AV_ROW(navhip_arrival_vel_in, substate, 1, SK_PER_QUERY),         AV_ROW(navhip_arrival_vel_in, sink_valid, 1, SK_PER_QUERY),
-    AV_ROW(navhip_arrival_vel_in, sink_xz, 8, SK_PER_QUERY),          AV_ROW(navhip_arrival_vel_in, los_latched, 1, SK_PER_QUERY),
-    AV_ROW(navhip_arrival_vel_in, los_hyst, 4, SK_PER_QUERY),
-};
-const sk_row av_out_rows[] = {
-    AV_ROW_OUT(navhip_arrival_vel_out, vdes_xz, 8, SK_ALWAYS),        AV_ROW_OUT(navhip_arrival_vel_out, status, 1, SK_ALWAYS),
-    AV_ROW_OUT(navhip_arrival_vel_out, substate, 1, SK_ALWAYS),       AV_ROW_OUT(navhip_arrival_vel_out, sink_valid, 1, SK_ALWAYS),
-    AV_ROW_OUT(navhip_arrival_vel_out, sink_xz, 8, SK_ALWAYS),        AV_ROW_OUT(navhip_arrival_vel_out, los_latched, 1, SK_ALWAYS),
-    AV_ROW_OUT(navhip_arrival_vel_out, los_hyst, 4, SK_ALWAYS),       AV_ROW_OUT(navhip_arrival_vel_out, dense_vdes_xz, 8, SK_DEV_ONLY),
-};
-#undef AV_ROW
-#undef AV_ROW_OUT
-static_assert(sizeof(navhip_arrival_vel_in) == sizeof(av_in_rows) / sizeof(av_in_rows[0]) * sizeof(void*) + 16,
-              "navhip_arrival_vel_in changed: does av_in_rows cover it?");       // n_zones, nq, n_slots, n_keys
-static_assert(sizeof(navhip_arrival_vel_out) == sizeof(av_out_rows) / sizeof(av_out_rows[0]) * sizeof(void*),
-              "navhip_arrival_vel_out changed: does av_out_rows cover it?");
-
-bool sk_listed(std::initializer_list<size_t> members, size_t off)
-{
-    for(size_t m : members) if(m == off) return true;
-    return false;
-}
-
-// Stage the members of *in whose group is on, and have reserve() point the same members of *twin at the device copies.
-// elsewhere: members this caller does not take from *in (another pass produces them on the device): it sets them in *twin.
-template<class T, size_t N>
-void sk_stage(sk_plan &p, const sk_row (&tab)[N], const T *in, T *twin, const sk_dims &D, std::initializer_list<size_t> elsewhere = {})
-{
-    for(const sk_row &r : tab) {
-        if(!D.on[r.group] || sk_listed(elsewhere, r.off)) continue;
-        const size_t bytes = D.len[r.len] * r.elem;
-        if(r.out) p.out(p.scratch(bytes, &nh_member(twin, r.off)), (void*)nh_member(in, r.off), r.elem, D.lo, D.cnt);
-        else      p.in(nh_member(in, r.off), bytes, D.pad > r.pad ? D.pad : r.pad, &nh_member(twin, r.off));
-    }
-}
-
-// ... and the listed arrays of the snapshot (nh_world_rows knows their sizes)
-void sk_stage_world(sk_plan &p, const navhip_world *w, navhip_world *twin, const sk_dims &D, std::initializer_list<size_t> members,
-                    size_t nmembers = 0, size_t pad = 0)
-{
-    for(const nh_world_row &r : nh_world_rows) {
-        if(!sk_listed(members, r.off)) continue;
-        const size_t cnt = r.count == NH_PER_ENT ? D.len[SK_PER_UNIT] : r.count == NH_PER_FLOCK ? D.len[SK_PER_FLOCK]
-                         : r.count == NH_PER_FLOCK_PLUS1 ? D.len[SK_PER_FLOCK_PLUS1] : nmembers;
-        p.in(nh_member(w, r.off), cnt * r.row_bytes, D.pad > pad ? D.pad : pad, &nh_member(twin, r.off));
-    }
-}
-#define SK_W(member) offsetof(navhip_world, member)
-
-// the scalars of the world, no array: what is not staged must not travel as a host pointer
-navhip_world sk_device_world(const navhip_world *w)
-{
-    navhip_world d = *w;
-    for(const nh_world_row &r : nh_world_rows) nh_member(&d, r.off) = nullptr;
-    return d;
-}
-
-void sk_map_view(const navhip_ctx *ctx, const navhip_world *w, nh_step_params *P)
-{
-    memset(P, 0, sizeof(*P));
-    nh_fill_map_view(ctx, &P->map);
-    P->map_x = w->map_pos_x; P->map_z = w->map_pos_z;
-    P->n_ents = w->n_ents; P->hz = w->hz;
-}
+NH_COVERS(av_in_rows, navhip_arrival_vel_in, 16);           // n_zones, nq, n_slots, n_keys
+NH_COVERS(av_out_rows, navhip_arrival_vel_out, 0);
 
 bool sk_work_range(const navhip_world *w, int *b, int *e)
 {
@@ -961,12 +807,12 @@ bool sk_work_range(const navhip_world *w, int *b, int *e)
     return *b >= 0 && *e <= w->n_ents && *b <= *e;
 }
 
-sk_dims sk_dims_of(const navhip_world *w, int b, int e)
+nh_dims sk_dims_of(const navhip_world *w, int b, int e)
 {
-    sk_dims D;
-    D.len[SK_PER_UNIT] = D.len[SK_PER_ARM_ROW] = (size_t)w->n_ents;
-    D.len[SK_PER_FLOCK] = (size_t)(w->n_flocks > 0 ? w->n_flocks : 0);
-    D.len[SK_PER_FLOCK_PLUS1] = D.len[SK_PER_FLOCK] + 1;
+    nh_dims D;
+    D.len[NH_LEN_UNIT] = D.len[SK_PER_ARM_ROW] = (size_t)w->n_ents;
+    D.len[NH_LEN_FLOCK] = (size_t)(w->n_flocks > 0 ? w->n_flocks : 0);
+    D.len[NH_LEN_FLOCK_PLUS1] = D.len[NH_LEN_FLOCK] + 1;
     D.lo = (size_t)b; D.cnt = (size_t)(e - b);
     return D;
 }
@@ -1027,7 +873,7 @@ bool sk_check_aux(const navhip_world *w, const navhip_state_aux_in *in, sk_aux_c
 // long the range tables are.  hw: the snapshot where the host has it; NULL in the resident pass, where states and flocks
 // are on the device: then every row with a range target is checked whatever its unit's state, row 0 passes when there
 // are no rows at all (what a unit of another state holds), and a surround unit's flock is not looked at.
-bool sk_check_arm_rows(const navhip_state_aux_in *in, int n_ents, const navhip_world *hw, size_t v0, size_t v1, sk_dims *D)
+bool sk_check_arm_rows(const navhip_state_aux_in *in, int n_ents, const navhip_world *hw, size_t v0, size_t v1, nh_dims *D)
 {
     D->on[SK_TURN] = in->ent_rot != nullptr; D->on[SK_RANGE] = in->range_target != nullptr; D->on[SK_SURROUND] = in->surround_target != nullptr;
     if(in->range_target) {
@@ -1058,6 +904,7 @@ bool sk_check_settle(const navhip_settle_in *in, const navhip_settle_out *out)
         && out->progress_anchor_xz && out->progress_anchored && out->stuck;
 }
 
+#define AV_FAIL(why) nh_fail(ctx, NAVHIP_ERR_ARG, name, why)     /* inside the check below: `name` is the form's */
 // The one argument check of navhip_arrival_velocity and navhip_arrival_velocity_dev; host_arrays: the arrays can be read
 // here (the host form), so what lies IN them is checked too.  Fills in the two mapping tables, the pool and how many rows
 // each table has.  The reason of a refusal goes to last_error.
@@ -1067,43 +914,39 @@ int av_check(navhip_ctx *ctx, const navhip_world *w, const navhip_arrival_vel_in
 {
     if(!ctx) return NAVHIP_ERR_ARG;
     const char *name = host_arrays ? "navhip_arrival_velocity: " : "navhip_arrival_velocity_dev: ";
-    auto fail = [&](const std::string &why) { ctx->last_error = name + why; return NAVHIP_ERR_ARG; };
-    if(!w || !in || !out) return fail("a missing argument");
-    if(in->nq < 0) return fail("nq < 0");
-    if(in->n_zones < 0 || in->n_slots < 0 || in->n_keys < 0 || w->n_ents < 0) return fail("a negative count");
+    if(!w || !in || !out) return AV_FAIL("a missing argument");
+    if(in->nq < 0) return AV_FAIL("nq < 0");
+    if(in->n_zones < 0 || in->n_slots < 0 || in->n_keys < 0 || w->n_ents < 0) return AV_FAIL("a negative count");
     if(in->nq == 0) return NAVHIP_OK;
-    if(!w->pos_xz) return fail("a missing array: world->pos_xz");
-    if(in->n_zones > 0 && (!in->zones || !in->zone_row || !in->com_row)) return fail("a missing array: zones, zone_row or com_row");
+    if(!w->pos_xz) return AV_FAIL("a missing array: world->pos_xz");
+    if(in->n_zones > 0 && (!in->zones || !in->zone_row || !in->com_row)) return AV_FAIL("a missing array: zones, zone_row or com_row");
     if((in->n_slots > 0 && (!in->slots_xz || !in->slot_ring)) || (in->n_keys > 0 && !in->region_keys))
-        return fail("a missing array: slots_xz, slot_ring or region_keys");
+        return AV_FAIL("a missing array: slots_xz, slot_ring or region_keys");
     if(!in->uid || !in->zone || !in->has_dest_los || !in->substate || !in->sink_valid || !in->sink_xz || !in->los_latched || !in->los_hyst)
-        return fail("a missing array of navhip_arrival_vel_in");
+        return AV_FAIL("a missing array of navhip_arrival_vel_in");
     if(!out->status || !out->substate || !out->sink_valid || !out->sink_xz || !out->los_latched || !out->los_hyst)
-        return fail("a missing array of navhip_arrival_vel_out");
+        return AV_FAIL("a missing array of navhip_arrival_vel_out");
     if(host_arrays ? (!out->vdes_xz || out->dense_vdes_xz) : (!out->vdes_xz && !out->dense_vdes_xz))
-        return fail(host_arrays ? "vdes_xz missing, or dense_vdes_xz given to the host form" : "neither vdes_xz nor dense_vdes_xz");
+        return AV_FAIL(host_arrays ? "vdes_xz missing, or dense_vdes_xz given to the host form" : "neither vdes_xz nor dense_vdes_xz");
     T->resident = w->n_field_slots == NAVHIP_POOL_RESIDENT;
     if(T->resident) {
-        if(!ctx->pool) return fail("NAVHIP_POOL_RESIDENT without a resident pool");
+        if(!ctx->pool) return AV_FAIL("NAVHIP_POOL_RESIDENT without a resident pool");
         T->com_slot = T->zone_slot = nh_pool_map(ctx); T->pool = nh_pool_fields(ctx);
         T->n_com_rows = T->n_zone_rows = nh_pool_dests(ctx);
     }else{
         T->com_slot = w->flock_field_slot; T->zone_slot = w->region_field_slot; T->pool = w->field_pool;
         T->n_com_rows = T->com_slot && w->n_flocks > 0 ? w->n_flocks : 0;
         T->n_zone_rows = T->zone_slot && w->n_region_rows > 0 ? w->n_region_rows : 0;
-        if((T->n_com_rows || T->n_zone_rows) && (!T->pool || w->n_field_slots < 1)) return fail("a mapping table without field_pool");
+        if((T->n_com_rows || T->n_zone_rows) && (!T->pool || w->n_field_slots < 1)) return AV_FAIL("a mapping table without field_pool");
     }
     if(!host_arrays) return NAVHIP_OK;
     for(int z = 0; z < in->n_zones; z++) {
         const navhip_arrival_zone &Z = in->zones[z];
         const std::string zn = "zone " + std::to_string(z);
-        if(Z.slot_begin < 0 || Z.slot_end < Z.slot_begin || Z.slot_end > in->n_slots) return fail(zn + ": its slot range leaves slots_xz / slot_ring");
-        if(Z.key_begin < 0 || Z.key_end < Z.key_begin || Z.key_end > in->n_keys) return fail(zn + ": its key range leaves region_keys");
-        for(int k = Z.key_begin + 1; k < Z.key_end; k++)
-            if(!(in->region_keys[k] > in->region_keys[k - 1])) return fail(zn + ": region_keys not ascending");
-        if(Z.layer < 0 || Z.layer >= NAVHIP_NAV_LAYER_MAX) return fail(zn + ": layer outside the map's");
-        if(in->zone_row[z] < -1 || in->zone_row[z] >= T->n_zone_rows) return fail(zn + ": zone_row outside region_field_slot");
-        if(in->com_row[z] < -1 || in->com_row[z] >= T->n_com_rows) return fail(zn + ": com_row outside flock_field_slot");
+        if(const char *fault = nh_zone_fault(Z, nullptr, in->n_slots, in->n_keys, 0, in->region_keys)) return AV_FAIL(zn + fault);
+        if(Z.layer < 0 || Z.layer >= NAVHIP_NAV_LAYER_MAX) return AV_FAIL(zn + ": layer outside the map's");
+        if(in->zone_row[z] < -1 || in->zone_row[z] >= T->n_zone_rows) return AV_FAIL(zn + ": zone_row outside region_field_slot");
+        if(in->com_row[z] < -1 || in->com_row[z] >= T->n_com_rows) return AV_FAIL(zn + ": com_row outside flock_field_slot");
     }
     return NAVHIP_OK;
 }
@@ -1126,7 +969,7 @@ int navhip_heading_gate_dev(navhip_ctx *ctx, const navhip_world *w, const navhip
         if(rc) return rc;
     }
     nh_step_params P;
-    sk_map_view(ctx, w, &P);
+    nh_step_params_init(ctx, w, &P);
     if(e > b)
         hipLaunchKernelGGL(k_heading_gate, dim3((e - b + 255) / 256), dim3(256), 0, stream ? (hipStream_t)stream : ctx->stream,
                            P, b, e, w->pos_xz, w->vel_xz, w->state, w->radius, w->flags, *in, out_vel, out_new_pos, out_gate);
@@ -1143,15 +986,15 @@ int navhip_heading_gate(navhip_ctx *ctx, const navhip_world *w, const navhip_gat
     if(!sk_check_gate(w, in) || !sk_work_range(w, &b, &e)) return NAVHIP_ERR_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    sk_dims D = sk_dims_of(w, b, e);
+    nh_dims D = sk_dims_of(w, b, e);
     D.on[SK_INTERP] = in->interp_from_xz != nullptr;
     const size_t n = (size_t)w->n_ents;
-    sk_plan P;
-    navhip_world d = sk_device_world(w);
+    nh_plan P;
+    navhip_world d = nh_device_world(w);
     navhip_gate_in di = {};
-    sk_stage_world(P, w, &d, D, {SK_W(pos_xz), SK_W(vel_xz), SK_W(state)});
-    if(D.on[SK_INTERP]) sk_stage_world(P, w, &d, D, {SK_W(radius), SK_W(flags)});
-    sk_stage(P, sk_gate_rows, in, &di, D);
+    nh_plan_world(P, w, &d, D, {NH_W(pos_xz), NH_W(vel_xz), NH_W(state)});
+    if(D.on[SK_INTERP]) nh_plan_world(P, w, &d, D, {NH_W(radius), NH_W(flags)});
+    nh_plan_rows(P, sk_gate_rows, in, &di, D);
     float *d_vel, *d_pos; uint8_t *d_gate;
     P.out(P.scratch(n * 8, (void**)&d_vel), out_vel, 8, D.lo, D.cnt);
     P.out(P.scratch(n * 8, (void**)&d_pos), out_new_pos, 8, D.lo, D.cnt);
@@ -1174,7 +1017,7 @@ int navhip_state_update_dev(navhip_ctx *ctx, const navhip_world *w, const navhip
     int rc = nh_refresh_derived(ctx, ctx->stream);
     if(rc) return rc;
     nh_step_params P;
-    sk_map_view(ctx, w, &P);
+    nh_step_params_init(ctx, w, &P);
     P.n_flocks = w->n_flocks;
     if(!sk_work_range(w, &P.work_begin, &P.work_end)) return NAVHIP_ERR_INVALID;
     P.pos_xz = w->pos_xz; P.radius = w->radius; P.flags = w->flags; P.state = w->state; P.flock = w->flock;
@@ -1197,8 +1040,8 @@ int navhip_state_update(navhip_ctx *ctx, const navhip_world *w, const navhip_sta
     if(w->n_flocks > 0 && (!w->flock_offsets || !in->flock_tiles_off)) return NAVHIP_ERR_INVALID;
     int b, e;
     if(!sk_work_range(w, &b, &e)) return NAVHIP_ERR_INVALID;
-    sk_dims D = sk_dims_of(w, b, e);
-    const size_t n = (size_t)w->n_ents, F = D.len[SK_PER_FLOCK];
+    nh_dims D = sk_dims_of(w, b, e);
+    const size_t n = (size_t)w->n_ents, F = D.len[NH_LEN_FLOCK];
     D.len[SK_PER_TILE] = F ? (size_t)in->flock_tiles_off[F] : 0;
     if(F && (size_t)w->flock_offsets[F] > n) {     // (an entity belongs to at most one flock: the scratch of the arrived-mate rule is sized by it)
         ctx->last_error = "navhip_state_update: more flock members than entities";
@@ -1215,13 +1058,13 @@ int navhip_state_update(navhip_ctx *ctx, const navhip_world *w, const navhip_sta
     hipStream_t s = ctx->stream;
     // the arrays of the snapshot that k_state_update reads: the world's own staging slots (nh_world_rows)
     navhip_world d;
-    int rc = nh_stage_world(ctx, w, &d, s, {SK_W(pos_xz), SK_W(radius), SK_W(flags), SK_W(state), SK_W(flock), SK_W(flock_target_xz),
-                                            SK_W(flock_offsets), SK_W(flock_members)});
+    int rc = nh_stage_world(ctx, w, &d, s, {NH_W(pos_xz), NH_W(radius), NH_W(flags), NH_W(state), NH_W(flock), NH_W(flock_target_xz),
+                                            NH_W(flock_offsets), NH_W(flock_members)});
     if(rc) return rc;
     // navhip_state_in and the two results: one copy per row
-    sk_plan P;
+    nh_plan P;
     navhip_state_in di = {};
-    sk_stage(P, sk_state_rows, in, &di, D);
+    nh_plan_rows(P, sk_state_rows, in, &di, D);
     uint8_t *d_state, *d_flags;
     P.out(P.scratch(n, (void**)&d_state), out_state, 1, D.lo, D.cnt);
     P.out(P.scratch(n, (void**)&d_flags), out_flags, 1, D.lo, D.cnt);
@@ -1242,7 +1085,7 @@ int navhip_state_update_aux_dev(navhip_ctx *ctx, const navhip_world *w, const na
     if(!sk_check_aux(w, in, SK_AUX_ALONE) || !sk_work_range(w, &b, &e)) return NAVHIP_ERR_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     nh_step_params P;
-    sk_map_view(ctx, w, &P);
+    nh_step_params_init(ctx, w, &P);
     P.work_begin = b; P.work_end = e;
     if(in->surround_target) { P.flock = w->flock; P.flock_target_xz = w->flock_target_xz; P.vel_xz = w->vel_xz; P.n_flocks = w->n_flocks; }
     if(e > b)
@@ -1259,23 +1102,23 @@ int navhip_state_update_aux(navhip_ctx *ctx, const navhip_world *w, const navhip
     if(w->n_ents == 0) return NAVHIP_OK;
     int b, e;
     if(!sk_check_aux(w, in, SK_AUX_ALONE) || !sk_work_range(w, &b, &e)) return NAVHIP_ERR_INVALID;
-    sk_dims D = sk_dims_of(w, b, e);
+    nh_dims D = sk_dims_of(w, b, e);
     if(!sk_check_arm_rows(in, w->n_ents, w, (size_t)b, (size_t)e, &D)) return NAVHIP_ERR_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const size_t n = (size_t)w->n_ents;
-    sk_plan P;
-    navhip_world d = sk_device_world(w);
+    nh_plan P;
+    navhip_world d = nh_device_world(w);
     navhip_state_aux_in di = {};
     if(D.on[SK_RANGE]) di.n_range_rows = in->n_range_rows;
-    sk_stage_world(P, w, &d, D, {SK_W(radius), SK_W(flags), SK_W(state)});
+    nh_plan_world(P, w, &d, D, {NH_W(radius), NH_W(flags), NH_W(state)});
     // (only the enter-range and surround arms read positions)
-    if(D.on[SK_RANGE] || D.on[SK_SURROUND]) sk_stage_world(P, w, &d, D, {SK_W(pos_xz)});
+    if(D.on[SK_RANGE] || D.on[SK_SURROUND]) nh_plan_world(P, w, &d, D, {NH_W(pos_xz)});
     if(D.on[SK_SURROUND]) {
-        sk_stage_world(P, w, &d, D, {SK_W(vel_xz), SK_W(flock)});
-        sk_stage_world(P, w, &d, D, {SK_W(flock_target_xz)}, 0, 8);
+        nh_plan_world(P, w, &d, D, {NH_W(vel_xz), NH_W(flock)});
+        nh_plan_world(P, w, &d, D, {NH_W(flock_target_xz)}, 0, 8);
     }
-    sk_stage(P, sk_aux_rows, in, &di, D);
+    nh_plan_rows(P, sk_aux_rows, in, &di, D);
     uint8_t *d_state, *d_flags; int32_t *d_ticks;
     P.out(P.in(io_state, n, 0, (void**)&d_state), io_state, 1, D.lo, D.cnt);
     P.out(P.in(io_flags, n, 0, (void**)&d_flags), io_flags, 1, D.lo, D.cnt);
@@ -1330,8 +1173,8 @@ int navhip_state_pass(navhip_ctx *ctx, const navhip_world *w, const navhip_state
     if(w->n_flocks < 0 || !sk_check_gate(w, &G) || !sk_check_state(w, &T) || (aux && !sk_check_aux(w, &X, SK_PASS))
     || !out->state || !out->flags || !out->gate || !out->new_pos_xz || (aux && !out->wait_ticks_left) || !sk_work_range(w, &b, &e))
         return NAVHIP_ERR_INVALID;
-    sk_dims D = sk_dims_of(w, b, e);
-    const size_t n = (size_t)w->n_ents, F = D.len[SK_PER_FLOCK];
+    nh_dims D = sk_dims_of(w, b, e);
+    const size_t n = (size_t)w->n_ents, F = D.len[NH_LEN_FLOCK];
     // (offsets that are not a CSR become a huge size_t below -- INVALID, not NOMEM)
     if(!sk_csr_ok(w->flock_offsets, F) || !sk_csr_ok(T.flock_tiles_off, F) || (F && (size_t)w->flock_offsets[F] > n)
     || (aux && !sk_check_arm_rows(&X, w->n_ents, w, (size_t)b, (size_t)e, &D))) return NAVHIP_ERR_INVALID;
@@ -1340,17 +1183,17 @@ int navhip_state_pass(navhip_ctx *ctx, const navhip_world *w, const navhip_state
     D.pad = 8;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    sk_plan P;
-    navhip_world d = sk_device_world(w);
+    nh_plan P;
+    navhip_world d = nh_device_world(w);
     navhip_gate_in dg = {}; navhip_state_in ds = {}; navhip_state_aux_in da = {}; navhip_state_pass_out r = {};
     if(D.on[SK_RANGE]) da.n_range_rows = X.n_range_rows;
     // the snapshot, once
-    sk_stage_world(P, w, &d, D, {SK_W(pos_xz), SK_W(vel_xz), SK_W(radius), SK_W(flags), SK_W(state), SK_W(flock), SK_W(flock_target_xz),
-                                 SK_W(flock_offsets), SK_W(flock_members)}, F ? (size_t)w->flock_offsets[F] : 0);
-    sk_stage(P, sk_gate_rows, &G, &dg, D);
-    sk_stage(P, sk_state_rows, &T, &ds, D, {offsetof(navhip_state_in, new_pos_xz), offsetof(navhip_state_in, vdes_xz)});
-    if(aux) sk_stage(P, sk_aux_rows, &X, &da, D, {offsetof(navhip_state_aux_in, new_pos_xz), offsetof(navhip_state_aux_in, vdes_xz)});
-    sk_stage(P, sk_pass_out_rows, out, &r, D);
+    nh_plan_world(P, w, &d, D, {NH_W(pos_xz), NH_W(vel_xz), NH_W(radius), NH_W(flags), NH_W(state), NH_W(flock), NH_W(flock_target_xz),
+                                 NH_W(flock_offsets), NH_W(flock_members)}, F ? (size_t)w->flock_offsets[F] : 0);
+    nh_plan_rows(P, sk_gate_rows, &G, &dg, D);
+    nh_plan_rows(P, sk_state_rows, &T, &ds, D, {offsetof(navhip_state_in, new_pos_xz), offsetof(navhip_state_in, vdes_xz)});
+    if(aux) nh_plan_rows(P, sk_aux_rows, &X, &da, D, {offsetof(navhip_state_aux_in, new_pos_xz), offsetof(navhip_state_aux_in, vdes_xz)});
+    nh_plan_rows(P, sk_pass_out_rows, out, &r, D);
     int rc = P.reserve(ctx, NH_STAGE_STATE_ARENA);
     if(!rc) rc = P.upload(ctx, s);
     if(!rc) rc = sk_run_passes(ctx, &d, b, e, dg, ds, aux ? &da : nullptr, r, nullptr, 0, nullptr, s);
@@ -1383,8 +1226,8 @@ int navhip_state_pass_resident(navhip_ctx *ctx, const navhip_state_pass_in *in, 
     const size_t ns = sp ? (size_t)X.n_sparse : 0;
     for(size_t k = 0; k < ns; k++)
         if(X.sparse_units[k] < b || X.sparse_units[k] >= e) return NAVHIP_ERR_INVALID;
-    sk_dims D = sk_dims_of(&d, b, e);
-    const size_t F = D.len[SK_PER_FLOCK];
+    nh_dims D = sk_dims_of(&d, b, e);
+    const size_t F = D.len[NH_LEN_FLOCK];
     // (the checks of the arms walk the rows of their arrays: the listed units', or the slab's)
     if(!sk_csr_ok(T.flock_tiles_off, F)
     || (aux && !sk_check_arm_rows(&X, d.n_ents, nullptr, sp ? 0 : (size_t)b, sp ? ns : (size_t)e, &D))) return NAVHIP_ERR_INVALID;
@@ -1396,16 +1239,16 @@ int navhip_state_pass_resident(navhip_ctx *ctx, const navhip_state_pass_in *in, 
     hipStream_t s = ctx->stream;
     // ---- inputs: one device slab; pageable arrays are packed into the pinned slab and cross the bus as ONE transfer,
     // pinned ones (navhip_host_alloc) are transferred in place.  Results: rows [b, e) of each, likewise
-    sk_plan I, R;
+    nh_plan I, R;
     navhip_gate_in dg = {}; navhip_state_in ds = {}; navhip_state_aux_in da = {}, dense = {}; navhip_state_pass_out r = {};
     if(D.on[SK_RANGE]) da.n_range_rows = X.n_range_rows;
-    sk_stage(I, sk_gate_rows, &G, &dg, D, {offsetof(navhip_gate_in, new_vel_xz), offsetof(navhip_gate_in, vdes_xz)});
-    sk_stage(I, sk_state_rows, &T, &ds, D, {offsetof(navhip_state_in, new_pos_xz), offsetof(navhip_state_in, vdes_xz)});
-    if(aux) sk_stage(I, sk_aux_rows, &X, &da, D, {offsetof(navhip_state_aux_in, new_pos_xz), offsetof(navhip_state_aux_in, vdes_xz),
+    nh_plan_rows(I, sk_gate_rows, &G, &dg, D, {offsetof(navhip_gate_in, new_vel_xz), offsetof(navhip_gate_in, vdes_xz)});
+    nh_plan_rows(I, sk_state_rows, &T, &ds, D, {offsetof(navhip_state_in, new_pos_xz), offsetof(navhip_state_in, vdes_xz)});
+    if(aux) nh_plan_rows(I, sk_aux_rows, &X, &da, D, {offsetof(navhip_state_aux_in, new_pos_xz), offsetof(navhip_state_aux_in, vdes_xz),
                                                   offsetof(navhip_state_aux_in, out_surround_dest_xz)});
     // (sparse: the dense twins the arm kernels read, filled on the device)
-    if(sp) for(const sk_row &t : sk_aux_rows) if(t.len == SK_PER_ARM_ROW && D.on[t.group]) I.scratch(n * t.elem, &nh_member(&dense, t.off));
-    sk_stage(R, sk_pass_out_rows, out, &r, D);
+    if(sp) for(const nh_row &t : sk_aux_rows) if(t.len == SK_PER_ARM_ROW && D.on[t.group]) I.scratch(n * t.elem, &nh_member(&dense, t.off));
+    nh_plan_rows(R, sk_pass_out_rows, out, &r, D);
     float *d_vdes, *d_sdest = nullptr, *d_listed = nullptr;     // (sparse: the surround positions of the listed units)
     R.scratch(n * 8, (void**)&d_vdes);
     if(su) { const int k = R.scratch(n * 8, (void**)&d_sdest); if(!sp) R.out(k, X.out_surround_dest_xz, 8, D.lo, D.cnt); }
@@ -1472,11 +1315,11 @@ static int sk_settled_count(navhip_ctx *ctx, const navhip_world *w, int nq, cons
         ctx->last_error = "navhip_settled_count_resident: no completed host-buffer step of this size is resident on the device";
         return NAVHIP_ERR_INVALID;
     }
-    sk_plan P;
+    nh_plan P;
     if(!resident) {
         // (a snapshot the velocity pass left on the device is read in place: the tick's tables are the same)
         d = *w;
-        sk_stage_world(P, w, &d, sk_dims_of(w, 0, 0), {SK_W(pos_xz), SK_W(radius), SK_W(flags), SK_W(state)});
+        nh_plan_world(P, w, &d, sk_dims_of(w, 0, 0), {NH_W(pos_xz), NH_W(radius), NH_W(flags), NH_W(state)});
     }
     d.grid_xmin = w->grid_xmin; d.grid_xmax = w->grid_xmax; d.grid_zmin = w->grid_zmin; d.grid_zmax = w->grid_zmax;
     int32_t *d_uid, *d_cnt, *d_out; float *d_q; uint32_t *d_ids;
@@ -1513,7 +1356,7 @@ int navhip_arrival_settle_dev(navhip_ctx *ctx, const navhip_world *w, const navh
     if(!w->vel_xz || !w->radius || !in->nsettled || !sk_check_settle(in, out)) return NAVHIP_ERR_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     nh_step_params P;
-    sk_map_view(ctx, w, &P);
+    nh_step_params_init(ctx, w, &P);
     hipLaunchKernelGGL(k_arrival_settle, dim3((in->nq + 15) / 16), dim3(256), 0, stream ? (hipStream_t)stream : ctx->stream,
                        P, w->vel_xz, w->radius, *in, *out);
     HIPCHK(ctx, hipGetLastError());
@@ -1548,26 +1391,25 @@ static int sk_arrival_settle(navhip_ctx *ctx, const navhip_world *w, const navhi
         if(in->uid[q] < 0 || in->uid[q] >= w->n_ents || in->zone[q] < 0 || in->zone[q] >= in->n_zones) return NAVHIP_ERR_INVALID;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    sk_dims D = sk_dims_of(w, 0, 0);
-    D.len[SK_PER_ZONE] = nz; D.len[SK_PER_SLOT] = n_slots; D.len[SK_PER_KEY] = n_keys; D.len[SK_PER_QUERY] = nq;
-    D.cnt = nq;
-    sk_plan P;
+    nh_dims D = sk_dims_of(w, 0, 0);
+    D.len[NH_LEN_ZONE] = nz; D.len[NH_LEN_SLOT] = n_slots; D.len[NH_LEN_KEY] = n_keys; D.len[NH_LEN_QUERY] = nq;
+    nh_plan P;
     navhip_world d = *w;
     // (the snapshot the velocity half left on the device is read in place: movestate.velocity and the radii are the tick's)
     if(resident) { d.vel_xz = rw.vel_xz; d.radius = rw.radius; }
-    else sk_stage_world(P, w, &d, D, {SK_W(vel_xz), SK_W(radius)});
+    else nh_plan_world(P, w, &d, D, {NH_W(vel_xz), NH_W(radius)});
     // (the inputs of the arm side by side, the results at the end: a context with an asynchronous step path owns
     // page-locked slabs, and each region then crosses the bus once)
     navhip_settle_in di = *in;
     navhip_settle_out dout = {};
     const int first_in = (int)P.rows.size();
-    sk_stage(P, sk_settle_in_rows, in, &di, D, {offsetof(navhip_settle_in, nsettled)});
+    nh_plan_rows(P, sk_settle_in_rows, in, &di, D, {offsetof(navhip_settle_in, nsettled)});
     if(!count_here) P.in(in->nsettled, nq * 4, 0, (void**)&di.nsettled);
     float *d_q; int32_t *d_cnt; uint32_t *d_ids;
     const int end_in = P.scratch(count_here ? nq * 8 : 0, (void**)&d_q);
     P.scratch(count_here ? nq * 4 : 0, (void**)&d_cnt); P.scratch(count_here ? nq * SK_QUERY_MAX * 4 : 0, (void**)&d_ids);
     const int first_out = (int)P.rows.size();
-    sk_stage(P, sk_settle_out_rows, out, &dout, D, {offsetof(navhip_settle_out, nsettled)});
+    nh_plan_rows(P, sk_settle_out_rows, out, &dout, D, {offsetof(navhip_settle_out, nsettled)});
     if(count_here) P.out(P.scratch(nq * 4, (void**)&di.nsettled), out->nsettled, 4, 0, nq);
     P.region(ctx, first_in, end_in, first_out);
     int rc = P.reserve(ctx, NH_STAGE_STATE_ARENA);
@@ -1606,7 +1448,7 @@ int navhip_arrival_velocity_dev(navhip_ctx *ctx, const navhip_world *w, const na
     if(rc || in->nq == 0) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     nh_step_params P;
-    sk_map_view(ctx, w, &P);
+    nh_step_params_init(ctx, w, &P);
     P.pos_xz = w->pos_xz;
     P.flock_field_slot = T.com_slot; P.region_field_slot = T.zone_slot; P.field_pool = T.pool;
     hipLaunchKernelGGL(k_arrival_velocity, dim3((in->nq + 15) / 16), dim3(256), 0, stream ? (hipStream_t)stream : ctx->stream,
@@ -1623,13 +1465,13 @@ int navhip_arrival_velocity(navhip_ctx *ctx, const navhip_world *w, const navhip
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const size_t nchunks = (size_t)ctx->nchunks;
-    sk_dims D = sk_dims_of(w, 0, 0);
-    D.len[SK_PER_ZONE] = (size_t)in->n_zones; D.len[SK_PER_SLOT] = (size_t)in->n_slots; D.len[SK_PER_KEY] = (size_t)in->n_keys;
-    D.len[SK_PER_QUERY] = D.cnt = (size_t)in->nq;
+    nh_dims D = sk_dims_of(w, 0, 0);
+    D.len[NH_LEN_ZONE] = (size_t)in->n_zones; D.len[NH_LEN_SLOT] = (size_t)in->n_slots; D.len[NH_LEN_KEY] = (size_t)in->n_keys;
+    D.len[NH_LEN_QUERY] = (size_t)in->nq;
     D.pad = 16;                                                             // (no array of a zone-less or slot-less call is empty)
-    sk_plan P;
-    navhip_world d = sk_device_world(w);
-    sk_stage_world(P, w, &d, D, {SK_W(pos_xz)});
+    nh_plan P;
+    navhip_world d = nh_device_world(w);
+    nh_plan_world(P, w, &d, D, {NH_W(pos_xz)});
     if(!T.resident) {
         // the world's own tables, as the step stages them (rows of -1 .. : see navhip_world)
         if(T.n_com_rows) P.in(w->flock_field_slot, (size_t)T.n_com_rows * nchunks * 4, D.pad, (void**)&d.flock_field_slot);
@@ -1638,8 +1480,8 @@ int navhip_arrival_velocity(navhip_ctx *ctx, const navhip_world *w, const navhip
     }
     navhip_arrival_vel_in di = *in;
     navhip_arrival_vel_out dout = {};
-    sk_stage(P, av_in_rows, in, &di, D);
-    sk_stage(P, av_out_rows, out, &dout, D);
+    nh_plan_rows(P, av_in_rows, in, &di, D);
+    nh_plan_rows(P, av_out_rows, out, &dout, D);
     rc = P.reserve(ctx, NH_STAGE_STATE_ARENA);
     if(!rc) rc = P.upload(ctx, s);
     if(rc) return rc;

@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "navhip_internal.h"
+#include "stage_plan.h"
 #include "agent_internal.h"
 #include "agent_math.h"         // nav_layer_for
 #include "lane_group.h"
@@ -303,11 +304,7 @@ __global__ __launch_bounds__(64) void k_surround_pick(dq_map M, uint32_t stride_
     }
 }
 
-static int sq_fail(navhip_ctx *ctx, const std::string &why)
-{
-    ctx->last_error = "navhip_surround_queries: " + why;
-    return NAVHIP_ERR_ARG;
-}
+#define SQ_FAIL(why) nh_fail(ctx, NAVHIP_ERR_ARG, "navhip_surround_queries: ", why)
 
 // Entity_NavLayerWithRadius on the host: nav_layer_for (agent_math.h) is device code in the device build
 static int sq_host_layer(uint32_t flags, float radius)
@@ -326,7 +323,7 @@ static int sq_launch(navhip_ctx *ctx, const navhip_world *w, const float *new_ve
     if(rc) return rc;
     const bool st = target_set && ctx->static_sets_n > 0;
     const size_t stride = st && ctx->static_sets_longest > SQ_TILES ? (size_t)ctx->static_sets_longest : (size_t)SQ_TILES;
-    if((size_t)nq * stride > 0xffffffffull) return sq_fail(ctx, "too many rows for one call: " + std::to_string(nq));
+    if((size_t)nq * stride > 0xffffffffull) return SQ_FAIL("too many rows for one call: " + std::to_string(nq));
     // scratch: the item count, the rows' records, the work items, the tile answers, sized from nq and the longest registered
     // list (grown on demand: nothing is allocated after the first call at a given nq and table)
     const size_t rows_off = 256, items_off = rows_off + nh_up256(sizeof(sq_row) * (size_t)nq);
@@ -422,11 +419,11 @@ int navhip_surround_queries_ex_dev(navhip_ctx *ctx, const navhip_world *w, const
                                    float *out_dest_xz, void *stream)
 {
     if(!ctx) return NAVHIP_ERR_ARG;
-    if(nq < 0) return sq_fail(ctx, "a negative count");
+    if(nq < 0) return SQ_FAIL("a negative count");
     if(!w || (nq > 0 && (!w->pos_xz || !w->radius || !w->flags || !new_vel_xz || !target || !out_query || !out_dest_xz)))
-        return sq_fail(ctx, "a missing array");
+        return SQ_FAIL("a missing array");
     if(!units && nq != w->n_ents)
-        return sq_fail(ctx, "the dense form has one row per entity: nq " + std::to_string(nq) + ", n_ents " + std::to_string(w->n_ents));
+        return SQ_FAIL("the dense form has one row per entity: nq " + std::to_string(nq) + ", n_ents " + std::to_string(w->n_ents));
     if(nq == 0) return NAVHIP_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     return sq_launch(ctx, w, new_vel_xz, units, target, target_set, nq, out_query, out_dest_xz, stream ? (hipStream_t)stream : ctx->stream);
@@ -442,44 +439,47 @@ int navhip_surround_queries_ex(navhip_ctx *ctx, const navhip_world *w, const flo
                                const int32_t *target, const int32_t *target_set, int nq, uint8_t *out_query, float *out_dest_xz)
 {
     if(!ctx) return NAVHIP_ERR_ARG;
-    if(nq < 0) return sq_fail(ctx, "a negative count");
+    if(nq < 0) return SQ_FAIL("a negative count");
     if(!w || !w->pos_xz || !w->radius || !w->flags || !new_vel_xz || !target || !out_query || !out_dest_xz)
-        return sq_fail(ctx, "a missing array");
+        return SQ_FAIL("a missing array");
     if(!units && nq != w->n_ents)
-        return sq_fail(ctx, "the dense form has one row per entity: nq " + std::to_string(nq) + ", n_ents " + std::to_string(w->n_ents));
+        return SQ_FAIL("the dense form has one row per entity: nq " + std::to_string(nq) + ", n_ents " + std::to_string(w->n_ents));
     // every row, before anything is launched
     for(int k = 0; k < nq; k++) {
         const int u = units ? units[k] : k;
         const std::string row = "row " + std::to_string(k);
-        if(u < 0 || u >= w->n_ents) return sq_fail(ctx, row + ": unit " + std::to_string(u) + " is outside the world");
+        if(u < 0 || u >= w->n_ents) return SQ_FAIL(row + ": unit " + std::to_string(u) + " is outside the world");
         const navhip_layer &L = ctx->layers[sq_host_layer(w->flags[u], w->radius[u])];
         if(!L.cost || !L.blockers || !L.islands)
-            return sq_fail(ctx, row + ": its unit's layer has no resident cost / blockers / islands planes");
+            return SQ_FAIL(row + ": its unit's layer has no resident cost / blockers / islands planes");
         const int t = target[k];
         if(target_set && t >= 0 && t < w->n_ents && !(w->flags[t] & NAVHIP_ENTITY_FLAG_MOVABLE)
            && (target_set[k] < 0 || target_set[k] >= ctx->static_sets_n))
-            return sq_fail(ctx, row + ": set " + std::to_string(target_set[k]) + " of its static target is outside the table of "
+            return SQ_FAIL(row + ": set " + std::to_string(target_set[k]) + " of its static target is outside the table of "
                                 + std::to_string(ctx->static_sets_n) + " sets");
     }
     if(nq == 0) return NAVHIP_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     navhip_world d;
-    const float *d_vel; const int32_t *d_units, *d_target, *d_set;
+    const float *d_vel; const int32_t *d_units = nullptr, *d_target, *d_set = nullptr;
     uint8_t *d_query; float *d_dest;
+    const size_t rows = (size_t)nq;
+    // the three arrays of the snapshot in the world's own slots (which drops a resident snapshot), the rest in one arena
     int rc = nh_stage_world(ctx, w, &d, s, {offsetof(navhip_world, pos_xz), offsetof(navhip_world, radius), offsetof(navhip_world, flags)});
-    if(!rc) rc = nh_stage_in(ctx, NH_STAGE_CALL0, new_vel_xz, 8 * (size_t)w->n_ents, (const void**)&d_vel, s);
-    if(!rc) rc = nh_stage_in(ctx, NH_STAGE_CALL1, units, 4 * (size_t)nq, (const void**)&d_units, s);
-    if(!rc) rc = nh_stage_in(ctx, NH_STAGE_CALL2, target, 4 * (size_t)nq, (const void**)&d_target, s);
-    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_CALL3, (size_t)nq, (void**)&d_query);
-    if(!rc) rc = nh_stage_reserve(ctx, NH_STAGE_CALL4, 16 * (size_t)nq, (void**)&d_dest);
-    if(!rc) rc = nh_stage_in(ctx, NH_STAGE_CALL5, target_set, 4 * (size_t)nq, (const void**)&d_set, s);
-    if(!rc) rc = sq_launch(ctx, &d, d_vel, d_units, d_target, d_set, nq, d_query, d_dest, s);
     if(rc) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(out_query, d_query, (size_t)nq, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(out_dest_xz, d_dest, 16 * (size_t)nq, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    return NAVHIP_OK;
+    nh_plan P;
+    P.in(new_vel_xz, 8 * (size_t)w->n_ents, 16, (void**)&d_vel);
+    if(units) P.in(units, 4 * rows, 0, (void**)&d_units);
+    P.in(target, 4 * rows, 0, (void**)&d_target);
+    if(target_set) P.in(target_set, 4 * rows, 0, (void**)&d_set);
+    P.out(P.scratch(rows, (void**)&d_query), out_query, 1, 0, rows);
+    P.out(P.scratch(16 * rows, (void**)&d_dest), out_dest_xz, 16, 0, rows);
+    rc = P.reserve(ctx, NH_STAGE_CALL0);
+    if(!rc) rc = P.upload(ctx, s);
+    if(!rc) rc = sq_launch(ctx, &d, d_vel, d_units, d_target, d_set, nq, d_query, d_dest, s);
+    if(!rc) rc = P.download(ctx, s);
+    return rc;
 }
 
 int navhip_surround_queries(navhip_ctx *ctx, const navhip_world *w, const float *new_vel_xz, const int32_t *units,

@@ -497,32 +497,40 @@ def test_agent_kernel_units_hold_their_own_kernels_and_one_unit_includes_the_gro
 
 
 def test_state_staging_tables_cover_every_array():
-    """csrc/state_kernels.hip stages the input and output structs of the state half of the tick from ONE list per
-    struct (sk_gate_rows, sk_state_rows, sk_aux_rows, sk_pass_out_rows, sk_settle_in_rows, sk_settle_out_rows): each
-    pointer member declared in include/navhip.h has exactly one row in the list of its struct, with the element size of
-    its declared type, and each list is guarded by a static_assert on the size of its struct."""
+    """The units whose host-buffer forms stage whole structs (csrc/state_kernels.hip, arrival_flock_kernels.hip,
+    arrival_build_kernels.hip) do so from ONE list per struct on the plan of csrc/stage_plan.h (sk_gate_rows,
+    sk_state_rows, sk_aux_rows, sk_pass_out_rows, sk_settle_in_rows, sk_settle_out_rows, av_*_rows, af_*_rows,
+    ab_*_rows): each pointer member declared in include/navhip.h has exactly one row in the list of its struct, with the
+    element size of its declared type, and each list is guarded by a static_assert on the size of its struct."""
     hdr = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    src = open(os.path.join(ROOT, "permafrost-engine_amd", "csrc", "state_kernels.hip")).read()
-    rows = re.findall(r"\bSK_ROW(?:_PAD|_OUT)?\((navhip_\w+),\s*(\w+),\s*([\w() ]+?),\s*SK_PER_\w+,\s*SK_\w+", src)
+    csrc = os.path.join(ROOT, "permafrost-engine_amd", "csrc")
+    plan = open(os.path.join(csrc, "stage_plan.h")).read()
+    assert re.search(r"#define NH_COVERS\(tab, T, scalar_bytes\) \\\n\s*static_assert\(sizeof\(T\) == ", plan)
     width = {"float": 4, "int32_t": 4, "uint32_t": 4, "int16_t": 2, "uint8_t": 1, "uint64_t": 8}
-    structs = ("navhip_gate_in", "navhip_state_in", "navhip_state_aux_in", "navhip_state_pass_out", "navhip_settle_in",
-               "navhip_settle_out")
-    assert sorted(set(s for s, _, _ in rows)) == sorted(structs)
-    for struct in structs:
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), hdr, re.S).group(1)
-        members = {}
-        for decl in re.findall(r"(?:const\s+)?(\w+)\s*(\*[^;]*);", body):
-            for name in re.findall(r"\*\s*(\w+)", decl[1]):
-                members[name] = decl[0]
-        assert members
-        mine = [(m, e) for s, m, e in rows if s == struct]
-        assert sorted(m for m, _ in mine) == sorted(members), (struct, sorted(set(members) ^ set(m for m, _ in mine)))
-        for m, e in mine:
-            if members[m] in width:            # a row's element is a whole number of the declared type: [n][2] floats = 8
-                assert int(e) % width[members[m]] == 0, (struct, m, e)
-            else:
-                assert e == "sizeof(%s)" % members[m], (struct, m, e)
-    tables = re.findall(r"^const sk_row (sk_\w+_rows)\[\]", src, re.M)
-    guards = re.findall(r"^SK_COVERS\((sk_\w+_rows), (navhip_\w+),", src, re.M)
-    assert len(tables) == len(structs) and sorted(tables) == sorted(t for t, _ in guards)
-    assert sorted(s for _, s in guards) == sorted(structs)
+    units = {"state_kernels.hip": ("navhip_gate_in", "navhip_state_in", "navhip_state_aux_in", "navhip_state_pass_out",
+                                   "navhip_settle_in", "navhip_settle_out", "navhip_arrival_vel_in", "navhip_arrival_vel_out"),
+             "arrival_flock_kernels.hip": ("navhip_arrival_flock_in", "navhip_arrival_flock_out"),
+             "arrival_build_kernels.hip": ("navhip_arrival_build_in", "navhip_arrival_build_out")}
+    for unit, structs in units.items():
+        src = open(os.path.join(csrc, unit)).read()
+        assert '#include "stage_plan.h"' in src and "struct nh_plan" not in src, unit
+        rows = re.findall(r"\bNH_ROW(?:_PAD|_OUT|_OUT_PAD|_OUT_RANGE|_IO)?\((navhip_\w+),\s*(\w+),\s*([\w() ]+?),\s*(?:NH_LEN|SK_PER)_\w+,\s*(?:NH_ON|SK)_\w+", src)
+        assert sorted(set(s for s, _, _ in rows)) == sorted(structs), unit
+        for struct in structs:
+            body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), hdr, re.S).group(1)
+            members = {}
+            for decl in re.findall(r"(?:const\s+)?(\w+)\s*(\*[^;]*);", body):
+                for name in re.findall(r"\*\s*(\w+)", decl[1]):
+                    members[name] = decl[0]
+            assert members
+            mine = [(m, e) for s, m, e in rows if s == struct]
+            assert sorted(m for m, _ in mine) == sorted(members), (struct, sorted(set(members) ^ set(m for m, _ in mine)))
+            for m, e in mine:
+                if members[m] in width:            # a row's element is a whole number of the declared type: [n][2] floats = 8
+                    assert int(e) % width[members[m]] == 0, (struct, m, e)
+                else:
+                    assert e == "sizeof(%s)" % members[m], (struct, m, e)
+        tables = re.findall(r"^const nh_row (\w+_rows)\[\]", src, re.M)
+        guards = re.findall(r"^NH_COVERS\((\w+_rows), (navhip_\w+),", src, re.M)
+        assert len(tables) == len(structs) and sorted(tables) == sorted(t for t, _ in guards), unit
+        assert sorted(s for _, s in guards) == sorted(structs), unit
